@@ -23,6 +23,13 @@ plumbing case (configs[0]) as `cartpole_config1`.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
         --master-addr 127.0.0.1 --master-port 29500 bench.py --gpus 8 ...
 
+A plain run sets up, warms up, times exactly --steps steps and prints the
+headline.  Everything else -- the measured HBM peak, the per-kernel tables and
+rooflines, the CPU baselines, the other BASELINE configs as extra keys, the
+longer repeat of a short window, the all-gather on its own, the detail file --
+is measured with --full.  --dump-outputs DIR writes what the timed path handed
+its caller after its last step as DIR/<name>.npy.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -36,7 +43,9 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 achievable
-MIN_WINDOW_S = 0.5      # a timed window shorter than this is repeated over more steps
+MIN_WINDOW_S = 0.5      # --full: a timed window shorter than this is repeated over more steps
+DUMP_BUDGET_BYTES = 64 * 1024 * 1024    # --dump-outputs: all files together
+INPUT_TENSORS = ("action", "reset")     # exported tensors the caller writes
 # instruction issue (the yardstick of the kernels that HBM says nothing about):
 # 256 CUs x 4 SIMDs; a wavefront issues at most one instruction every ~4 cycles
 # (MI355X_MICROARCH.md, "8 issue slots of ~4 cyc" per 32-cycle MFMA at one wave
@@ -252,14 +261,56 @@ def parse_args():
                         "carry 15-40 %% more contacts than the steady state the "
                         "metric is about; part of the synthetic-data preparation, "
                         "not of the warm-up)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="measure everything besides the headline: HBM peak, per-kernel "
+                        "tables and rooflines, CPU baselines, the other BASELINE "
+                        "configs, the longer window behind a short one, the detail "
+                        "file (a plain run only times the --steps window)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write the tensors the simulator exports "
+                        "to its caller (all but its inputs; with --gpus N the gathered "
+                        "observation tensors, on rank 0) as DIR/<name>.npy: float32 "
+                        "for floating-point and 1-2 byte integer types, float64 for "
+                        "wider integers, at most 64 MB in all (a larger tensor is "
+                        "written as a fixed, seeded sample of its rows)")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="--full without the CPU baselines")
     p.add_argument("--no-secondary", action="store_true",
-                   help="skip the configs[1] (physics off, 4096 worlds) measurement")
+                   help="--full without the other BASELINE configs")
     p.add_argument("--profile-reps", type=int, default=30)
     p.add_argument("--force-collective", action="store_true",
                    help="run the RCCL observation all-gather even with one rank "
                         "(exercises the multi-GPU code path on a 1-GPU box)")
     return p.parse_args()
+
+
+def dump_outputs(arrays, out_dir):
+    """--dump-outputs: one DIR/<name>.npy per array, DUMP_BUDGET_BYTES in all.
+    Arrays are taken smallest first, each up to an even share of what is left;
+    one larger than its share is written as a sample of its rows (sorted, drawn
+    with numpy seed 0), the same rows in every run of the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def out_type(a):
+        return np.dtype(np.float32 if a.dtype.kind == "f" or a.dtype.itemsize <= 2
+                        else np.float64)
+
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    order = sorted(arrays, key=lambda k: arrays[k].size * out_type(arrays[k]).itemsize)
+    left = DUMP_BUDGET_BYTES
+    for i, name in enumerate(order):
+        a = arrays[name]
+        t = out_type(a)
+        share = left // (len(order) - i)
+        if a.size * t.itemsize > share and a.ndim and len(a):
+            row_bytes = max(a[0].size * t.itemsize, 1)
+            keep = max(1, min(len(a), share // row_bytes))
+            rows = np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))
+            a = a[rows]
+        a = a.astype(t)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def measure_hbm_bandwidth(seconds=0.2):
@@ -840,10 +891,12 @@ def cpu_raycast_sample(sim, worlds, resolution, sample_worlds=8192):
 
 
 def run_render(worlds, gpu_id, seed, denom, steps, warmup, profile_reps, settle,
-               resolution=64, cpu_sample=True):
+               resolution=64, cpu_sample=True, extras=True, dump=None):
     """BASELINE.json configs[4]: the physics Escape Room + the batch ray caster,
     resolution^2 RGB-D per agent.  A step = one replay of the step graph followed
-    by one replay of the render graph (TLAS build + ray cast of every view)."""
+    by one replay of the render graph (TLAS build + ray cast of every view).
+    extras=False: the timed window only (no kernel tables, roofline or CPU
+    sample); dump(sim) is called right after the timed steps."""
     import torch
     from madrona_amd.simlib import Simulator, hip_lib_path
 
@@ -873,14 +926,26 @@ def run_render(worlds, gpu_id, seed, denom, steps, warmup, profile_reps, settle,
         dt = time.perf_counter() - t0
         rt.mwhip_mark_window(sim.hip_exec(), 2)
         sim.sync()
-        step_stats = sim.profile(profile_reps)
-        render_stats = sim.profile(profile_reps, graph=render)
-        cpu_views = cpu_raycast_sample(sim, worlds, resolution) if cpu_sample else None
+        if dump is not None:
+            dump(sim)
         views = worlds * AGENTS["escape_room_phys"]
         # instances per world: floor, 4 borders, 2 agents, 3 x (2 walls, door, 4
         # cubes, 2 buttons)
         instances = 34
-    ms = dt / steps * 1e3
+        ms = dt / steps * 1e3
+        out = {
+            "workload": f"Escape-Room + XPBD + batch ray caster, {resolution}x{resolution} "
+                        f"RGB-D per agent, {worlds} worlds (BASELINE.json configs[4]), "
+                        f"{views} views, {instances} instances/world, 1 directional light, "
+                        f"auto-reset p=1/{denom} per world per step",
+            "value": worlds * steps / dt, "unit": "steps/s", "ms_per_step": ms,
+            "steps": steps, "warmup": warmup,
+        }
+        if not extras:
+            return out
+        step_stats = sim.profile(profile_reps)
+        render_stats = sim.profile(profile_reps, graph=render)
+        cpu_views = cpu_raycast_sample(sim, worlds, resolution) if cpu_sample else None
     rays = views * resolution * resolution
     cast = [k for k in render_stats if "raycast" in k["name"]]
     tlas = [k for k in render_stats if "tlas" in k["name"]]
@@ -891,13 +956,7 @@ def run_render(worlds, gpu_id, seed, denom, steps, warmup, profile_reps, settle,
     cast_traffic, cast_traffic_src = traffic_for(
         recorded_traffic(), "escape_room_render", worlds, "render:raycast",
         per_launch=True)
-    out = {
-        "workload": f"Escape-Room + XPBD + batch ray caster, {resolution}x{resolution} "
-                    f"RGB-D per agent, {worlds} worlds (BASELINE.json configs[4]), "
-                    f"{views} views, {instances} instances/world, 1 directional light, "
-                    f"auto-reset p=1/{denom} per world per step",
-        "value": worlds * steps / dt, "unit": "steps/s", "ms_per_step": ms,
-        "steps": steps, "warmup": warmup,
+    out.update({
         "step_graph_us": round(sum(k["avg_us"] for k in step_stats), 1),
         "render_graph_us": round(sum(k["avg_us"] for k in render_stats), 1),
         "primary_rays_per_s": rays / (cast_us * 1e-6) if cast_us > 0 else None,
@@ -920,7 +979,7 @@ def run_render(worlds, gpu_id, seed, denom, steps, warmup, profile_reps, settle,
         "kernels": [{"name": k["name"], "avg_us": round(k["avg_us"], 2)}
                     for k in render_stats],
         "tlas_build_us": round(sum(k["avg_us"] for k in tlas), 2),
-    }
+    })
     issue = issue_roofline(
         "render:raycast (same kernel, instruction-issue yardstick)",
         "escape_room_render", worlds, "render:raycast", cast_us, 3,
@@ -1032,10 +1091,16 @@ def main():
         if args.settle < 0:
             args.settle = 200
         worlds = args.worlds
-        hbm_measured = measure_hbm_bandwidth()
+        hbm_measured = measure_hbm_bandwidth() if args.full else None
+        dump = None
+        if args.dump_outputs:
+            def dump(sim):
+                dump_outputs({n: sim.read_tensor(n) for n in sim.tensor_names
+                              if n not in INPUT_TENSORS}, args.dump_outputs)
         r = run_render(worlds, local_rank, 5, args.auto_reset_denom, args.steps,
                        args.warmup, args.profile_reps, args.settle,
-                       cpu_sample=not args.no_cpu_baseline)
+                       cpu_sample=not args.no_cpu_baseline, extras=args.full,
+                       dump=dump)
         out = {
             "metric": "aggregate env steps/sec", "value": r["value"], "unit": "steps/s",
             "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -1047,18 +1112,22 @@ def main():
                        "worlds_per_gpu": worlds, "settle_steps": args.settle,
                        "total_worlds": worlds, "dist_world_size": 1,
                        "parallelism": "worlds sharded over 1 GPU(s)"},
-            "roofline": dict(r["roofline"], peak_measured=hbm_measured),
-            "cpu_baseline": r["cpu_baseline_render_pass"],
-            "render": {k: r[k] for k in ("step_graph_us", "render_graph_us",
-                                         "primary_rays_per_s",
-                                         "views_per_s_render_pass", "tlas_build_us",
-                                         "kernels")},
+            "roofline": None,
+            "cpu_baseline": None,
         }
+        if args.full:
+            out["roofline"] = dict(r["roofline"], peak_measured=hbm_measured)
+            out["cpu_baseline"] = r["cpu_baseline_render_pass"]
+            out["render"] = {k: r[k] for k in ("step_graph_us", "render_graph_us",
+                                               "primary_rays_per_s",
+                                               "views_per_s_render_pass",
+                                               "tlas_build_us", "kernels")}
         import ctypes
         ctypes.CDLL(None).fflush(None)
         sys.stdout.flush()
         os.dup2(saved_stdout, 1)
-        print(json.dumps(driver_line(out, write_detail(out))), flush=True)
+        print(json.dumps(driver_line(out, write_detail(out) if args.full else None)),
+              flush=True)
         return
 
     import torch
@@ -1081,7 +1150,7 @@ def main():
     from madrona_amd.simlib import Simulator, hip_lib_path, runtime_lib
 
     # the spec peak next to what this box's HBM delivers
-    hbm_measured = measure_hbm_bandwidth() if rank == 0 else None
+    hbm_measured = measure_hbm_bandwidth() if rank == 0 and args.full else None
 
     shard = shard_for(rank, world_size, worlds_per_rank=args.worlds)
     seed = 5
@@ -1140,31 +1209,34 @@ def main():
     value = total_worlds * args.steps / elapsed
     ms_per_step = elapsed / args.steps * 1e3
 
-    # A window this short (the driver's --steps 20 is ~25 ms) says little: it is
-    # repeated over enough steps for MIN_WINDOW_S, and THAT window is the line's
-    # `value` / `ms_per_step`; the --steps window stays next to it as
-    # `short_window`.
+    per_rank_ms = [round(t / args.steps * 1e3, 5) for t in per_rank]
+
+    # what the timed path handed its caller after its last step: the gathered
+    # observation tensors with --gpus N, else every tensor the simulator exports
+    if args.dump_outputs and rank == 0:
+        if distributed:
+            arrays = {n: t.cpu().numpy() for n, t in sharded._global.items()}
+        else:
+            arrays = {n: sim.read_tensor(n) for n in sim.tensor_names
+                      if n not in INPUT_TENSORS}
+        dump_outputs(arrays, args.dump_outputs)
+
+    # --full: a window this short (--steps 20 of the headline is ~16 ms) says
+    # little: it is repeated over enough steps for MIN_WINDOW_S and reported next
+    # to the line's `value` / `ms_per_step`, which stay the --steps window's
     long_window = None
-    short_window = None
-    if elapsed < MIN_WINDOW_S:
+    if args.full and elapsed < MIN_WINDOW_S:
         more = int(math.ceil(MIN_WINDOW_S / max(elapsed / args.steps, 1e-7)))
         el2, per_rank2 = timed(more, mark=False)
         long_window = {"steps": more, "seconds": round(el2, 4),
                        "ms_per_step": el2 / more * 1e3,
-                       "value": total_worlds * more / el2}
-        short_window = {"steps": args.steps, "seconds": round(elapsed, 5),
-                        "ms_per_step": ms_per_step, "value": value,
-                        "per_rank_ms_per_step":
-                            [round(t / args.steps * 1e3, 5) for t in per_rank]}
-        value = long_window["value"]
-        ms_per_step = long_window["ms_per_step"]
-        per_rank_ms = [round(t / more * 1e3, 5) for t in per_rank2]
-    else:
-        per_rank_ms = [round(t / args.steps * 1e3, 5) for t in per_rank]
+                       "value": total_worlds * more / el2,
+                       "per_rank_ms_per_step": [round(t / more * 1e3, 5)
+                                                for t in per_rank2]}
 
     # the collective on its own (packed observation record, RCCL all-gather)
     allgather = None
-    if distributed and sharded._packed_global is not None:
+    if args.full and distributed and sharded._packed_global is not None:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         reps = 20
         barrier()
@@ -1183,7 +1255,7 @@ def main():
     # receives (N - 1) records over N - 1 links at once, a ring moves
     # (N - 1) / N of the gathered buffer over one link.
     xgmi_bound = None
-    if distributed and sharded._packed_global is not None:
+    if args.full and distributed and sharded._packed_global is not None:
         per_rank_bytes = sharded._packed_global.numel() * 4 // max(world_size, 1)
         gathered = per_rank_bytes * world_size
         link = 153e9
@@ -1201,7 +1273,7 @@ def main():
     # ---- per-kernel timing (HIP events on the executor's stream) + roofline ----
     roofline = None
     kernels = []
-    if rank == 0:
+    if rank == 0 and args.full:
         stats = sim.profile(args.profile_reps)
         roofline = rooflines(stats, args.sim, args.worlds, ms_per_step)
         if roofline is not None:
@@ -1209,7 +1281,7 @@ def main():
         kernels = kernel_table(stats, args.sim, args.worlds)
 
     cpu = None
-    if rank == 0 and world_size == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world_size == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.sim, args.worlds, args.auto_reset_denom, seed,
                            args.settle)
 
@@ -1218,7 +1290,7 @@ def main():
     # BASELINE configs[1] (physics off, 4096 worlds) next to the headline
     secondary = None
     if (rank == 0 and world_size == 1 and args.sim == "escape_room_phys"
-            and not args.no_secondary):
+            and args.full and not args.no_secondary):
         secondary = run_single("escape_room", 4096, local_rank, seed,
                                args.auto_reset_denom, 3000, 200, args.profile_reps,
                                settle=args.settle)
@@ -1226,7 +1298,7 @@ def main():
     # BASELINE configs[4]: the same worlds + 64x64 RGB-D per agent
     render = None
     if (rank == 0 and world_size == 1 and args.sim == "escape_room_phys"
-            and not args.no_secondary):
+            and args.full and not args.no_secondary):
         render = run_render(args.worlds, local_rank, seed, args.auto_reset_denom,
                             200, 30, 10, min(args.settle, 200),
                             cpu_sample=not args.no_cpu_baseline)
@@ -1237,7 +1309,7 @@ def main():
     # ... link unchanged".
     portable = None
     if (rank == 0 and world_size == 1 and args.sim == "escape_room_phys"
-            and not args.no_secondary
+            and args.full and not args.no_secondary
             and os.path.exists(hip_lib_path("escape_room_phys_portable"))):
         portable = {}
         for key, name, w, steps in (("config3", "escape_room_phys_portable",
@@ -1264,7 +1336,7 @@ def main():
     hideseek = None
     cartpole = None
     if (rank == 0 and world_size == 1 and args.sim == "escape_room_phys"
-            and not args.no_secondary):
+            and args.full and not args.no_secondary):
         r = run_single("hideseek", 8192, local_rank, seed, args.auto_reset_denom,
                        300, 50, 10, settle=args.settle)
         hideseek = {"workload": r["workload"], "value": r["value"],
@@ -1306,9 +1378,8 @@ def main():
                                + (", one packed RCCL all-gather of the observation "
                                   "tensors per step" if distributed else ""),
             },
-            "window_s": round(long_window["seconds"] if long_window else elapsed, 5),
-            "timed_steps": long_window["steps"] if long_window else args.steps,
-            "short_window": short_window,
+            "window_s": round(elapsed, 5),
+            "timed_steps": args.steps,
             "long_window": long_window,
             "per_rank_ms_per_step": per_rank_ms,
             "allgather": allgather,
@@ -1328,7 +1399,8 @@ def main():
         ctypes.CDLL(None).fflush(None)
         sys.stdout.flush()
         os.dup2(saved_stdout, 1)
-        print(json.dumps(driver_line(out, write_detail(out))), flush=True)
+        print(json.dumps(driver_line(out, write_detail(out) if args.full else None)),
+              flush=True)
 
 
 if __name__ == "__main__":

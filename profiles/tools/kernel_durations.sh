@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/kd
 timeout 400 rocprofv3 --kernel-trace --output-format csv -d /tmp/kd -o out -- \
-    python $R/bench.py "$@" --no-cpu-baseline --no-secondary > /dev/null 2> /tmp/kd.err
+    python $R/bench.py --full "$@" --no-cpu-baseline --no-secondary > /dev/null 2> /tmp/kd.err
 python - "$pat" <<'PY'
 import csv, glob, re, sys
 pat = sys.argv[1]

@@ -10,7 +10,7 @@ for set in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES SQ_BUSY_CYCLES" "S
   i=$((i+1))
   rm -rf /tmp/pi_$i
   timeout 300 rocprofv3 --kernel-trace --pmc $set -d /tmp/pi_$i -o out -- \
-      python $R/bench.py --steps 60 --warmup 10 --settle 100 --no-cpu-baseline --no-secondary \
+      python $R/bench.py --full --steps 60 --warmup 10 --settle 100 --no-cpu-baseline --no-secondary \
       > /dev/null 2> $O/pass_$i.err
   eval "db_$i=$(find /tmp/pi_$i -name '*.db' | head -1)"
 done

@@ -3,7 +3,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
 run() {  # label, env...
   label=$1; shift
-  env "$@" timeout 400 python bench.py --sim escape_room_render --no-cpu-baseline > /tmp/rc.json 2>/dev/null
+  env "$@" timeout 400 python bench.py --full --sim escape_room_render --no-cpu-baseline > /tmp/rc.json 2>/dev/null
   python - "$label" <<'PY'
 import json, sys
 d = json.load(open('/tmp/rc.json'))

@@ -13,16 +13,16 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 
 # the driver's command line, then the other BASELINE shapes
-python $R/bench.py > $O/${ROUND}_bench_default.json 2> $O/bench_default.err
-python $R/bench.py --sim escape_room --steps 3000 > $O/${ROUND}_bench_escape_room_w4096.json 2> $O/bench_er.err
-python $R/bench.py --sim hideseek > $O/${ROUND}_bench_hideseek_w8192.json 2> $O/bench_hideseek.err
-python $R/bench.py --sim escape_room --worlds 65536 --steps 300 --no-cpu-baseline > $O/${ROUND}_bench_escape_room_w65536.json 2> $O/bench_er64k.err
+python $R/bench.py --full > $O/${ROUND}_bench_default.json 2> $O/bench_default.err
+python $R/bench.py --full --sim escape_room --steps 3000 > $O/${ROUND}_bench_escape_room_w4096.json 2> $O/bench_er.err
+python $R/bench.py --full --sim hideseek > $O/${ROUND}_bench_hideseek_w8192.json 2> $O/bench_hideseek.err
+python $R/bench.py --full --sim escape_room --worlds 65536 --steps 300 --no-cpu-baseline > $O/${ROUND}_bench_escape_room_w65536.json 2> $O/bench_er64k.err
 
 prof() {   # name, bench args...
   name=$1; shift
   rm -rf /tmp/prof_$name
   timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_$name -o out -- \
-      python $R/bench.py "$@" --warmup 100 --no-cpu-baseline --no-secondary \
+      python $R/bench.py --full "$@" --warmup 100 --no-cpu-baseline --no-secondary \
       > $O/${ROUND}_${name}_under_rocprof.json 2> $O/${name}_under_rocprof.err
   db=$(find /tmp/prof_$name -name '*.db' | head -1)
   python $R/profiles/summarize_rocprof.py $db $O/${ROUND}_${name}_kernel_stats
@@ -36,7 +36,7 @@ pmc() {    # sim, worlds, bench args...
   for ctr in FETCH_SIZE WRITE_SIZE; do
     rm -rf /tmp/pmc_${sim}_${worlds}_$ctr
     timeout 600 rocprofv3 --kernel-trace --pmc $ctr -d /tmp/pmc_${sim}_${worlds}_$ctr -o out -- \
-        python $R/bench.py --sim $sim --worlds $worlds "$@" --steps 100 --warmup 20 --settle 30 \
+        python $R/bench.py --full --sim $sim --worlds $worlds "$@" --steps 100 --warmup 20 --settle 30 \
         --no-cpu-baseline --no-secondary > /dev/null 2> $O/pmc_${sim}_${worlds}_$ctr.err
     db=$(find /tmp/pmc_${sim}_${worlds}_$ctr -name '*.db' | head -1)
     python $R/profiles/summarize_pmc.py $db > $O/${ROUND}_pmc_${sim}_w${worlds}_$ctr.txt

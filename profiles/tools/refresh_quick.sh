@@ -10,8 +10,8 @@ O=$R/gpurun_out/refresh
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 
-timeout 300 python $R/bench.py > $O/${ROUND}_bench_default.json 2> $O/bench_default.err
-timeout 200 python $R/bench.py --sim hideseek > $O/${ROUND}_bench_hideseek_w8192.json 2> $O/bench_hideseek.err
+timeout 300 python $R/bench.py --full > $O/${ROUND}_bench_default.json 2> $O/bench_default.err
+timeout 200 python $R/bench.py --full --sim hideseek > $O/${ROUND}_bench_hideseek_w8192.json 2> $O/bench_hideseek.err
 
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -o /tmp/atomic_mb $R/profiles/tools/atomic_microbench.hip \
   && timeout 120 /tmp/atomic_mb > $O/${ROUND}_atomic_microbench.txt 2>&1
@@ -24,7 +24,7 @@ prof() {   # name, command...
   db=$(find /tmp/prof_$name -name '*.db' | head -1)
   python $R/profiles/summarize_rocprof.py $db $O/${ROUND}_${name}_kernel_stats
 }
-prof bench_escape_room_phys_w8192 python $R/bench.py --steps 300 --warmup 100 --no-cpu-baseline --no-secondary
+prof bench_escape_room_phys_w8192 python $R/bench.py --full --steps 300 --warmup 100 --no-cpu-baseline --no-secondary
 prof render_config5_w8192 python -c "
 import sys, json; sys.path.insert(0, '$R')
 import bench
@@ -33,7 +33,7 @@ print(json.dumps(bench.run_render(8192, 0, 5, 200, 100, 20, 5, 100)))"
 for ctr in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmc_$ctr
   timeout 400 rocprofv3 --kernel-trace --pmc $ctr -d /tmp/pmc_$ctr -o out -- \
-      python $R/bench.py --steps 100 --warmup 20 --settle 30 --no-cpu-baseline --no-secondary \
+      python $R/bench.py --full --steps 100 --warmup 20 --settle 30 --no-cpu-baseline --no-secondary \
       > /dev/null 2> $O/pmc_$ctr.err
   db=$(find /tmp/pmc_$ctr -name '*.db' | head -1)
   python $R/profiles/summarize_pmc.py $db > $O/${ROUND}_pmc_escape_room_phys_w8192_$ctr.txt

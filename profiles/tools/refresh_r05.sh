@@ -18,7 +18,7 @@ pmc() {    # sim, worlds, bench args...
   for ctr in FETCH_SIZE WRITE_SIZE; do
     rm -rf /tmp/pmc_${sim}_${worlds}_$ctr
     timeout 400 rocprofv3 --kernel-trace --pmc $ctr -d /tmp/pmc_${sim}_${worlds}_$ctr -o out -- \
-        python $R/bench.py --sim $sim --worlds $worlds "$@" --steps 60 --warmup 10 --settle 30 \
+        python $R/bench.py --full --sim $sim --worlds $worlds "$@" --steps 60 --warmup 10 --settle 30 \
         --profile-reps 5 --no-cpu-baseline --no-secondary > /dev/null 2> $O/pmc_${sim}_${worlds}_$ctr.err
     db=$(find /tmp/pmc_${sim}_${worlds}_$ctr -name '*.db' | head -1)
     python $R/profiles/summarize_pmc.py $db > $O/${ROUND}_pmc_${sim}_w${worlds}_$ctr.txt
@@ -53,7 +53,7 @@ issue() {    # sim, worlds, bench args...
     i=$((i+1))
     rm -rf /tmp/pi_${sim}_$i
     timeout 400 rocprofv3 --kernel-trace --pmc $set -d /tmp/pi_${sim}_$i -o out -- \
-        python $R/bench.py --sim $sim --worlds $worlds "$@" --steps 60 --warmup 10 --settle 30 \
+        python $R/bench.py --full --sim $sim --worlds $worlds "$@" --steps 60 --warmup 10 --settle 30 \
         --profile-reps 5 --no-cpu-baseline --no-secondary > /dev/null 2> $O/issue_${sim}_$i.err
     dbs="$dbs $(find /tmp/pi_${sim}_$i -name '*.db' | head -1)"
   done
@@ -80,15 +80,15 @@ ls -la $O
 # files of THIS refresh, so they go where it looks before the bench lines run
 cp $O/${ROUND}_hbm_traffic.json $O/${ROUND}_issue_counters.json $R/profiles/ 2>/dev/null
 
-timeout 300 python $R/bench.py > $O/${ROUND}_bench_default.json 2> $O/bench_default.err
+timeout 300 python $R/bench.py --full > $O/${ROUND}_bench_default.json 2> $O/bench_default.err
 cp $(ls -t $R/gpurun_out/bench_detail_*.json | head -1) $O/${ROUND}_bench_default_detail.json
-timeout 200 python $R/bench.py --sim hideseek > $O/${ROUND}_bench_hideseek_w8192.json 2> $O/bench_hideseek.err
+timeout 200 python $R/bench.py --full --sim hideseek > $O/${ROUND}_bench_hideseek_w8192.json 2> $O/bench_hideseek.err
 cp $(ls -t $R/gpurun_out/bench_detail_*.json | head -1) $O/${ROUND}_bench_hideseek_w8192_detail.json
-timeout 200 python $R/bench.py --sim escape_room --steps 3000 > $O/${ROUND}_bench_escape_room_w4096.json 2> $O/bench_er.err
+timeout 200 python $R/bench.py --full --sim escape_room --steps 3000 > $O/${ROUND}_bench_escape_room_w4096.json 2> $O/bench_er.err
 cp $(ls -t $R/gpurun_out/bench_detail_*.json | head -1) $O/${ROUND}_bench_escape_room_w4096_detail.json
-timeout 200 python $R/bench.py --sim escape_room --worlds 65536 --steps 300 --no-cpu-baseline > $O/${ROUND}_bench_escape_room_w65536.json 2> $O/bench_er64k.err
+timeout 200 python $R/bench.py --full --sim escape_room --worlds 65536 --steps 300 --no-cpu-baseline > $O/${ROUND}_bench_escape_room_w65536.json 2> $O/bench_er64k.err
 cp $(ls -t $R/gpurun_out/bench_detail_*.json | head -1) $O/${ROUND}_bench_escape_room_w65536_detail.json
-timeout 300 python $R/bench.py --sim escape_room_render > $O/${ROUND}_bench_escape_room_render_w8192.json 2> $O/bench_render.err
+timeout 300 python $R/bench.py --full --sim escape_room_render > $O/${ROUND}_bench_escape_room_render_w8192.json 2> $O/bench_render.err
 cp $(ls -t $R/gpurun_out/bench_detail_*.json | head -1) $O/${ROUND}_bench_escape_room_render_w8192_detail.json
 
 prof() {   # name, command...
@@ -99,7 +99,7 @@ prof() {   # name, command...
   db=$(find /tmp/prof_$name -name '*.db' | head -1)
   python $R/profiles/summarize_rocprof.py $db $O/${ROUND}_${name}_kernel_stats
 }
-prof bench_escape_room_phys_w8192 python $R/bench.py --steps 300 --warmup 100 --no-cpu-baseline --no-secondary
-prof render_config5_w8192 python $R/bench.py --sim escape_room_render --steps 100 --warmup 20 --no-cpu-baseline
-prof bench_hideseek_w8192 python $R/bench.py --sim hideseek --steps 300 --warmup 100 --no-cpu-baseline --no-secondary
+prof bench_escape_room_phys_w8192 python $R/bench.py --full --steps 300 --warmup 100 --no-cpu-baseline --no-secondary
+prof render_config5_w8192 python $R/bench.py --full --sim escape_room_render --steps 100 --warmup 20 --no-cpu-baseline
+prof bench_hideseek_w8192 python $R/bench.py --full --sim hideseek --steps 300 --warmup 100 --no-cpu-baseline --no-secondary
 

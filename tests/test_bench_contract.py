@@ -204,3 +204,31 @@ def test_driver_line_carries_every_baseline_config():
     assert line["cartpole_config1"]["cpu_reference"] == 1.0e6
     assert line["config"]["rccl_ranks"] == 0
     assert len(json.dumps(line)) < bench.LINE_BUDGET_BYTES
+
+
+def test_dump_outputs_types_budget_and_repeatable_sample(tmp_path):
+    """--dump-outputs: float32 / float64 files only, exact values for what fits,
+    at most DUMP_BUDGET_BYTES in all, and the sample of an oversized output (the
+    RGB images of config 5) is the same rows in every run."""
+    import numpy as np
+    bench = _load("bench", os.path.join(ROOT, "bench.py"))
+    rng = np.random.default_rng(1)
+    W = 8192
+    arrays = {"reward": rng.random((W, 2, 1), dtype=np.float32),
+              "done": rng.integers(0, 2, (W, 2, 1)).astype(np.int32),
+              "lidar": rng.random((W, 2, 30, 2), dtype=np.float32),
+              "rgb": rng.integers(0, 256, (2 * W, 64, 64, 4)).astype(np.uint8)}
+    for d in ("a", "b"):
+        bench.dump_outputs(arrays, str(tmp_path / d))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["done.npy", "lidar.npy", "reward.npy", "rgb.npy"]
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_BUDGET_BYTES
+    assert got["done"].dtype == np.float64 and got["rgb"].dtype == np.float32
+    for k in ("reward", "done", "lidar"):
+        assert np.array_equal(got[k], arrays[k]), k
+    rgb = got["rgb"]
+    assert 0 < len(rgb) < 2 * W and rgb.shape[1:] == (64, 64, 4)
+    assert np.array_equal(rgb, np.load(tmp_path / "b" / "rgb.npy"))
+    assert any(np.array_equal(rgb[0], arrays["rgb"][i].astype(np.float32))
+               for i in range(2 * W))

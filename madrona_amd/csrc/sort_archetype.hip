@@ -2034,7 +2034,8 @@ void buildSortLaunches(const SortBatch &batch, std::vector<KernelLaunch> &out)
         k.block = dim3(kSortThreads, 1, 1);
         k.setArgs(batch.stateDev, batch.sitesDev, batch.gatherColumnsDev,
                   batch.gatherSlicesDev, (const MiscOp *)nullptr, 0u);
-        k.role = "sort.gather";
+        // (the 16-byte variant names itself: tests check which one ran)
+        k.role = batch.gatherWide ? "sort.gather.wide" : "sort.gather";
         k.kind = MWHIP_NODE_SORT_ARCHETYPE;
         k.sortBatch = &batch;
         k.sortRole = SortRole::Gather;

@@ -259,6 +259,17 @@ class Simulator:
         if rc != 0:
             raise RuntimeError(f"sim_hip_run_taskgraph({taskgraph_id}) -> {rc}")
 
+    def taskgraph_graph(self, taskgraph_id: int) -> int:
+        """Launch-graph handle of ONE task graph (the graph run_taskgraph
+        replays; HIP backend), e.g. for profile(graph=...)."""
+        fn = self.lib.sim_hip_taskgraph_graph
+        fn.restype = C.c_uint64
+        fn.argtypes = [C.c_void_p, C.c_uint32]
+        g = int(fn(self.handle, taskgraph_id))
+        if g == 0:
+            raise RuntimeError(f"sim_hip_taskgraph_graph({taskgraph_id}) -> 0")
+        return g
+
     def render(self) -> None:
         """MWCudaExecutor::buildRenderGraph + run: TLAS build and ray cast of every
         view into the simulator's "rgb" / "depth" tensors (HIP backend)."""

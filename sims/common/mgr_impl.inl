@@ -118,6 +118,15 @@ static void preStep()
         T::preStep();
     }
 }
+
+// optional: exports that depend on the creation flags
+template <typename T, typename List>
+static void describeFlagTensors(List &out, const SimCreateArgs &args)
+{
+    if constexpr (requires { T::describeFlagTensors(out, args); }) {
+        T::describeFlagTensors(out, args);
+    }
+}
 }
 
 #ifndef SIM_BACKEND_REF_CPU
@@ -220,6 +229,7 @@ SimHandle *sim_create(const SimCreateArgs *args)
 #endif
 
     Traits::describeTensors(h->tensors, args->num_worlds);
+    simmgr::describeFlagTensors<Traits>(h->tensors, *args);
     Traits::describeColumns(h->columns);
 
     return h;
@@ -361,13 +371,11 @@ int64_t sim_column_dump(SimHandle *h, uint32_t idx, void *dst,
 #endif
 }
 
-int sim_hip_run_taskgraph(SimHandle *h, uint32_t taskgraph_id)
+#ifndef SIM_BACKEND_REF_CPU
+// launch graph of ONE task graph, built the first time it is asked for
+static madrona::MWCudaLaunchGraph *probeGraph(SimHandle *h, uint32_t taskgraph_id)
 {
-#ifdef SIM_BACKEND_REF_CPU
-    (void)h; (void)taskgraph_id;
-    return -1;
-#else
-    if (taskgraph_id >= SimTraits::numTaskGraphs) return -1;
+    if (taskgraph_id >= SimTraits::numTaskGraphs) return nullptr;
     if (h->probeGraphs.size() <= taskgraph_id) {
         h->probeGraphs.resize(taskgraph_id + 1, nullptr);
     }
@@ -375,8 +383,31 @@ int sim_hip_run_taskgraph(SimHandle *h, uint32_t taskgraph_id)
         h->probeGraphs[taskgraph_id] = new madrona::MWCudaLaunchGraph(
             h->exec->buildLaunchGraph(taskgraph_id));
     }
-    h->exec->run(*h->probeGraphs[taskgraph_id]);
+    return h->probeGraphs[taskgraph_id];
+}
+#endif
+
+int sim_hip_run_taskgraph(SimHandle *h, uint32_t taskgraph_id)
+{
+#ifdef SIM_BACKEND_REF_CPU
+    (void)h; (void)taskgraph_id;
+    return -1;
+#else
+    madrona::MWCudaLaunchGraph *g = probeGraph(h, taskgraph_id);
+    if (g == nullptr) return -1;
+    h->exec->run(*g);
     return 0;
+#endif
+}
+
+uint64_t sim_hip_taskgraph_graph(SimHandle *h, uint32_t taskgraph_id)
+{
+#ifdef SIM_BACKEND_REF_CPU
+    (void)h; (void)taskgraph_id;
+    return 0;
+#else
+    madrona::MWCudaLaunchGraph *g = probeGraph(h, taskgraph_id);
+    return g == nullptr ? 0 : g->handle();
 #endif
 }
 

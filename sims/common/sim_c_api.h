@@ -69,6 +69,9 @@ SIM_API int64_t sim_column_dump(SimHandle *h, uint32_t idx, void *dst, uint64_t 
  * order -- every row below the table's row count, destroyed ones included, no
  * grouping by world -- to look at the table between nodes.  Returns rows. */
 SIM_API int sim_hip_run_taskgraph(SimHandle *h, uint32_t taskgraph_id);
+/* HIP backend only (0 on the reference): launch-graph handle of that one task
+ * graph (the graph sim_hip_run_taskgraph replays), e.g. for mwhip_profile. */
+SIM_API uint64_t sim_hip_taskgraph_graph(SimHandle *h, uint32_t taskgraph_id);
 SIM_API int64_t sim_column_dump_raw(SimHandle *h, uint32_t idx, void *dst,
                                     uint64_t dst_bytes);
 

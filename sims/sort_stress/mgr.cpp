@@ -23,13 +23,17 @@ struct SimTraits {
                              (args.flags >> 1) & 1u,
                              (args.flags >> 2) & 1u,
                              (args.flags >> 3) & 1u,
-                             (args.flags >> 4) & 1u };
+                             (args.flags >> 4) & 1u,
+                             (args.flags >> 5) & 1u,
+                             (args.flags >> 6) & 1u };
     }
 
     static void makeInits(const SimCreateArgs &, Sim::WorldInit *) {}
 
     template <typename T>
     static void describeTensors(T &out, uint32_t num_worlds);
+    template <typename T>
+    static void describeFlagTensors(T &out, const SimCreateArgs &args);
     template <typename T>
     static void describeColumns(T &cols);
 };
@@ -41,6 +45,31 @@ void SimTraits::describeTensors(T &out, uint32_t num_worlds)
 {
     out.push_back({ "churn", SIM_I32, { (int64_t)num_worlds, 3 },
                     (uint32_t)sortstress::ExportID::Churn });
+}
+
+// exports that only exist with flags 32 (plan / probe) and 64 (item_vec3),
+// HIP backend only
+template <typename T>
+void SimTraits::describeFlagTensors(T &out, const SimCreateArgs &args)
+{
+#ifndef SIM_BACKEND_REF_CPU
+    using namespace sortstress;
+    const int64_t w = (int64_t)args.num_worlds;
+    if ((args.flags & 32u) != 0u) {
+        out.push_back({ "plan", SIM_I32, { w, 5 }, (uint32_t)ExportID::Plan });
+        out.push_back({ "probe", SIM_I32,
+                        { w, (int64_t)(sizeof(ProbeOut) / 4) },
+                        (uint32_t)ExportID::Probe });
+    }
+    if ((args.flags & 64u) != 0u) {
+        // (the first consts::maxItems rows per world of the column, as many
+        // as a table the plan sets up can hold)
+        out.push_back({ "item_vec3", SIM_F32, { w * consts::maxItems, 3 },
+                        (uint32_t)ExportID::ItemVec3 });
+    }
+#else
+    (void)out; (void)args;
+#endif
 }
 
 template <typename T>

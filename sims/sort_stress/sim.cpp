@@ -9,7 +9,7 @@ using namespace madrona;
 
 namespace sortstress {
 
-void Sim::registerTypes(ECSRegistry &registry, const Config &)
+void Sim::registerTypes(ECSRegistry &registry, const Config &cfg)
 {
     registry.registerComponent<Tag8>();
     registry.registerComponent<Half>();
@@ -25,6 +25,18 @@ void Sim::registerTypes(ECSRegistry &registry, const Config &)
     registry.registerArchetype<Scratch>();
 
     registry.exportSingleton<Churn>((uint32_t)ExportID::Churn);
+
+#ifdef MADRONA_GPU_MODE
+    if (cfg.plan != 0) {
+        registry.registerSingleton<Plan>();
+        registry.registerSingleton<ProbeOut>();
+        registry.exportSingleton<Plan>((uint32_t)ExportID::Plan);
+        registry.exportSingleton<ProbeOut>((uint32_t)ExportID::Probe);
+    }
+    if (cfg.exportVec3 != 0) {
+        registry.exportColumn<Item, Vec3>((uint32_t)ExportID::ItemVec3);
+    }
+#endif
 }
 
 static inline void fillItem(Engine &ctx, Entity e, RNG &rng)
@@ -200,6 +212,95 @@ inline void siblingOtherSystem(Engine &, Blob20 &b)
     b.v[4] += 3u;
 }
 
+#ifdef MADRONA_GPU_MODE
+// ---- shape-controlled sort tests (Config::plan) ----------------------------
+static inline uint32_t mixBits(uint32_t x)
+{
+    x ^= x >> 16;
+    x *= 0x7FEB352Du;
+    x ^= x >> 15;
+    x *= 0x846CA68Bu;
+    x ^= x >> 16;
+    return x;
+}
+
+static inline uint32_t planKey(const Plan &plan, uint32_t world, uint32_t slot)
+{
+    const uint32_t ordinal = world * 64u + slot;
+    const uint32_t h = mixBits(plan.param ^ mixBits(ordinal + 0x9E3779B9u));
+    switch ((KeyMode)plan.mode) {
+    case KeyMode::Random: return h;
+    case KeyMode::Equal: return plan.param;
+    case KeyMode::TwoValues: return (h & 1u) != 0u ? ~plan.param : plan.param;
+    case KeyMode::TopByte: return (h & 0xFF000000u) | (plan.param & 0x00FFFFFFu);
+    case KeyMode::LowByte: return (plan.param & 0xFFFFFF00u) | (h & 0xFFu);
+    case KeyMode::Ascending: return plan.param + ordinal;
+    case KeyMode::Descending: return ~(plan.param + ordinal);
+    case KeyMode::AllOnes: return 0xFFFFFFFFu;
+    case KeyMode::ZeroOrOnes: return (h & 1u) != 0u ? 0xFFFFFFFFu : 0u;
+    default: return h;
+    }
+}
+
+// Brings the world to plan.numItems items (destroys from the back, creates new
+// ones behind); the compaction that follows makes the table world-major.
+inline void planResizeSystem(Engine &ctx, Plan &plan)
+{
+    Sim &sim = ctx.data();
+    int32_t target = plan.numItems < 0 ? 0 :
+        (plan.numItems > consts::maxItems ? consts::maxItems : plan.numItems);
+    while (sim.numItems > target) {
+        ctx.destroyEntity(sim.items[--sim.numItems]);
+    }
+    while (sim.numItems < target) {
+        Entity e = ctx.makeEntity<Item>();
+        fillItem(ctx, e, sim.rng);
+        sim.items[sim.numItems++] = e;
+    }
+}
+
+// Keys by plan.mode, then the items the plan names are destroyed: their rows
+// stay in the table (WorldID -1) until the next compaction.
+inline void planKeysSystem(Engine &ctx, Plan &plan)
+{
+    Sim &sim = ctx.data();
+    for (int32_t i = 0; i < sim.numItems; i++) {
+        ctx.get<Key>(sim.items[i]).v = planKey(plan, sim.globalWorld, (uint32_t)i);
+    }
+    int32_t kept = 0;
+    for (int32_t i = 0; i < sim.numItems; i++) {
+        const uint32_t bit = i < 32 ? (plan.destroyLo >> i) & 1u :
+            (plan.destroyHi >> (i - 32)) & 1u;
+        if (bit != 0u) {
+            ctx.destroyEntity(sim.items[i]);
+        } else {
+            sim.items[kept++] = sim.items[i];
+        }
+    }
+    sim.numItems = kept;
+}
+
+// Every held item's Key read through its entity handle (the Loc a sort left).
+inline void probeSystem(Engine &ctx, ProbeOut &out)
+{
+    Sim &sim = ctx.data();
+    out.numItems = sim.numItems;
+    out.pad = 0;
+    for (int32_t i = 0; i < consts::maxItems; i++) {
+        if (i < sim.numItems) {
+            Entity e = sim.items[i];
+            out.items[i][0] = e.gen;
+            out.items[i][1] = (uint32_t)e.id;
+            out.items[i][2] = ctx.get<Key>(e).v;
+        } else {
+            out.items[i][0] = 0xFFFFFFFFu;
+            out.items[i][1] = 0xFFFFFFFFu;
+            out.items[i][2] = 0u;
+        }
+    }
+}
+#endif
+
 void Sim::setupTasks(TaskGraphManager &taskgraph_mgr, const Config &cfg)
 {
     TaskGraphBuilder &builder = taskgraph_mgr.init(TaskGraphID::Step);
@@ -262,6 +363,43 @@ void Sim::setupTasks(TaskGraphManager &taskgraph_mgr, const Config &cfg)
         auto c = b.addToGraph<CompactArchetypeNode<Item>>({});
         b.addToGraph<SortArchetypeNode<Scratch, WorldID>>({c});
     }
+    {
+        TaskGraphBuilder &b = taskgraph_mgr.init(TaskGraphID::LoadPlan);
+        if (cfg.plan != 0) {
+            auto resize = b.addToGraph<ParallelForNode<Engine,
+                planResizeSystem, Plan>>({});
+            auto c = b.addToGraph<CompactArchetypeNode<Item>>({resize});
+            b.addToGraph<ParallelForNode<Engine, planKeysSystem, Plan>>({c});
+        } else {
+            b.addToGraph<ResetTmpAllocNode>({});
+        }
+    }
+    {
+        TaskGraphBuilder &b = taskgraph_mgr.init(TaskGraphID::KeySort);
+        auto sort = b.addToGraph<SortArchetypeNode<Item, Key>>({});
+        b.addToGraph<ResetTmpAllocNode>({sort});
+    }
+    {
+        TaskGraphBuilder &b = taskgraph_mgr.init(TaskGraphID::WorldSort);
+        auto c = b.addToGraph<CompactArchetypeNode<Item>>({});
+        b.addToGraph<ResetTmpAllocNode>({c});
+    }
+    {
+        TaskGraphBuilder &b = taskgraph_mgr.init(TaskGraphID::Probe);
+        if (cfg.plan != 0) {
+            b.addToGraph<ParallelForNode<Engine, probeSystem, ProbeOut>>({});
+        } else {
+            b.addToGraph<ResetTmpAllocNode>({});
+        }
+    }
+    {
+        TaskGraphBuilder &b = taskgraph_mgr.init(TaskGraphID::PlanResize);
+        if (cfg.plan != 0) {
+            b.addToGraph<ParallelForNode<Engine, planResizeSystem, Plan>>({});
+        } else {
+            b.addToGraph<ResetTmpAllocNode>({});
+        }
+    }
 #endif
 }
 
@@ -287,6 +425,14 @@ Sim::Sim(Engine &ctx, const Config &cfg, const WorldInit &)
     if (cfg.rampUp != 0 || cfg.burst != 0) {
         initial = 1;
     }
+    globalWorld = global_world;
+#ifdef MADRONA_GPU_MODE
+    if (cfg.plan != 0) {
+        initial = 0;
+        ctx.singleton<Plan>() = Plan {};
+        ctx.singleton<ProbeOut>() = ProbeOut {};
+    }
+#endif
     burst = 0;
     if (cfg.burst != 0) {
         burst = global_world < 100u ? 1u :

@@ -23,6 +23,11 @@ inline constexpr int32_t maxScratch = 12;
 
 enum class ExportID : uint32_t {
     Churn,
+#ifdef MADRONA_GPU_MODE
+    Plan,
+    Probe,
+    ItemVec3,
+#endif
     NumExports,
 };
 
@@ -42,6 +47,41 @@ struct Churn {
     uint32_t scratchSum;
 };
 
+#ifdef MADRONA_GPU_MODE
+// How a world's Item keys are set by LoadPlan (KeyMode::*, Plan::mode)
+enum class KeyMode : uint32_t {
+    Random,         // full 32-bit hash values, top bit included
+    Equal,          // every key = param
+    TwoValues,      // param or ~param
+    TopByte,        // only the top byte varies (the rest = param)
+    LowByte,        // only the low byte varies (the rest = param)
+    Ascending,      // param + 64 * world + slot: ascending in table order
+    Descending,     // the complement of Ascending
+    AllOnes,        // every key 0xFFFFFFFF
+    ZeroOrOnes,     // 0 or 0xFFFFFFFF
+    NumModes,
+};
+
+// Written by the host (export "plan") before LoadPlan runs: the world's item
+// count, how its keys are set, and which of its items are then destroyed
+// WITHOUT compaction (bit i: items[i]; their rows stay, WorldID -1).
+struct Plan {
+    int32_t numItems;
+    uint32_t mode;
+    uint32_t param;
+    uint32_t destroyLo;
+    uint32_t destroyHi;
+};
+
+// Written by Probe (export "probe"): every item a world holds, read through
+// its entity handle (gen, id, Key).
+struct ProbeOut {
+    int32_t numItems;
+    int32_t pad;
+    uint32_t items[consts::maxItems][3];
+};
+#endif
+
 // Task graphs.  Step = the graph every parity test replays.  The other three
 // exist on the HIP backend only and split a step so that a test can look at
 // the table between nodes: churn WITHOUT compaction (destroyed rows stay),
@@ -54,6 +94,17 @@ enum class TaskGraphID : uint32_t {
     ChurnOnly,
     SortByKey,
     CompactOnly,
+    // Shape-controlled sort tests (tests/test_sort_node_edges_gpu.py):
+    // LoadPlan brings every world to its Plan; KeySort / WorldSort are a key
+    // sort / compaction each followed by a ResetTmpAlloc that the sort batch
+    // may carry; Probe reads every held item's Key through its handle;
+    // PlanResize only creates / destroys to Plan::numItems (no compaction:
+    // new rows behind the sorted prefix, destroyed ones left in it).
+    LoadPlan,
+    KeySort,
+    WorldSort,
+    Probe,
+    PlanResize,
 #endif
     NumTaskGraphs,
 };
@@ -93,6 +144,13 @@ struct Sim : public madrona::WorldBase {
         // the registration order the reference's executors follow),
         // siblingOtherSystem touches Blob20 alone
         uint32_t siblings;
+        // 1 (HIP backend only): the Plan / ProbeOut singletons exist and are
+        // exported, every world starts with no items (LoadPlan sets the table
+        // up).  Off in every parity test: the singletons take entity ids.
+        uint32_t plan;
+        // 1 (HIP backend only): Item's Vec3 column is exported ("item_vec3"),
+        // a pinned column the sort node must keep in place
+        uint32_t exportVec3;
     };
 
     struct WorldInit {};
@@ -109,6 +167,7 @@ struct Sim : public madrona::WorldBase {
     uint32_t rampUp;
     uint32_t chatty;
     uint32_t burst;         // 0: off, 1: a bursting world, 2: churns, 3: stands still
+    uint32_t globalWorld;
     int32_t numItems;
     Entity items[consts::maxItems];
 };

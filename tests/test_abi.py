@@ -43,6 +43,7 @@ def test_simulator_library_exports_c_api(built, sim):
     lib = C.CDLL(hip_lib_path(sim))
     for fn in ["sim_create", "sim_destroy", "sim_step", "sim_tensor_ptr",
                "sim_column_dump", "sim_column_dump_raw", "sim_hip_run_taskgraph",
+               "sim_hip_taskgraph_graph",
                "sim_hip_exec", "sim_hip_step_graph", "madronaMWHipUserEntry"]:
         assert hasattr(lib, fn), fn
 

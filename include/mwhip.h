@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MWHIP_ABI_VERSION 7u   /* 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
+#define MWHIP_ABI_VERSION 8u   /* 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
 
 typedef struct mwhip_exec mwhip_exec; /* opaque; == MWCudaExecutor::Impl */
 
@@ -201,6 +201,11 @@ void *mwhip_get_module_data(mwhip_exec *exec, uint32_t slot);
 uint32_t mwhip_archetype_capacity(mwhip_exec *exec, uint32_t archetype_id);
 /* how many times a table has been grown so far (tests / monitoring) */
 uint32_t mwhip_num_table_growths(mwhip_exec *exec);
+/* the persistent region's current bump offset in bytes (device rawAlloc /
+ * HostAllocator: mwhip::persistAlloc, 16-B granules): right after creation,
+ * what the last constructor pass took; device code that allocates there while
+ * steps run moves it on.  Read only (tests / monitoring).  ~0ull on error. */
+uint64_t mwhip_persist_bytes_used(mwhip_exec *exec);
 /* device address of the archetype's table header (mwhip::TableHdr) */
 void *mwhip_table_header(mwhip_exec *exec, uint32_t archetype_id);
 /* copies `count` words of the query table starting at `offset` */

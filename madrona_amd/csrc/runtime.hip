@@ -1166,6 +1166,19 @@ extern "C" uint32_t mwhip_num_table_growths(mwhip_exec *exec)
     return exec->numGrowths;
 }
 
+extern "C" uint64_t mwhip_persist_bytes_used(mwhip_exec *exec)
+{
+    // the region's bump offset: every constructor pass starts it over, and
+    // device rawAlloc / HostAllocator calls from step code move it on
+    unsigned long long used = 0;
+    if (hipStreamSynchronize(exec->stream) != hipSuccess ||
+        hipMemcpy(&used, (char *)exec->stateDev + offsetof(EcsState, persistOffset),
+                  sizeof(used), hipMemcpyDeviceToHost) != hipSuccess) {
+        return ~0ull;
+    }
+    return used;
+}
+
 extern "C" int mwhip_synchronize(mwhip_exec *exec)
 {
     HIPCHK(hipStreamSynchronize(exec->stream));

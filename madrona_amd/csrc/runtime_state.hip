@@ -720,26 +720,60 @@ MWHIP_RT int constructWorlds(mwhip_exec *exec)
     uint32_t err = 0;
     rc = fetchError(exec, &err);
     if (rc != 0) return rc;
-    // (both recoverable conditions may be raised by one pass: test bits, handle
-    // the persistent region first -- after its overflow every world aliases
-    // persistBase, which can produce secondary flags that the rerun clears)
-    if ((err & kErrPersistOverflow) != 0u) {
-        // The constructors asked for more persistent memory (BVH arrays, ...)
-        // than MADRONA_MWHIP_PERSIST_KB_PER_WORLD provides.  persistAlloc kept
-        // counting, so the offset is what they need: size the region for it
-        // and run pass 1 again.
-        unsigned long long needed = 0;
-        HIPCHK(hipMemcpy(&needed, (char *)exec->stateDev +
-            offsetof(EcsState, persistOffset), sizeof(needed),
-            hipMemcpyDeviceToHost));
-        unsigned long long capacity = needed + needed / 8 + (1ull << 20);
-        char *region = nullptr;
-        rc = devAlloc(exec, (void **)&region, capacity, false);
-        if (rc != 0) return rc;
-        rc = pokeState(exec, &EcsState::persistBase, region);
-        if (rc != 0) return rc;
-        rc = pokeState(exec, &EcsState::persistCapacity, capacity);
-        if (rc != 0) return rc;
+    // (an overflowed pass can raise secondary flags -- its late allocations
+    // alias the region's base -- which the rerun clears: handle the regions
+    // first)
+    // Constructors that ask for more persistent memory (BVH arrays, navmeshes,
+    // ...) than MADRONA_MWHIP_PERSIST_KB_PER_WORLD provides, or for more
+    // scratch (Context::tmpAlloc, a navmesh builder's temporaries) than the
+    // scratch region holds -- the mailbox that grows it while steps run is not
+    // served yet: size the region for what the pass asked for and run pass 1
+    // again.  The allocators keep counting past the end, but code that sees
+    // the overflow may stop asking (Navmesh::initFromPolygons builds nothing
+    // then), so the count can fall short: the region at least doubles each
+    // round.
+    constexpr uint32_t kRegionOverflow = kErrPersistOverflow | kErrTmpOverflow;
+    for (int attempt = 0; (err & kRegionOverflow) != 0u && attempt < 16;
+             attempt++) {
+        if ((err & kErrPersistOverflow) != 0u) {
+            unsigned long long needed = 0;
+            HIPCHK(hipMemcpy(&needed, (char *)exec->stateDev +
+                offsetof(EcsState, persistOffset), sizeof(needed),
+                hipMemcpyDeviceToHost));
+            unsigned long long capacity = std::max(
+                needed + needed / 8 + (1ull << 20), 2 * hs.persistCapacity);
+            char *region = nullptr;
+            rc = devAlloc(exec, (void **)&region, capacity, false);
+            if (rc != 0) return rc;
+            rc = pokeState(exec, &EcsState::persistBase, region);
+            if (rc != 0) return rc;
+            rc = pokeState(exec, &EcsState::persistCapacity, capacity);
+            if (rc != 0) return rc;
+            hs.persistBase = region;
+            hs.persistCapacity = capacity;
+        }
+        if ((err & kErrTmpOverflow) != 0u) {
+            unsigned long long needed = 0;
+            HIPCHK(hipMemcpy(&needed, (char *)exec->stateDev +
+                offsetof(EcsState, tmpOffset), sizeof(needed),
+                hipMemcpyDeviceToHost));
+            unsigned long long capacity = std::max(
+                needed + needed / 8 + (1ull << 20), 2 * hs.tmpCapacity);
+            if (exec->tmpVm != nullptr) {
+                rc = growTmpRegion(exec, capacity);
+                if (rc != 0) return rc;
+            } else {
+                char *region = nullptr;
+                rc = devAlloc(exec, (void **)&region, capacity, false);
+                if (rc != 0) return rc;
+                rc = pokeState(exec, &EcsState::tmpBase, region);
+                if (rc != 0) return rc;
+                hs.tmpBase = region;
+                hs.tmpCapacity = capacity;
+            }
+            rc = pokeState(exec, &EcsState::tmpCapacity, hs.tmpCapacity);
+            if (rc != 0) return rc;
+        }
 
         rc = resetForInitPass(exec);
         if (rc != 0) return rc;
@@ -847,6 +881,11 @@ MWHIP_RT int constructWorlds(mwhip_exec *exec)
     }
 
     rc = pokeState(exec, &EcsState::runtimeIdBase, (int32_t)next);
+    if (rc != 0) return rc;
+    // what the constructors took from the scratch region (Context::tmpAlloc,
+    // Navmesh::initFromPolygons' temporaries) is dead now: the first step
+    // starts with all of it
+    rc = pokeState(exec, &EcsState::tmpOffset, 0ull);
     if (rc != 0) return rc;
     return pokeState(exec, &EcsState::initMode, 0u);
 }

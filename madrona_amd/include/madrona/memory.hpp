@@ -96,6 +96,24 @@ public:
     }
 };
 
+// True on the device once an allocation from the persistent region (rawAlloc,
+// HostAllocator) or from the scratch region (TmpAllocator, Context::tmpAlloc)
+// did not fit: such an allocation returns the region's base, which other lanes
+// use too.  In the world constructors the executor then sizes the regions and
+// runs the constructors again, so code that just allocated there should write
+// nothing through the pointers it got (Navmesh::initFromPolygons returns an
+// empty mesh).  A lane always sees its own failed allocation here.
+MADRONA_HD inline bool allocOverflowed()
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (__hip_atomic_load(&getStateManager()->errorFlags, __ATOMIC_RELAXED,
+                              __HIP_MEMORY_SCOPE_AGENT) &
+            (mwhip::kErrPersistOverflow | mwhip::kErrTmpOverflow)) != 0u;
+#else
+    return false;
+#endif
+}
+
 // (both allocators are stateless façades over the device-resident ecs_state:
 // the state's address stands in for "the" allocator object)
 MADRONA_HD inline HostAllocator *getHostAllocator()

@@ -34,3 +34,8 @@ def build_oracle() -> None:
     _make(oracle_dir, "restate")
     if os.path.isdir(os.path.join(REFERENCE_ROOT, "src")):
         _make(oracle_dir, "parity", "speed")
+        # mesh_cast: through the oracle Makefile's pattern rules for a
+        # simulator directory (reference CPU backend + the reference's own
+        # MeshBVH queries behind the manager's probes)
+        _make(oracle_dir, "_ref/libmesh_cast_ref.so",
+              "_ref/libmesh_cast_ref_speed.so")

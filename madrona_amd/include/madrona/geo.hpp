@@ -96,4 +96,66 @@ MADRONA_HD inline math::Vector3 computeTriangleGeoNormal(math::Vector3 ab,
     return bc.length2() < ac.length2() ? normal_bc : normal_ac;
 }
 
+// Point of triangle (a, b, c) closest to the origin; ab = b - a, ac = c - a.
+// Ericson, Real-Time Collision Detection 5.1.5: the origin's projections onto
+// the two sides decide which Voronoi region of the triangle it lies in, asked
+// in the book's order (vertex A, vertex B, edge AB, vertex C, edge AC, edge
+// BC, face) because regions share their borders.  The arithmetic is that of
+// reference geo.inl:180-238.
+MADRONA_HD inline math::Vector3 triangleClosestPointToOrigin(math::Vector3 a,
+                                                             math::Vector3 b,
+                                                             math::Vector3 c,
+                                                             math::Vector3 ab,
+                                                             math::Vector3 ac)
+{
+    // <side, vertex>: how far past the origin's foot each vertex lies along
+    // each side (positive: the origin is behind the vertex)
+    const float ab_at_a = dot(ab, a), ac_at_a = dot(ac, a);
+    const float ab_at_b = dot(ab, b), ac_at_b = dot(ac, b);
+    const float ab_at_c = dot(ab, c), ac_at_c = dot(ac, c);
+
+    // start + dir * (num / den)
+    auto along = [](math::Vector3 start, math::Vector3 dir, float num,
+                    float den) {
+        float s = num / den;
+        return start + s * dir;
+    };
+
+    if (ab_at_a >= 0.f && ac_at_a >= 0.f) {
+        return a;
+    }
+
+    if (ab_at_b <= 0.f && ab_at_b <= ac_at_b) {
+        return b;
+    }
+
+    // signed areas of the sub-triangles opposite C, B, A (scaled alike)
+    const float area_c = ab_at_a * ac_at_b - ab_at_b * ac_at_a;
+    if (area_c <= 0.f && ab_at_a <= 0.f && ab_at_b >= 0.f) {
+        return along(a, ab, ab_at_a, ab_at_a - ab_at_b);
+    }
+
+    if (ac_at_c <= 0.f && ab_at_c >= ac_at_c) {
+        return c;
+    }
+
+    const float area_b = ab_at_c * ac_at_a - ab_at_a * ac_at_c;
+    if (area_b <= 0.f && ac_at_a <= 0.f && ac_at_c >= 0.f) {
+        return along(a, ac, ac_at_a, ac_at_a - ac_at_c);
+    }
+
+    const float area_a = ab_at_b * ac_at_c - ab_at_c * ac_at_b;
+    const float past_b = ac_at_b - ab_at_b;
+    const float past_c = ab_at_c - ac_at_c;
+    if (area_a <= 0.f && past_b <= 0.f && past_c <= 0.f) {
+        return along(b, c - b, past_b, past_b + past_c);
+    }
+
+    // inside: barycentric blend, normalised by one reciprocal
+    const float inv_area = 1.f / (area_a + area_b + area_c);
+    const float weight_b = area_b * inv_area;
+    const float weight_c = area_c * inv_area;
+    return a + ab * weight_b + ac * weight_c;
+}
+
 }

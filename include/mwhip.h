@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MWHIP_ABI_VERSION 8u   /* 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
+#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
 
 typedef struct mwhip_exec mwhip_exec; /* opaque; == MWCudaExecutor::Impl */
 
@@ -509,6 +509,52 @@ typedef struct mwhip_kernel_stat {
 } mwhip_kernel_stat;
 int32_t mwhip_profile(mwhip_exec *exec, uint64_t graph, uint32_t reps,
                       mwhip_kernel_stat *out, uint32_t max_out);
+
+/* Snapshots: one saved copy of everything a step reads and an earlier step wrote
+ * -- the live rows of every column of every table with numRows / needsSort /
+ * sortedRows / tailRows and the per-world ranges, the entity slots in use, the
+ * per-world id caches, idFreeHead / numIds / the run-time id partition, the
+ * per-world data, tmpOffset and the persistent region up to persistOffset --
+ * held in device memory that belongs to the executor.  One kernel launch per
+ * save or restore (behind a one-workgroup prologue on save) moves the live rows
+ * only; the row counts are read on the device, so the asynchronous forms are
+ * stream-ordered behind the replays queued before them.  A snapshot can be
+ * saved into and restored from any number of times, by the executor that made
+ * it.  NOT rewound: the executor's replay counters (and with them the input
+ * rings' slot position), errorFlags, capacities, and the ray caster's output
+ * columns (derived state: they keep their contents until the next render
+ * pass).  (No reference counterpart.)
+ *
+ * mwhip_snapshot_save waits for the stream, sizes the snapshot for the rows
+ * mapped now, saves and waits again: it cannot overflow.
+ * mwhip_snapshot_save_async keeps the size of the last synchronous save (or of
+ * mwhip_snapshot_create): a table that has outgrown that room is not copied
+ * and the snapshot is marked overflowed -- restoring it is refused until it has
+ * been saved into again.
+ * Errors (non-zero, text in mwhip_last_error(), state untouched): an unknown
+ * handle or one of another executor, restoring a snapshot that was never saved,
+ * restoring one whose last save overflowed. */
+int mwhip_snapshot_create(mwhip_exec *exec, uint64_t *snapshot_out);
+void mwhip_snapshot_destroy(mwhip_exec *exec, uint64_t snapshot);
+int mwhip_snapshot_save(mwhip_exec *exec, uint64_t snapshot);
+int mwhip_snapshot_restore(mwhip_exec *exec, uint64_t snapshot);
+int mwhip_snapshot_save_async(mwhip_exec *exec, uint64_t snapshot);
+int mwhip_snapshot_restore_async(mwhip_exec *exec, uint64_t snapshot);
+/* bytes the last save holds (waits for the stream); 0: never saved / unknown */
+uint64_t mwhip_snapshot_bytes(mwhip_exec *exec, uint64_t snapshot);
+/* UNSTABLE, measurement only (profiles/tools/snapshot_time.py needs it for its
+ * copy-per-segment yardstick): not part of what ABI 9 promises, may change or
+ * go without a version bump, and hands out raw device addresses that the next
+ * growth or sort invalidates -- do not build on it.  The segments of the last
+ * save as (live address, address in the snapshot, bytes) triples, at most
+ * max_out of them; returns how many there are.  Waits for the stream. */
+typedef struct mwhip_snapshot_segment {
+    void *live;
+    void *saved;
+    uint64_t num_bytes;
+} mwhip_snapshot_segment;
+int32_t mwhip_snapshot_segments(mwhip_exec *exec, uint64_t snapshot,
+                                mwhip_snapshot_segment *out, uint32_t max_out);
 
 #ifdef __cplusplus
 }

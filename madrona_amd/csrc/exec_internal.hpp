@@ -1,7 +1,8 @@
 // Host-side internals shared by the translation units of libmadrona_hip.so
 // (runtime.hip: the C ABI; runtime_state.hip: device state, world construction,
 // table growth; runtime_launch.hip: launch lists and step graphs;
-// runtime_kernels.hip: the runtime's own small kernels).  Not installed.
+// runtime_kernels.hip: the runtime's own small kernels; snapshot.hip: saving
+// and restoring all world state).  Not installed.
 #pragma once
 #include "runtime_internal.hpp"
 #include <madrona/tracing.hpp>
@@ -233,6 +234,8 @@ struct LaunchGraph {
 // other translation units)
 extern MWHIP_RT __thread std::vector<void *> *t_allocScope;   // (runtime_state.hip)
 
+struct mwhip_snapshot_rec;      // (snapshot.hip)
+
 struct mwhip_exec {
     mwhip_state_config cfg {};
     mwhip_user_entry entry {};
@@ -331,6 +334,9 @@ struct mwhip_exec {
     mwhip_render_layout renderLayout {};
     BvhNode *tlasNodes = nullptr;
     PreparedInstance *preparedInstances = nullptr;
+
+    // mwhip_snapshot_create: by handle, freed with the executor (freeSnapshots)
+    std::unordered_map<uint64_t, mwhip_snapshot_rec *> snapshots;
 };
 
 // ---- functions one translation unit defines and another calls ----------------------
@@ -380,6 +386,8 @@ MWHIP_RT int collectDeviceTrace(mwhip_exec *exec);
       // (runtime_state.hip)
 MWHIP_RT void writeDeviceTrace(mwhip_exec *exec);
       // (runtime_state.hip)
+MWHIP_RT void freeSnapshots(mwhip_exec *exec);
+      // (snapshot.hip)
 
 template <typename T>
 inline int devAllocT(mwhip_exec *exec, T **out, size_t count, bool zero = true)

@@ -627,6 +627,7 @@ extern "C" void mwhip_destroy(mwhip_exec *exec)
     for (auto &kv : exec->launchGraphs) {
         releaseLaunchGraph(*kv.second);
     }
+    freeSnapshots(exec);
     for (void *p : exec->allocations) {
         (void)hipFree(p);
     }

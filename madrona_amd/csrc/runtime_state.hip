@@ -575,6 +575,10 @@ MWHIP_RT const char *describeError(uint32_t flags)
                "instance table was not world-sorted, or a traversal stack "
                "overflowed";
     }
+    if (flags & kErrSnapshot) {
+        return "a queued snapshot restore was skipped: the save queued before "
+               "it had outgrown the snapshot (save into it again, synchronously)";
+    }
     return "unknown device error";
 }
 

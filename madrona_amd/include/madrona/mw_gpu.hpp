@@ -173,6 +173,78 @@ private:
 friend class MWCudaExecutor;
 };
 
+// Everything a batch of worlds is -- tables, entity store, per-world data, the
+// persistent region -- saved in device memory and put back, any number of times
+// (mwhip_snapshot_*, include/mwhip.h).  An extension of this backend: the
+// reference leaves checkpoints to each simulator.  Not rewound: the executor's
+// replay count (and the slot position of an input ring with it) and the ray
+// caster's output columns, which keep their contents until the next render
+// pass.  Belongs to the executor that made it and must not outlive it.
+class MWHipSnapshot {
+public:
+    MWHipSnapshot() : exec_(nullptr), snapshot_(0) {}
+    MWHipSnapshot(const MWHipSnapshot &) = delete;
+    MWHipSnapshot(MWHipSnapshot &&o) : exec_(o.exec_), snapshot_(o.snapshot_)
+    {
+        o.exec_ = nullptr;
+        o.snapshot_ = 0;
+    }
+
+    ~MWHipSnapshot()
+    {
+        if (exec_ != nullptr) {
+            mwhip_snapshot_destroy(exec_, snapshot_);
+        }
+    }
+
+    MWHipSnapshot &operator=(MWHipSnapshot &&o)
+    {
+        if (this != &o) {
+            if (exec_ != nullptr) {
+                mwhip_snapshot_destroy(exec_, snapshot_);
+            }
+            exec_ = o.exec_;
+            snapshot_ = o.snapshot_;
+            o.exec_ = nullptr;
+            o.snapshot_ = 0;
+        }
+        return *this;
+    }
+
+    // wait for the executor's stream; save() makes room for every row mapped
+    void save() { req(mwhip_snapshot_save(exec_, snapshot_), "save"); }
+    void restore() { req(mwhip_snapshot_restore(exec_, snapshot_), "restore"); }
+    // queued on the executor's stream behind the replays queued so far
+    void saveAsync() { req(mwhip_snapshot_save_async(exec_, snapshot_), "saveAsync"); }
+    void restoreAsync()
+    {
+        req(mwhip_snapshot_restore_async(exec_, snapshot_), "restoreAsync");
+    }
+    // bytes the last save holds
+    uint64_t numBytes() const { return mwhip_snapshot_bytes(exec_, snapshot_); }
+
+    uint64_t handle() const { return snapshot_; }
+
+private:
+    MWHipSnapshot(mwhip_exec *exec, uint64_t snapshot)
+        : exec_(exec), snapshot_(snapshot)
+    {}
+
+    static void req(int rc, const char *what)
+    {
+        if (rc != 0) {
+            fprintf(stderr, "madrona_amd: snapshot %s failed (%d): %s\n", what, rc,
+                    mwhip_last_error());
+            abort();
+        }
+    }
+
+    mwhip_exec *exec_;
+    uint64_t snapshot_;
+
+friend class MWCudaExecutor;
+};
+
 namespace detail {
 
 // A renderer's MeshBVHData / MaterialData (host or device memory) as the
@@ -451,6 +523,14 @@ public:
     void *getExported(CountT slot) const
     {
         return mwhip_get_exported(exec_, (uint32_t)slot);
+    }
+
+    // an empty snapshot of this executor's worlds (see MWHipSnapshot)
+    MWHipSnapshot makeSnapshot()
+    {
+        uint64_t snapshot = 0;
+        req(mwhip_snapshot_create(exec_, &snapshot), "makeSnapshot");
+        return MWHipSnapshot(exec_, snapshot);
     }
 
     mwhip_exec *handle() const { return exec_; }

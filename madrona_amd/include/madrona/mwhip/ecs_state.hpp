@@ -72,6 +72,11 @@ enum ColumnFlags : uint32_t {
 //                       table was unsorted / a traversal stack overflowed: the
 //                       rgb / depth outputs of that world's views are stale or
 //                       partial.
+//   kErrSnapshot        a queued mwhip_snapshot_restore_async found that the
+//                       save queued before it had overflowed (a table grew
+//                       past the snapshot's room while both were in flight):
+//                       NOTHING was restored, the worlds went on from where
+//                       they were.
 //   the others          (entity store, tmpAlloc, constructor blocks, sort
 //                       look-back) leave the tables in an undefined state:
 //                       discard the executor.
@@ -84,6 +89,7 @@ enum ErrorFlags : uint32_t {
     kErrPersistOverflow = 1u << 5,
     kErrPhysics = 1u << 6,
     kErrRender = 1u << 7,
+    kErrSnapshot = 1u << 8,
 };
 
 struct TableHdr {

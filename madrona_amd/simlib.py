@@ -150,7 +150,85 @@ def runtime_lib() -> C.CDLL:
     lib.mwhip_pack_rows.restype = C.c_int
     lib.mwhip_pack_rows.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p),
                                     C.POINTER(C.c_uint32), C.c_uint32, C.c_void_p]
+    lib.mwhip_snapshot_create.restype = C.c_int
+    lib.mwhip_snapshot_create.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.mwhip_snapshot_destroy.restype = None
+    lib.mwhip_snapshot_destroy.argtypes = [C.c_void_p, C.c_uint64]
+    for fn in (lib.mwhip_snapshot_save, lib.mwhip_snapshot_restore,
+               lib.mwhip_snapshot_save_async, lib.mwhip_snapshot_restore_async):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_uint64]
+    lib.mwhip_snapshot_bytes.restype = C.c_uint64
+    lib.mwhip_snapshot_bytes.argtypes = [C.c_void_p, C.c_uint64]
     return lib
+
+
+class Snapshot:
+    """One saved copy of all world state of a HIP-backend simulator, in device
+    memory (mwhip_snapshot_*, include/mwhip.h): save() / restore() wait,
+    save_async() / restore_async() are queued on the executor's stream behind
+    the replays queued so far (step_async).  Reusable; belongs to the
+    simulator that made it; Simulator.close() frees what is left and empties
+    those snapshots (their close() then does nothing, any other call raises).
+    Not rewound: the executor's replay count (the input
+    ring's slot position) and the rgb / depth outputs of the render pass."""
+
+    def __init__(self, sim: "Simulator"):
+        self._rt = runtime_lib()
+        self._exec = sim.hip_exec()
+        if not self._exec:
+            raise RuntimeError("snapshots need the HIP backend")
+        handle = C.c_uint64(0)
+        self._check(self._rt.mwhip_snapshot_create(self._exec, C.byref(handle)),
+                    "mwhip_snapshot_create")
+        self.handle = int(handle.value)
+
+    def _check(self, rc: int, what: str) -> None:
+        if rc != 0:
+            raise RuntimeError(f"{what} -> {rc}: {self._rt.mwhip_last_error().decode()}")
+
+    def _live(self) -> int:
+        # (the executor pointer dies with the simulator: never passed on then)
+        if not self.handle:
+            raise RuntimeError("this snapshot is closed (or its simulator is)")
+        return self.handle
+
+    def _orphan(self) -> None:
+        """Simulator.close(): the executor has freed (or is about to free) it."""
+        self.handle = 0
+        self._exec = 0
+
+    def save(self) -> None:
+        self._check(self._rt.mwhip_snapshot_save(self._exec, self._live()),
+                    "mwhip_snapshot_save")
+
+    def restore(self) -> None:
+        self._check(self._rt.mwhip_snapshot_restore(self._exec, self._live()),
+                    "mwhip_snapshot_restore")
+
+    def save_async(self) -> None:
+        self._check(self._rt.mwhip_snapshot_save_async(self._exec, self._live()),
+                    "mwhip_snapshot_save_async")
+
+    def restore_async(self) -> None:
+        self._check(self._rt.mwhip_snapshot_restore_async(self._exec, self._live()),
+                    "mwhip_snapshot_restore_async")
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes the last save holds (waits for the executor's stream)."""
+        return int(self._rt.mwhip_snapshot_bytes(self._exec, self._live()))
+
+    def close(self) -> None:
+        if self.handle:
+            self._rt.mwhip_snapshot_destroy(self._exec, self.handle)
+            self.handle = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class Simulator:
@@ -175,6 +253,7 @@ class Simulator:
             raise RuntimeError(f"sim_create failed for {lib_path}")
         self.backend = self.lib.sim_backend(self.handle).decode()
         self._async = None
+        self._snapshots: List["Snapshot"] = []
         self._tensor_info: Dict[str, Tuple[int, np.dtype, Tuple[int, ...], bool]] = {}
         for i in range(self.lib.sim_num_tensors(self.handle)):
             info = SimTensorInfo()
@@ -191,6 +270,10 @@ class Simulator:
     # -- lifecycle ---------------------------------------------------------
     def close(self) -> None:
         if self.handle:
+            # sim_destroy frees the executor and its snapshots with it
+            for snap in self._snapshots:
+                snap._orphan()
+            self._snapshots.clear()
             self.lib.sim_destroy(self.handle)
             self.handle = None
 
@@ -293,6 +376,15 @@ class Simulator:
 
     def hip_exec(self) -> int:
         return int(self.lib.sim_hip_exec(self.handle) or 0)
+
+    def snapshot(self) -> "Snapshot":
+        """A new, empty Snapshot of this simulator (HIP backend; raises on the
+        reference backend, which has no executor to ask)."""
+        if self.backend != "hip":
+            raise RuntimeError(f"snapshots need the HIP backend, this is {self.backend!r}")
+        snap = Snapshot(self)
+        self._snapshots.append(snap)
+        return snap
 
     # ---- stream-ordered stepping (HIP backend) -----------------------------------
     def stream(self) -> int:

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
+#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded(); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
 
 typedef struct mwhip_exec mwhip_exec; /* opaque; == MWCudaExecutor::Impl */
 
@@ -484,6 +484,49 @@ int mwhip_pack_rows(mwhip_exec *exec, uint32_t num_columns,
 int mwhip_set_input_ring(mwhip_exec *exec, void *dst, const void *ring,
                          uint64_t slot_bytes, uint32_t num_slots);
 
+/* Device-resident output rings (added under ABI 9): the k-th replay after this
+ * call (k = 0, 1, ...) of ANY graph of the executor of kind `when` -- step graphs
+ * (mwhip_build_launch_graph, mwhip_build_launch_graph_with_pack) or render
+ * graphs (mwhip_build_render_graph) -- copies slot_bytes bytes from `src` --
+ * normally an exported column, any device address works -- into
+ * ring + (k % num_slots) * slot_bytes, as its last act before its health kernel
+ * (behind the pack node of a graph that has one).  K queued replays so leave a
+ * time-major [K, ...] trajectory behind with nothing foreign on the executor's
+ * stream between two graph launches.  Step replays do not
+ * advance render rings nor render replays step rings; inside one step replay
+ * the input rings and the output rings see the same k: slot k holds what the
+ * step that consumed action slot k produced.  slot_bytes is any count >= 1
+ * (images, 1-byte flags): the copy is 16 bytes, 4 bytes or 1 byte wide by the
+ * alignment of source and slot, chosen per replay on the device.  All rings of
+ * one kind share ONE kernel launch per replay.
+ * ring == NULL removes the ring of (src, when); setting a pair that has a ring
+ * replaces it and restarts k at 0.  At most MWHIP_MAX_OUTPUT_RINGS rings per
+ * executor over both kinds.  The ring is the caller's memory: it must stay
+ * allocated until it is removed or the executor destroyed, and not reading a
+ * slot while a queued replay rewrites it is the caller's job.  Like
+ * mwhip_set_input_ring: waits for the executor's stream and rebuilds the launch
+ * graphs (handles stay valid).  The rings keep their position over later
+ * rebuilds (table growth, mwhip_set_input_ring); a snapshot restore does not
+ * rewind them (they hang off the replay counters).
+ * Errors (non-zero, text in mwhip_last_error(), nothing changed): a null src;
+ * zero slots or zero bytes with a non-null ring; a seventeenth ring; an unknown
+ * `when`.  (No reference counterpart; its per-step recorder,
+ * madrona::viz::Recorder, is render side only.) */
+#define MWHIP_MAX_OUTPUT_RINGS 16
+#define MWHIP_RING_ON_STEP   0u   /* recorded by every replay of a step graph   */
+#define MWHIP_RING_ON_RENDER 1u   /* recorded by every replay of a render graph */
+int mwhip_set_output_ring(mwhip_exec *exec, const void *src, void *ring,
+                          uint64_t slot_bytes, uint32_t num_slots, uint32_t when);
+/* Waits for the executor's stream; *replays_out = replays that have recorded
+ * into the ring of (src, when) since it was set (NOT modulo num_slots).
+ * The device counts replays in 32 bits: the count returns to 0 after 2^32
+ * replays of that kind since the ring was set, and at that point the slot
+ * position jumps unless num_slots is a power of two (set the ring again
+ * before then; mwhip_set_input_ring's rings share this).
+ * Non-zero (and a message) when the pair has no ring. */
+int mwhip_output_ring_recorded(mwhip_exec *exec, const void *src, uint32_t when,
+                               uint64_t *replays_out);
+
 /* Queues a one-wave marker kernel (benchWindowMarker) on the executor's stream:
  * a pair of them brackets a measurement window in a rocprofv3 kernel trace
  * (profiles/summarize_rocprof.py trims to it).  Measurement only. */
@@ -521,7 +564,7 @@ int32_t mwhip_profile(mwhip_exec *exec, uint64_t graph, uint32_t reps,
  * stream-ordered behind the replays queued before them.  A snapshot can be
  * saved into and restored from any number of times, by the executor that made
  * it.  NOT rewound: the executor's replay counters (and with them the input
- * rings' slot position), errorFlags, capacities, and the ray caster's output
+ * and output rings' slot position), errorFlags, capacities, and the ray caster's output
  * columns (derived state: they keep their contents until the next render
  * pass).  (No reference counterpart.)
  *

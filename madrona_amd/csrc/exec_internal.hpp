@@ -73,6 +73,23 @@ struct PackArgs {
     uint32_t numRows;
 };
 
+// every output ring of one kind (mwhip_set_output_ring), the kernel argument of
+// outputRingKernel
+struct OutputRingArgs {
+    struct Ring {
+        const char *src;
+        char *ring;
+        uint64_t slotBytes;
+        uint32_t numSlots;
+        uint32_t firstReplay;   // replays of the kind completed when the ring was set
+    };
+    Ring rings[MWHIP_MAX_OUTPUT_RINGS];
+    uint64_t totalChunks;       // 16 KiB chunks over all rings
+    uint32_t numRings;
+    uint32_t counterWord;       // kStepReplayWord / kRenderReplayWord
+};
+constexpr uint64_t kOutputRingChunk = 16u << 10;    // == kCopyChunk (copy_chunk.hpp)
+
 // layout of the pinned health record (int32 words)
 constexpr uint32_t kStatsRows = 2;                          // [kMaxArchetypes]
 constexpr uint32_t kStatsGate = 2 + kMaxArchetypes;         // profiling gate flag
@@ -84,6 +101,9 @@ constexpr uint32_t kStatsWords = 4 + 3 * kMaxArchetypes;
 // word of the replay-signal block that counts completed replays of STEP graphs
 // only (the ones that start with the input rings); word 0 counts every replay
 constexpr uint32_t kStepReplayWord = 16;
+// ... and the one that counts completed replays of RENDER graphs (the render
+// kind of output rings hangs off it)
+constexpr uint32_t kRenderReplayWord = 17;
 
 // host stubs of those kernels (for KernelLaunch::fn / hipLaunchKernel)
 MWHIP_RT const void *miscOpsKernelFn();
@@ -92,6 +112,7 @@ MWHIP_RT const void *gateKernelFn();
 MWHIP_RT const void *benchWindowMarkerFn();
 MWHIP_RT const void *packRowsKernelFn();
 MWHIP_RT const void *inputRingKernelFn();
+MWHIP_RT const void *outputRingKernelFn();
 #ifdef MADRONA_TRACING
 MWHIP_RT const void *traceMarkKernelFn();
 #endif
@@ -302,6 +323,13 @@ struct mwhip_exec {
         uint32_t firstReplay;   // replays completed when the ring was set
     };
     std::vector<InputRing> inputRings;
+
+    // mwhip_set_output_ring: at most MWHIP_MAX_OUTPUT_RINGS over both kinds
+    struct OutputRing {
+        OutputRingArgs::Ring ring;
+        uint32_t when;          // MWHIP_RING_ON_STEP / MWHIP_RING_ON_RENDER
+    };
+    std::vector<OutputRing> outputRings;
 
     // MADRONA_TRACING builds: the device event log (mw_gpu/tracing.hpp), the
     // records of the first steps, the names funcID indexes

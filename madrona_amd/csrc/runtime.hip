@@ -1109,6 +1109,91 @@ extern "C" int mwhip_set_input_ring(mwhip_exec *exec, void *dst, const void *rin
     return rebuildAllLaunchGraphs(exec);
 }
 
+static std::vector<mwhip_exec::OutputRing>::iterator
+findOutputRing(mwhip_exec *exec, const void *src, uint32_t when)
+{
+    auto &rings = exec->outputRings;
+    return std::find_if(rings.begin(), rings.end(),
+        [src, when](const mwhip_exec::OutputRing &r) {
+            return (const void *)r.ring.src == src && r.when == when;
+        });
+}
+
+static int completedReplays(mwhip_exec *exec, uint32_t when, uint32_t *out)
+{
+    HIPCHK(hipStreamSynchronize(exec->stream));
+    HIPCHK(hipMemcpy(out, exec->replaySignal +
+        (when == MWHIP_RING_ON_RENDER ? kRenderReplayWord : kStepReplayWord),
+        sizeof(*out), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int mwhip_set_output_ring(mwhip_exec *exec, const void *src, void *ring,
+                                     uint64_t slot_bytes, uint32_t num_slots,
+                                     uint32_t when)
+{
+    // (every refusal comes before anything changes)
+    if (src == nullptr) {
+        return fail(-2, "set_output_ring: no source");
+    }
+    if (when != MWHIP_RING_ON_STEP && when != MWHIP_RING_ON_RENDER) {
+        return fail(-2, "set_output_ring: when = %u (MWHIP_RING_ON_STEP or "
+                    "MWHIP_RING_ON_RENDER)", when);
+    }
+    if (ring != nullptr && (num_slots == 0 || slot_bytes == 0)) {
+        return fail(-2, "set_output_ring: %llu bytes x %u slots (at least one of "
+                    "each)", (unsigned long long)slot_bytes, num_slots);
+    }
+    if (exec == nullptr) {
+        return fail(-2, "set_output_ring: no executor");
+    }
+    auto &rings = exec->outputRings;
+    auto at = findOutputRing(exec, src, when);
+    if (ring != nullptr && at == rings.end() &&
+            rings.size() >= MWHIP_MAX_OUTPUT_RINGS) {
+        return fail(-2, "set_output_ring: at most %u rings",
+                    (uint32_t)MWHIP_MAX_OUTPUT_RINGS);
+    }
+    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
+    if (ring == nullptr) {
+        if (at == rings.end()) return 0;
+        rings.erase(at);
+    } else {
+        // (every replay of every graph of that kind counts from here on)
+        uint32_t done = 0;
+        int rc = completedReplays(exec, when, &done);
+        if (rc != 0) return rc;
+        const mwhip_exec::OutputRing fresh {
+            { (const char *)src, (char *)ring, slot_bytes, num_slots, done }, when };
+        if (at != rings.end()) {
+            *at = fresh;
+        } else {
+            rings.push_back(fresh);
+        }
+    }
+    return rebuildAllLaunchGraphs(exec);
+}
+
+extern "C" int mwhip_output_ring_recorded(mwhip_exec *exec, const void *src,
+                                          uint32_t when, uint64_t *replays_out)
+{
+    if (exec == nullptr || replays_out == nullptr) {
+        return fail(-2, "output_ring_recorded: no executor / no result");
+    }
+    auto at = findOutputRing(exec, src, when);
+    if (at == exec->outputRings.end()) {
+        return fail(-2, "output_ring_recorded: no output ring of kind %u on %p",
+                    when, src);
+    }
+    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
+    uint32_t done = 0;
+    int rc = completedReplays(exec, when, &done);
+    if (rc != 0) return rc;
+    // (the device counts in 32 bits and wraps; so does the difference)
+    *replays_out = (uint32_t)(done - at->ring.firstReplay);
+    return 0;
+}
+
 // Another stream waits for every replay queued so far WITHOUT touching the
 // executor's stream: the last kernel of each replay bumps a counter in signal
 // memory and the waiting stream polls it (hipStreamWaitValue32).  An event
@@ -1445,6 +1530,7 @@ extern "C" int32_t mwhip_profile(mwhip_exec *exec, uint64_t graph, uint32_t reps
             total_us[i] += (double)ms * 1000.0;
 
             const KernelLaunch &k = lg.launches[i];
+            total_bytes[i] += k.fixedBytes;
             if (k.kind == MWHIP_NODE_KERNEL &&
                     k.countMode == MWHIP_COUNT_QUERY_ROWS) {
                 // rows at the start of the step (steady-state approximation)

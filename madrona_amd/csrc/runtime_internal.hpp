@@ -181,7 +181,7 @@ struct KernelLaunch {
     const void *fn = nullptr;
     dim3 grid { 1, 1, 1 };
     dim3 block { 1, 1, 1 };
-    alignas(16) unsigned char argStorage[320] {};
+    alignas(16) unsigned char argStorage[576] {};    // (the largest: OutputRingArgs)
     uint32_t argOffsets[9] {};
     uint32_t numArgs = 0;
     uint32_t dynamicLds = 0;        // bytes of dynamic LDS
@@ -191,6 +191,7 @@ struct KernelLaunch {
     uint32_t kind = MWHIP_NODE_KERNEL;
     uint32_t archetype = 0xFFFFFFFFu;
     uint32_t bytesPerRow = 0;
+    double fixedBytes = 0;          // algorithmic bytes of a launch that has no rows
     uint32_t ioDeclared = 0;        // bytesPerRow from a declared read / write set
     uint32_t nodeIndex = 0xFFFFFFFFu;   // position of the node in its task graph's order
     uint32_t countMode = 0;

@@ -1082,6 +1082,37 @@ MWHIP_RT int instantiateLaunchGraph(mwhip_exec *exec,
         lg->launches.insert(lg->launches.end() - 1, k);
     }
 
+    // the output rings of this graph's kind: one launch for all of them, the
+    // replay's last act before its health kernel (behind the pack node)
+    {
+        const uint32_t when = lg->isRender ? MWHIP_RING_ON_RENDER : MWHIP_RING_ON_STEP;
+        OutputRingArgs args {};
+        args.counterWord = lg->isRender ? kRenderReplayWord : kStepReplayWord;
+        uint64_t bytes = 0;
+        for (const mwhip_exec::OutputRing &out_ring : exec->outputRings) {
+            if (out_ring.when != when) continue;
+            args.rings[args.numRings++] = out_ring.ring;
+            args.totalChunks += (out_ring.ring.slotBytes + kOutputRingChunk - 1) /
+                kOutputRingChunk;
+            bytes += out_ring.ring.slotBytes;
+        }
+        if (args.numRings != 0) {
+            KernelLaunch k;
+            static_assert(sizeof(void *) + sizeof(OutputRingArgs) <=
+                          sizeof(k.argStorage));
+            k.fn = outputRingKernelFn();
+            k.grid = dim3((uint32_t)std::min<uint64_t>(args.totalChunks,
+                                                       8ull * exec->numCUs), 1, 1);
+            k.block = dim3(256, 1, 1);
+            k.setArgs(exec->stateDev, args);
+            k.name = "ring";
+            k.role = lg->isRender ? "ring.out.render" : "ring.out";
+            k.kind = MWHIP_NODE_RECYCLE;
+            k.fixedBytes = 2.0 * (double)bytes;     // read + written
+            lg->launches.insert(lg->launches.end() - 1, k);
+        }
+    }
+
 #ifdef MADRONA_TRACING
     rc = addTraceMarkers(exec, *lg);
     if (rc != 0) return rc;

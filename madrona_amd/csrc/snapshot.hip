@@ -22,11 +22,12 @@
 // whichever side is current then) -- no kernel of a restore writes them.
 // No atomics, no spin-waits: two plain launches on the executor's stream.
 #include "exec_internal.hpp"
+#include "copy_chunk.hpp"
 
 namespace {
 
-constexpr uint32_t kSnapThreads = 256;
-constexpr uint32_t kSnapChunk = 16u << 10;      // bytes per (segment, chunk) pair
+constexpr uint32_t kSnapThreads = kCopyThreads;
+constexpr uint32_t kSnapChunk = kCopyChunk;     // bytes per (segment, chunk) pair
 constexpr uint64_t kSnapAlign = 256;            // every segment's place in the snapshot
 
 // where a segment's length comes from when it is saved
@@ -198,54 +199,6 @@ snapshotMeasure(const EcsState *S, SnapHeader *hdr, SnapReport *report)
     }
 }
 
-typedef uint32_t SnapU4 __attribute__((ext_vector_type(4)));
-using GlobalU4 = __attribute__((address_space(1))) SnapU4;
-using GlobalU32 = __attribute__((address_space(1))) uint32_t;
-using GlobalU8 = __attribute__((address_space(1))) uint8_t;
-
-// n <= kSnapChunk bytes, the whole workgroup
-__device__ inline void snapCopyChunk(char *dst, const char *src, uint32_t n)
-{
-    const uint32_t tid = threadIdx.x;
-    const unsigned long long both = (unsigned long long)dst | (unsigned long long)src;
-    uint32_t done = 0;
-    if ((both & 15ull) == 0ull) {
-        // 16 bytes per lane, every load of the chunk in flight before a store
-        constexpr uint32_t kPerThread = kSnapChunk / 16u / kSnapThreads;
-        const GlobalU4 *s4 = (const GlobalU4 *)(unsigned long long)src;
-        GlobalU4 *d4 = (GlobalU4 *)(unsigned long long)dst;
-        const uint32_t num_vec = n >> 4;
-        SnapU4 v[kPerThread];
-#pragma unroll
-        for (uint32_t j = 0; j < kPerThread; j++) {
-            const uint32_t i = j * kSnapThreads + tid;
-            if (i < num_vec) v[j] = s4[i];
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < kPerThread; j++) {
-            const uint32_t i = j * kSnapThreads + tid;
-            if (i < num_vec) d4[i] = v[j];
-        }
-        done = num_vec << 4;
-    } else if ((both & 3ull) == 0ull) {
-        // (header words: their live side is a field of a struct)
-        const GlobalU32 *s1 = (const GlobalU32 *)(unsigned long long)src;
-        GlobalU32 *d1 = (GlobalU32 *)(unsigned long long)dst;
-        const uint32_t num_words = n >> 2;
-        for (uint32_t i = tid; i < num_words; i += kSnapThreads) {
-            d1[i] = s1[i];
-        }
-        done = num_words << 2;
-    }
-    // the odd bytes at the end (columns of 1, 2 bytes per row), or everything
-    // when an address is not even dword aligned
-    const GlobalU8 *s8 = (const GlobalU8 *)(unsigned long long)src;
-    GlobalU8 *d8 = (GlobalU8 *)(unsigned long long)dst;
-    for (uint32_t i = done + tid; i < n; i += kSnapThreads) {
-        d8[i] = s8[i];
-    }
-}
-
 // Save (second launch) and restore (the only one).  restore: nothing is moved
 // unless the snapshot holds a complete save -- and then the executor is told:
 // kErrSnapshot in errorFlags (sticky: every later replay's health kernel
@@ -292,9 +245,9 @@ snapshotCopy(EcsState *S, int32_t *stats_host, SnapHeader *hdr, char *data,
         char *live = seg.liveSlot != nullptr ? (char *)*seg.liveSlot : seg.live;
         char *saved = data + seg.savedOffset;
         if (restore != 0u) {
-            snapCopyChunk(live + off, saved + off, n);
+            copyChunk(live + off, saved + off, n);
         } else {
-            snapCopyChunk(saved + off, live + off, n);
+            copyChunk(saved + off, live + off, n);
         }
     }
 }

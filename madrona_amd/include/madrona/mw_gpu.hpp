@@ -177,7 +177,7 @@ friend class MWCudaExecutor;
 // persistent region -- saved in device memory and put back, any number of times
 // (mwhip_snapshot_*, include/mwhip.h).  An extension of this backend: the
 // reference leaves checkpoints to each simulator.  Not rewound: the executor's
-// replay count (and the slot position of an input ring with it) and the ray
+// replay count (and the slot position of the input and output rings with it) and the ray
 // caster's output columns, which keep their contents until the next render
 // pass.  Belongs to the executor that made it and must not outlive it.
 class MWHipSnapshot {
@@ -531,6 +531,39 @@ public:
         uint64_t snapshot = 0;
         req(mwhip_snapshot_create(exec_, &snapshot), "makeSnapshot");
         return MWHipSnapshot(exec_, snapshot);
+    }
+
+    // Device-resident rings (extensions of this backend, include/mwhip.h).
+    // The k-th replay of a step graph after the call starts by copying slot
+    // k % num_slots of `ring` (whole dwords) into `dst`, normally an exported
+    // action column; ring == nullptr removes the ring of dst
+    void setInputRing(void *dst, const void *ring, uint64_t slot_bytes,
+                      uint32_t num_slots)
+    {
+        req(mwhip_set_input_ring(exec_, dst, ring, slot_bytes, num_slots),
+            "setInputRing");
+    }
+
+    // ... and ends (before its health kernel) by copying slot_bytes bytes of
+    // `src` into slot k % num_slots of `ring`; on_render: replays of a render
+    // graph record instead.  ring == nullptr removes the ring of (src, kind)
+    void setOutputRing(const void *src, void *ring, uint64_t slot_bytes,
+                       uint32_t num_slots, bool on_render = false)
+    {
+        req(mwhip_set_output_ring(exec_, src, ring, slot_bytes, num_slots,
+                on_render ? MWHIP_RING_ON_RENDER : MWHIP_RING_ON_STEP),
+            "setOutputRing");
+    }
+
+    // replays that have recorded into that ring since it was set (waits for
+    // the executor's stream; not modulo its slots)
+    uint64_t outputRingRecorded(const void *src, bool on_render = false)
+    {
+        uint64_t replays = 0;
+        req(mwhip_output_ring_recorded(exec_, src,
+                on_render ? MWHIP_RING_ON_RENDER : MWHIP_RING_ON_STEP, &replays),
+            "outputRingRecorded");
+        return replays;
     }
 
     mwhip_exec *handle() const { return exec_; }

@@ -145,6 +145,12 @@ def runtime_lib() -> C.CDLL:
     lib.mwhip_set_input_ring.restype = C.c_int
     lib.mwhip_set_input_ring.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_uint64, C.c_uint32]
+    lib.mwhip_set_output_ring.restype = C.c_int
+    lib.mwhip_set_output_ring.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_uint64, C.c_uint32, C.c_uint32]
+    lib.mwhip_output_ring_recorded.restype = C.c_int
+    lib.mwhip_output_ring_recorded.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32,
+                                               C.POINTER(C.c_uint64)]
     lib.mwhip_mark_window.restype = C.c_int
     lib.mwhip_mark_window.argtypes = [C.c_void_p, C.c_uint32]
     lib.mwhip_pack_rows.restype = C.c_int
@@ -231,6 +237,124 @@ class Snapshot:
         self.close()
 
 
+RING_ON_STEP = 0      # MWHIP_RING_ON_STEP
+RING_ON_RENDER = 1    # MWHIP_RING_ON_RENDER
+
+
+class Trajectory:
+    """Exported tensors of a HIP-backend simulator recorded per step on the
+    device (mwhip_set_output_ring, include/mwhip.h): traj[name] is a torch
+    tensor [steps, *dims] of the tensor's dtype on the simulator's device, and
+    the k-th replay after record() -- of the step graph, or of the render graph
+    with on_render -- leaves the tensor as it is when the replay ends in slot
+    k % steps.  Nothing foreign sits on the executor's stream between two
+    replays: queue them with step_async and read when they are done (sync(),
+    stream_wait_replays()); a slot that a replay still queued will rewrite must
+    not be read before that replay is through.  A ring is named by (tensor,
+    kind) on the executor, so a tensor that an open trajectory of the same kind
+    already records is refused (ValueError) rather than taken over.  close()
+    removes the rings and lets the simulator forget the trajectory;
+    Simulator.close() orphans what is left (the tensors stay valid)."""
+
+    def __init__(self, sim: "Simulator", names: List[str], steps: int,
+                 on_render: bool = False):
+        import torch
+
+        self._rt = runtime_lib()
+        self._exec = sim.hip_exec()
+        if not self._exec:
+            raise RuntimeError("recording needs the HIP backend")
+        if steps < 1:
+            raise ValueError("record(): at least one step")
+        self.steps = int(steps)
+        self._when = RING_ON_RENDER if on_render else RING_ON_STEP
+        names = list(names)
+        taken = [name for name in names if names.count(name) > 1 or any(
+            other._when == self._when and name in other._srcs
+            for other in sim._trajectories)]
+        if taken:
+            raise ValueError(
+                f"record(): {sorted(set(taken))} named twice or already recorded by an "
+                "open trajectory of this kind (close() it first)")
+        # (the simulator's list of open trajectories; close() leaves it)
+        self._open_in = sim._trajectories
+        self._tensors: Dict[str, "torch.Tensor"] = {}
+        self._srcs: Dict[str, int] = {}
+        device = torch.device("cuda", sim.gpu_id)
+        for name in names:
+            _, dtype, dims, _ = sim.tensor_meta(name)
+            self._tensors[name] = torch.zeros(
+                (self.steps, *dims), device=device,
+                dtype=torch.from_numpy(np.empty(0, dtype)).dtype)
+        # (the fills run on torch's stream, the replays on the executor's)
+        torch.cuda.synchronize(device)
+        try:
+            for name, ring in self._tensors.items():
+                src = sim.tensor_ptr(name)
+                self._check(self._rt.mwhip_set_output_ring(
+                    self._exec, src, ring.data_ptr(),
+                    ring[0].numel() * ring.element_size(), self.steps, self._when),
+                    f"mwhip_set_output_ring({name})")
+                self._srcs[name] = src
+        except Exception:
+            self.close()
+            raise
+
+    def _check(self, rc: int, what: str) -> None:
+        if rc != 0:
+            raise RuntimeError(f"{what} -> {rc}: {self._rt.mwhip_last_error().decode()}")
+
+    def _orphan(self) -> None:
+        """Simulator.close(): the executor (and its rings) is gone."""
+        self._exec = 0
+        self._srcs = {}
+        self._open_in = None
+
+    def __getitem__(self, name: str):
+        return self._tensors[name]
+
+    @property
+    def names(self) -> List[str]:
+        return list(self._tensors.keys())
+
+    @property
+    def recorded(self) -> int:
+        """Replays that have recorded since record() (waits for the executor's
+        stream; not taken modulo `steps`)."""
+        if not self._exec or not self._srcs:
+            raise RuntimeError("this trajectory is closed (or its simulator is)")
+        out = C.c_uint64(0)
+        self._check(self._rt.mwhip_output_ring_recorded(
+            self._exec, next(iter(self._srcs.values())), self._when, C.byref(out)),
+            "mwhip_output_ring_recorded")
+        return int(out.value)
+
+    def slot(self, k: int) -> int:
+        """Index along dimension 0 of what replay k (0-based) recorded."""
+        return int(k) % self.steps
+
+    def close(self) -> None:
+        """Removes the rings (waits for the executor's stream); the tensors keep
+        what has been recorded."""
+        if self._exec:
+            for name, src in self._srcs.items():
+                self._rt.mwhip_set_output_ring(self._exec, src, None, 0, 0, self._when)
+        self._srcs = {}
+        self._exec = 0
+        # the simulator keeps open trajectories only: the ring tensors live as
+        # long as the caller holds this object, no longer
+        if self._open_in is not None:
+            if self in self._open_in:
+                self._open_in.remove(self)
+            self._open_in = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class Simulator:
     """One simulator instance behind the C API (either backend)."""
 
@@ -247,6 +371,7 @@ class Simulator:
         self.lib = C.CDLL(lib_path, mode=C.RTLD_LOCAL)
         _bind(self.lib)
         self.num_worlds = num_worlds
+        self.gpu_id = gpu_id
         args = SimCreateArgs(num_worlds, seed, gpu_id, num_workers, world_base, flags)
         self.handle = self.lib.sim_create(C.byref(args))
         if not self.handle:
@@ -254,6 +379,7 @@ class Simulator:
         self.backend = self.lib.sim_backend(self.handle).decode()
         self._async = None
         self._snapshots: List["Snapshot"] = []
+        self._trajectories: List["Trajectory"] = []
         self._tensor_info: Dict[str, Tuple[int, np.dtype, Tuple[int, ...], bool]] = {}
         for i in range(self.lib.sim_num_tensors(self.handle)):
             info = SimTensorInfo()
@@ -274,6 +400,10 @@ class Simulator:
             for snap in self._snapshots:
                 snap._orphan()
             self._snapshots.clear()
+            # ... and forgets its output rings (the trajectories keep their tensors)
+            for traj in self._trajectories:
+                traj._orphan()
+            self._trajectories.clear()
             self.lib.sim_destroy(self.handle)
             self.handle = None
 
@@ -385,6 +515,19 @@ class Simulator:
         snap = Snapshot(self)
         self._snapshots.append(snap)
         return snap
+
+    def record(self, names: List[str], steps: int, on_render: bool = False) -> "Trajectory":
+        """Records the exported tensors `names` on the device from the next
+        replay on, `steps` slots each (see Trajectory): every replay of the
+        step graph -- step(), step_async(), packed graphs -- or, with
+        on_render, of the render graph.  HIP backend; raises on the reference
+        backend, which has no executor to ask."""
+        if self.backend != "hip":
+            raise RuntimeError(
+                f"recording on the device needs the HIP backend, this is {self.backend!r}")
+        traj = Trajectory(self, names, steps, on_render)
+        self._trajectories.append(traj)
+        return traj
 
     # ---- stream-ordered stepping (HIP backend) -----------------------------------
     def stream(self) -> int:

@@ -1,0 +1,529 @@
+"""-m gpu: device-resident output rings (mwhip_set_output_ring,
+Simulator.record()).
+
+The oracle is a TWIN: a second simulator of the same library, seed and inputs,
+stepped one step at a time by hand and read after every step.  A ring must hold,
+bit for bit, what the twin's tensor held after the step (or render pass) that
+wrote the slot.  Shapes are the smallest at which the copy kernel's branches
+differ: odd world counts (slots that alternate between 16-, 8- and 4-byte
+alignment), slot sizes on both sides of a 16-byte vector and of a 16 KiB chunk,
+sources that are not dword aligned."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from madrona_amd.simlib import (RING_ON_RENDER, RING_ON_STEP, Simulator, hip_lib_path,
+                                runtime_lib)
+from madrona_amd.tensor import DeviceColumn
+
+pytestmark = pytest.mark.gpu
+
+W_ODD = 37
+SENTINEL = 0xA5
+
+
+def _torch():
+    import torch
+    assert torch.cuda.is_available()
+    return torch
+
+
+def _escape(worlds=W_ODD, flags=9, sim="escape_room"):
+    return Simulator(hip_lib_path(sim), worlds, seed=5, flags=flags)
+
+
+def _action(worlds, t, grab=False):
+    rng = np.random.default_rng([31, t, worlds])
+    shape = (worlds, 2)
+    return np.stack([rng.integers(0, 4, shape), rng.integers(0, 8, shape),
+                     rng.integers(-2, 3, shape),
+                     rng.integers(0, 2, shape) if grab else np.zeros(shape, int)],
+                    -1).astype(np.int32)
+
+
+def _bytes(array):
+    return np.ascontiguousarray(array).reshape(-1).view(np.uint8)
+
+
+def _slot_bytes(traj, name, slot):
+    return _bytes(traj[name][slot].cpu().numpy())
+
+
+def _read_all(sim, names):
+    return {name: _bytes(sim.read_tensor(name)) for name in names}
+
+
+def _assert_slot(traj, name, slot, want, what):
+    got = _slot_bytes(traj, name, slot)
+    assert got.shape == want.shape and np.array_equal(got, want), (what, name, slot)
+
+
+def _set_ring(rt, sim, src, ring_ptr, slot_bytes, slots, when=RING_ON_STEP):
+    return rt.mwhip_set_output_ring(sim.hip_exec(), src, ring_ptr or None, slot_bytes,
+                                    slots, when)
+
+
+def _recorded(rt, sim, src, when=RING_ON_STEP):
+    out = C.c_uint64(0)
+    rc = rt.mwhip_output_ring_recorded(sim.hip_exec(), src, when, C.byref(out))
+    assert rc == 0, rt.mwhip_last_error()
+    return int(out.value)
+
+
+def _device_bytes(ptr, count):
+    """A torch uint8 view of `count` bytes of device memory at `ptr`."""
+    torch = _torch()
+    return torch.as_tensor(DeviceColumn(ptr, np.uint8, (count,)), device="cuda")
+
+
+# ---- 1. every step, with wrap-around ----------------------------------------------
+def test_every_step_is_recorded_and_the_rings_wrap(built):
+    """All ten exported tensors of escape_room at 37 worlds ([37,1] int32 is
+    148 B a slot, [37,2,1] 296 B: successive slots are 16-, 8- and 4-byte
+    aligned in turn) on rings of 5 slots, 23 replays queued back to back."""
+    torch = _torch()
+    with _escape() as sim, _escape() as twin:
+        names = sim.tensor_names
+        assert len(names) == 10
+        for s in (sim, twin):
+            s.write_tensor("action", _action(W_ODD, 0))
+        traj = sim.record(names, 5)
+        sim.step_async(23)
+        want = {}
+        for k in range(23):
+            twin.step(1)
+            if k >= 18:
+                want[k] = _read_all(twin, names)
+        sim.sync()
+        for k in range(18, 23):
+            assert traj.slot(k) == k % 5
+            for name in names:
+                _assert_slot(traj, name, k % 5, want[k][name], ("step", k))
+        assert traj.recorded == 23
+        traj.close()
+
+        # three replays into rings that hold a sentinel: slots 3 and 4 keep it
+        traj = sim.record(names, 5)
+        for name in names:
+            traj[name].view(torch.uint8).fill_(SENTINEL)
+        torch.cuda.synchronize()
+        sim.step_async(3)
+        want = {}
+        for k in range(3):
+            twin.step(1)
+            want[k] = _read_all(twin, names)
+        sim.sync()
+        assert traj.recorded == 3
+        for name in names:
+            for k in range(3):
+                _assert_slot(traj, name, k, want[k][name], ("short", k))
+            for slot in (3, 4):
+                assert (_slot_bytes(traj, name, slot) == SENTINEL).all(), (name, slot)
+        traj.close()
+
+
+# ---- 2. with the input ring: both kinds see the same k -----------------------------
+def test_slot_k_holds_what_the_step_that_consumed_action_k_produced(built):
+    torch = _torch()
+    with _escape() as sim, _escape() as twin:
+        names = sim.tensor_names
+        actions = [_action(W_ODD, t) for t in range(5)]
+        action_ring = torch.from_numpy(np.stack(actions)).cuda()
+        torch.cuda.synchronize()
+        sim.set_input_ring("action", action_ring.data_ptr(), 5)
+        traj = sim.record(names, 23)
+        sim.step_async(23)
+        want = []
+        for k in range(23):
+            twin.write_tensor("action", actions[k % 5])
+            twin.step(1)
+            want.append(_read_all(twin, names))
+        sim.sync()
+        for k in range(23):
+            for name in names:
+                _assert_slot(traj, name, k, want[k][name], ("input ring", k))
+        assert traj.recorded == 23
+        traj.close()
+        sim.set_input_ring("action", 0, 5)
+
+
+# ---- 3. widths and edges, at the ABI -----------------------------------------------
+OFFSETS = (0, 1, 4, 16)
+SIZES = (1, 3, 4, 15, 16, 17, 16384, 16384 + 5, 3 * 16384 + 20)
+GUARD = 64
+
+
+def _run_pairs(rt, sim, twin, twin_bytes, lidar, triples):
+    """Sets one ring of 3 slots per (src offset, bytes, what) triple, replays 4
+    times next to the twin, checks every slot and the guards, removes the rings."""
+    torch = _torch()
+    assert len(triples) <= 16
+    rings = []
+    for off, size, _ in triples:
+        ring = torch.full((GUARD + 3 * size + GUARD,), SENTINEL, dtype=torch.uint8,
+                          device="cuda")
+        rings.append(ring)
+    torch.cuda.synchronize()
+    for (off, size, what), ring in zip(triples, rings):
+        rc = _set_ring(rt, sim, lidar + off, ring.data_ptr() + GUARD, size, 3)
+        assert rc == 0, (what, rt.mwhip_last_error())
+    sim.step_async(4)
+    want = []
+    for k in range(4):
+        twin.step(1)
+        torch.cuda.synchronize()
+        want.append(twin_bytes.cpu().numpy())
+    sim.sync()
+    for (off, size, what), ring in zip(triples, rings):
+        got = ring.cpu().numpy()
+        assert (got[:GUARD] == SENTINEL).all(), ("guard before", what)
+        assert (got[GUARD + 3 * size:] == SENTINEL).all(), ("guard after", what)
+        # 4 replays into 3 slots: slot 0 was rewritten by the fourth
+        for slot, k in ((0, 3), (1, 1), (2, 2)):
+            part = got[GUARD + slot * size:GUARD + (slot + 1) * size]
+            assert np.array_equal(part, want[k][off:off + size]), (what, slot)
+        assert _recorded(rt, sim, lidar + off) == 4, what
+    for off, size, what in triples:
+        assert _set_ring(rt, sim, lidar + off, 0, 0, 0) == 0, what
+
+
+def test_widths_and_edges_at_the_abi(built):
+    """Every (source offset, slot bytes) pair of {0, 1, 4, 16} x {1, 3, 4, 15,
+    16, 17, 16 Ki, 16 Ki + 5, 48 Ki + 20}, with `src` that far into the lidar
+    column of escape_room at 64 worlds (the column's memory is mapped for 64
+    rows per world, 983 040 bytes; the tensor is its first 30 720: what lies
+    behind it is zero on both simulators) and rings with 64 guard bytes on both
+    sides.
+
+    A ring is named by (src, when), so two pairs that share an offset cannot be
+    set at the same time.  Hence two passes: the pairs exactly as listed, the
+    four offsets of one size at a time; then sixteen rings at a time, the
+    source of size number j moved on by 32 * j bytes -- which keeps each
+    offset's alignment class (32-, 1-, 4- and 16-byte) -- so that a full table
+    of rings of very different sizes shares one grid."""
+    rt = runtime_lib()
+    with _escape(64) as sim, _escape(64) as twin:
+        for s in (sim, twin):
+            s.write_tensor("action", _action(64, 0))
+        lidar = sim.tensor_ptr("lidar")
+        reach = max(OFFSETS) + 32 * len(SIZES) + max(SIZES)
+        assert reach <= 64 * 64 * 240
+        twin_bytes = _device_bytes(twin.tensor_ptr("lidar"), reach)
+
+        for size in SIZES:
+            _run_pairs(rt, sim, twin, twin_bytes, lidar,
+                       [(off, size, (off, size)) for off in OFFSETS])
+
+        moved = [(off + 32 * j, size, (off, size, "moved"))
+                 for j, size in enumerate(SIZES) for off in OFFSETS]
+        assert len(moved) == 36
+        for first in range(0, len(moved), 16):
+            _run_pairs(rt, sim, twin, twin_bytes, lidar, moved[first:first + 16])
+
+
+def test_slots_of_several_chunks_over_live_data(built):
+    """The three sizes of a chunk and more once again, at 256 worlds: the lidar
+    tensor is 122 880 bytes there, so live, varying data lies under every byte
+    copied -- upper chunks and odd tail included -- and a chunk taken from the
+    wrong source offset shows.  (At the 64 worlds of the test above the tensor
+    ends at 30 720 bytes: what those sizes read past it is zero on both
+    simulators, and only a copy that did not happen would show there.)"""
+    rt = runtime_lib()
+    sizes = [size for size in SIZES if size >= 16384]
+    with _escape(256) as sim, _escape(256) as twin:
+        for s in (sim, twin):
+            s.write_tensor("action", _action(256, 0))
+        lidar = sim.tensor_ptr("lidar")
+        tensor_bytes = 256 * 2 * 30 * 2 * 4
+        assert sim.read_tensor("lidar").nbytes == tensor_bytes
+        reach = max(OFFSETS) + 32 * len(sizes) + max(sizes)
+        assert reach <= tensor_bytes
+        twin_bytes = _device_bytes(twin.tensor_ptr("lidar"), reach)
+        _run_pairs(rt, sim, twin, twin_bytes, lidar,
+                   [(off + 32 * j, size, (off, size, "live"))
+                    for j, size in enumerate(sizes) for off in OFFSETS])
+        # the data is live to the end and differs from chunk to chunk
+        now = twin_bytes.cpu().numpy()
+        chunks = [now[first:first + 16384] for first in range(0, reach - 16384, 16384)]
+        assert all(chunk.any() for chunk in chunks)
+        assert not any(np.array_equal(chunks[0], chunk) for chunk in chunks[1:])
+
+
+# ---- 4. one launch ------------------------------------------------------------------
+def _ring_kernels(sim):
+    return [k for k in sim.profile(reps=1) if "ring.out" in k["name"]]
+
+
+def test_all_rings_of_a_kind_share_one_launch(built):
+    torch = _torch()
+    rt = runtime_lib()
+    with _escape() as sim:
+        assert _ring_kernels(sim) == []
+
+        traj = sim.record(["reward", "lidar"], 2)
+        sizes = [W_ODD * 2 * 4, W_ODD * 2 * 30 * 2 * 4]
+        kernels = _ring_kernels(sim)
+        assert [k["name"] for k in kernels] == ["ring:ring.out"]
+        assert kernels[0]["algo_bytes"] == 2 * sum(sizes)
+        traj.close()
+        assert _ring_kernels(sim) == []
+
+        # sixteen: sources 64 bytes apart inside the lidar tensor, 1 .. 16 x 37 bytes
+        lidar = sim.tensor_ptr("lidar")
+        sizes = [37 * (i + 1) for i in range(16)]
+        rings = [torch.zeros(2 * size, dtype=torch.uint8, device="cuda") for size in sizes]
+        torch.cuda.synchronize()
+        for i, (size, ring) in enumerate(zip(sizes, rings)):
+            assert _set_ring(rt, sim, lidar + 64 * i, ring.data_ptr(), size, 2) == 0
+        kernels = _ring_kernels(sim)
+        assert [k["name"] for k in kernels] == ["ring:ring.out"]
+        assert kernels[0]["algo_bytes"] == 2 * sum(sizes)
+        # (the profile ran the launch once: it recorded like a replay)
+        want = sim.read_tensor("lidar").view(np.uint8).reshape(-1)
+        for i, (size, ring) in enumerate(zip(sizes, rings)):
+            assert np.array_equal(ring[:size].cpu().numpy(), want[64 * i:64 * i + size]), i
+        for i in range(16):
+            assert _set_ring(rt, sim, lidar + 64 * i, 0, 0, 0) == 0
+        assert _ring_kernels(sim) == []
+
+
+# ---- 5. render rings ------------------------------------------------------------------
+def test_render_rings_follow_render_replays_only(built):
+    flags = 9 | (16 << 16)
+    with _escape(3, flags, "escape_room_render") as sim, \
+            _escape(3, flags, "escape_room_render") as twin:
+        for s in (sim, twin):
+            s.write_tensor("action", _action(3, 0, grab=True))
+        images = sim.record(["rgb", "depth"], 3, on_render=True)
+        rewards = sim.record(["reward"], 3)
+        want_images, want_rewards = [], []
+        for _ in range(4):
+            for s in (sim, twin):
+                s.step(1)
+                s.render()
+            want_rewards.append(_read_all(twin, ["reward"]))
+            want_images.append(_read_all(twin, ["rgb", "depth"]))
+        for _ in range(2):
+            for s in (sim, twin):
+                s.step(1)
+            want_rewards.append(_read_all(twin, ["reward"]))
+        sim.sync()
+        assert images.recorded == 4
+        assert rewards.recorded == 6
+        # 4 renders into 3 slots: slot 0 holds the fourth
+        for slot, k in ((0, 3), (1, 1), (2, 2)):
+            for name in ("rgb", "depth"):
+                _assert_slot(images, name, slot, want_images[k][name], ("render", k))
+        for k in (3, 4, 5):
+            _assert_slot(rewards, "reward", k % 3, want_rewards[k]["reward"], ("step", k))
+        # the passes differ (else slot 0 could not tell the first from the fourth)
+        assert not np.array_equal(want_images[0]["depth"], want_images[3]["depth"])
+        images.close()
+        rewards.close()
+
+
+# ---- 6. removal, replacement, refusals ------------------------------------------------
+def test_removal_replacement_and_refusals(built):
+    torch = _torch()
+    rt = runtime_lib()
+    with _escape() as sim, _escape() as twin:
+        for s in (sim, twin):
+            s.write_tensor("action", _action(W_ODD, 0))
+        src = sim.tensor_ptr("self_obs")
+        size = W_ODD * 2 * 8 * 4
+        ring = torch.full((4, size), SENTINEL, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+
+        def twin_steps(n):
+            out = []
+            for _ in range(n):
+                twin.step(1)
+                out.append(_bytes(twin.read_tensor("self_obs")))
+            return out
+
+        assert _set_ring(rt, sim, src, ring.data_ptr(), size, 4) == 0
+        sim.step(2)
+        want = twin_steps(2)
+        got = ring.cpu().numpy()
+        assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+        assert (got[2:] == SENTINEL).all()
+
+        # replacing restarts at slot 0 (and at a count of 0)
+        assert _set_ring(rt, sim, src, ring.data_ptr(), size, 4) == 0
+        assert _recorded(rt, sim, src) == 0
+        sim.step(1)
+        want = twin_steps(1)
+        got = ring.cpu().numpy()
+        assert np.array_equal(got[0], want[0])
+        assert (got[2:] == SENTINEL).all()
+        assert _recorded(rt, sim, src) == 1
+
+        # refusals: each says why, changes nothing, and the next step records
+        lidar = sim.tensor_ptr("lidar")
+        others = [torch.zeros(8, dtype=torch.uint8, device="cuda") for _ in range(15)]
+        torch.cuda.synchronize()
+        for i, other in enumerate(others):
+            assert _set_ring(rt, sim, lidar + 8 * i, other.data_ptr(), 8, 1) == 0
+        spare = torch.full((16,), SENTINEL, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        refused = [
+            (0, spare.data_ptr(), 8, 1, RING_ON_STEP),                  # null src
+            (lidar + 512, spare.data_ptr(), 8, 0, RING_ON_STEP),        # zero slots
+            (lidar + 512, spare.data_ptr(), 0, 1, RING_ON_STEP),        # zero bytes
+            (lidar + 512, spare.data_ptr(), 8, 1, RING_ON_STEP),        # a seventeenth
+            (lidar + 512, spare.data_ptr(), 8, 1, RING_ON_RENDER),      # ... of either kind
+            (src, spare.data_ptr(), 8, 1, 2),                           # when = 2
+        ]
+        for args in refused:
+            rc = rt.mwhip_set_output_ring(sim.hip_exec(), args[0] or None, *args[1:])
+            assert rc != 0, args
+            assert rt.mwhip_last_error(), args
+        out = C.c_uint64(0)
+        assert rt.mwhip_output_ring_recorded(sim.hip_exec(), lidar + 512, RING_ON_STEP,
+                                             C.byref(out)) != 0
+        assert rt.mwhip_last_error()
+        sim.step(1)
+        want = twin_steps(1)
+        got = ring.cpu().numpy()
+        assert np.array_equal(got[1], want[0])
+        assert _recorded(rt, sim, src) == 2
+        lidar_now = sim.read_tensor("lidar").view(np.uint8).reshape(-1)
+        for i, other in enumerate(others):
+            assert np.array_equal(other.cpu().numpy(), lidar_now[8 * i:8 * i + 8]), i
+            assert _recorded(rt, sim, lidar + 8 * i) == 1
+        assert (spare.cpu().numpy() == SENTINEL).all()
+
+        # after removal three more steps leave the buffer as it is
+        assert _set_ring(rt, sim, src, 0, 0, 0) == 0
+        before = ring.cpu().numpy()
+        sim.step(3)
+        twin_steps(3)
+        assert np.array_equal(ring.cpu().numpy(), before)
+        assert rt.mwhip_output_ring_recorded(sim.hip_exec(), src, RING_ON_STEP,
+                                             C.byref(out)) != 0
+        for i in range(15):
+            assert _set_ring(rt, sim, lidar + 8 * i, 0, 0, 0) == 0
+
+
+def test_a_closed_trajectory_is_forgotten_and_a_recorded_name_is_refused(built):
+    """The simulator keeps open trajectories only (a trainer that records once
+    per rollout must not pile up ring tensors), and a tensor that an open
+    trajectory of the same kind records is refused rather than taken over."""
+    with _escape() as sim, _escape() as twin:
+        for s in (sim, twin):
+            s.write_tensor("action", _action(W_ODD, 0))
+        for _ in range(3):
+            sim.record(["reward", "done"], 2).close()
+        assert sim._trajectories == []
+
+        first = sim.record(["reward"], 4)
+        with pytest.raises(ValueError, match="reward"):
+            sim.record(["done", "reward"], 2)
+        with pytest.raises(ValueError, match="done"):
+            sim.record(["done", "done"], 2)
+        assert sim._trajectories == [first]
+        # the refused calls set nothing and did not disturb the open one
+        sim.step(2)
+        want = []
+        for _ in range(2):
+            twin.step(1)
+            want.append(_bytes(twin.read_tensor("reward")))
+        assert first.recorded == 2
+        for k in range(2):
+            _assert_slot(first, "reward", k, want[k], ("kept", k))
+        # the other kind is another ring; a closed name is free again
+        with _escape(3, 9 | (16 << 16), "escape_room_render") as render_sim:
+            on_step = render_sim.record(["reward"], 2)
+            on_render = render_sim.record(["reward"], 2, on_render=True)
+            on_step.close()
+            render_sim.record(["reward"], 2).close()
+            on_render.close()
+            assert render_sim._trajectories == []
+        first.close()
+        assert sim._trajectories == []
+
+
+# ---- 7. across a rebuild ----------------------------------------------------------------
+def test_rings_keep_their_position_across_table_growth(built, monkeypatch):
+    """sort_stress ramping up with tables mapped for a quarter of what the
+    simulator declared (the set-up of test_tables_grow_between_replays): growth
+    rebuilds the launch graphs between replays."""
+    monkeypatch.setenv("MADRONA_MWHIP_INITIAL_CAPACITY_DIV", "4")
+    rt = runtime_lib()
+    rt.mwhip_num_table_growths.restype = C.c_uint32
+    rt.mwhip_num_table_growths.argtypes = [C.c_void_p]
+    W = 300
+    with Simulator(hip_lib_path("sort_stress"), W, seed=7, flags=2) as sim, \
+            Simulator(hip_lib_path("sort_stress"), W, seed=7, flags=2) as twin:
+        grown_at_start = rt.mwhip_num_table_growths(sim.hip_exec())
+        traj = sim.record(["churn"], 64)
+        want = []
+        while len(want) < 60:
+            sim.step(1)
+            twin.step(1)
+            want.append(_bytes(twin.read_tensor("churn")))
+            if rt.mwhip_num_table_growths(sim.hip_exec()) > grown_at_start and \
+                    len(want) >= 8:
+                break
+        assert rt.mwhip_num_table_growths(sim.hip_exec()) > grown_at_start, "nothing grew"
+        for k, value in enumerate(want):
+            _assert_slot(traj, "churn", k, value, ("growth", k))
+        assert traj.recorded == len(want)
+        assert any(not np.array_equal(want[0], value) for value in want[1:])
+        traj.close()
+
+
+# ---- 8. across a snapshot -----------------------------------------------------------------
+def test_a_restore_does_not_rewind_the_rings(built):
+    names = ["self_obs", "reward", "done", "steps_remaining", "lidar"]
+    with _escape() as sim:
+        sim.write_tensor("action", _action(W_ODD, 0))
+        sim.step(3)
+        traj = sim.record(names, 8)
+        snap = sim.snapshot()
+        snap.save()
+        sim.step(4)
+        snap.restore()
+        sim.step(4)
+        assert traj.recorded == 8
+        for name in names:
+            got = traj[name].cpu().numpy()
+            assert np.array_equal(_bytes(got[0:4]), _bytes(got[4:8])), name
+        # (the four steps differ from each other: the halves are not equal by default)
+        steps_remaining = traj["steps_remaining"].cpu().numpy()
+        assert not np.array_equal(steps_remaining[0], steps_remaining[1])
+        snap.close()
+        traj.close()
+
+
+# ---- 9. packed graphs record too ------------------------------------------------------------
+def test_replays_of_a_packed_graph_record_too(built):
+    torch = _torch()
+    names = ["self_obs", "lidar", "reward"]
+    with _escape() as sim, _escape() as twin:
+        for s in (sim, twin):
+            s.write_tensor("action", _action(W_ODD, 0))
+        words = sum(int(np.prod(sim.tensor_meta(name)[2][1:])) for name in names)
+        packed = torch.zeros((W_ODD, words), dtype=torch.int32, device="cuda")
+        again = torch.zeros_like(packed)
+        torch.cuda.synchronize()
+        graph = sim.packed_step_graph(names, packed.data_ptr())
+        traj = sim.record(names, 4)
+        sim.step_async(1)
+        sim.step_async(3, graph=graph)
+        want = []
+        for _ in range(4):
+            twin.step(1)
+            want.append(_read_all(twin, names))
+        sim.sync()
+        assert traj.recorded == 4
+        for k in range(4):
+            for name in names:
+                _assert_slot(traj, name, k, want[k][name], ("packed", k))
+        # the pack node still writes the record the all-gather sends
+        sim.pack_rows_async(names, again.data_ptr())
+        sim.sync()
+        assert torch.equal(packed, again)
+        assert packed.any()
+        traj.close()

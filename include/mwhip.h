@@ -201,6 +201,26 @@ void *mwhip_get_module_data(mwhip_exec *exec, uint32_t slot);
 uint32_t mwhip_archetype_capacity(mwhip_exec *exec, uint32_t archetype_id);
 /* how many times a table has been grown so far (tests / monitoring) */
 uint32_t mwhip_num_table_growths(mwhip_exec *exec);
+/* Cumulative counters of one table's sort node (device-resident, read after
+ * waiting for the executor's stream; tests / monitoring).  A compaction run
+ * that moves no surviving row of the sorted prefix patches the few new rows in
+ * place ("stay mode", MADRONA_MWHIP_SORT_STAY=0 turns it off) instead of
+ * gathering every column into its twin: stay_runs counts those runs, and
+ * rows_copied the rows the chains' gather kernel copied per column (the moved
+ * rows of a stay run, every row of the sorted table otherwise). */
+typedef struct mwhip_sort_counters {
+    uint64_t runs;          /* chain or single-launch runs that sorted */
+    uint64_t stay_runs;
+    uint64_t rows_copied;
+    uint64_t rows_in;       /* rows the sorted tables held before / after */
+    uint64_t rows_out;
+    uint64_t tail_rows;     /* compaction chain: rows behind the sorted prefix */
+} mwhip_sort_counters;
+/* 0: *out filled; 1: the table has never been part of a sort node (*out
+ * zeroed); -1: no such archetype id (ids are dense below the first -1);
+ * -2: the device could not be read */
+int mwhip_sort_stats(mwhip_exec *exec, uint32_t archetype_id,
+                     mwhip_sort_counters *out);
 /* the persistent region's current bump offset in bytes (device rawAlloc /
  * HostAllocator: mwhip::persistAlloc, 16-B granules): right after creation,
  * what the last constructor pass took; device code that allocates there while

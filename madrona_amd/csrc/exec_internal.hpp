@@ -175,7 +175,7 @@ struct ArchetypeRec {
     std::vector<void *> alt;
     // growable archetypes: the ranges behind primary / alt / sort buffers
     std::vector<VmRange *> primaryVm, altVm;
-    VmRange *sortVm[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
+    VmRange *sortVm[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
     std::vector<uint32_t> colBytes;
     std::vector<uint32_t> colFlags;
     std::vector<uint32_t> colComponent;
@@ -189,6 +189,8 @@ struct ArchetypeRec {
     int32_t *tileCounts = nullptr;      // compaction chain, per prefix tile
     int32_t *tileTailStart = nullptr;
     int32_t *tailLand = nullptr;        // [capacity] where each sorted tail row lands
+    int32_t *moveDest = nullptr;        // [capacity] where each tail row goes (stay mode)
+    void **sortColPtrs = nullptr;       // [2 * columns] buffers when a chain started
 };
 
 struct QueryRec {

@@ -1252,6 +1252,32 @@ extern "C" uint32_t mwhip_num_table_growths(mwhip_exec *exec)
     return exec->numGrowths;
 }
 
+extern "C" int mwhip_sort_stats(mwhip_exec *exec, uint32_t archetype_id,
+                                mwhip_sort_counters *out)
+{
+    *out = mwhip_sort_counters {};
+    if (archetype_id >= exec->archetypes.size()) {
+        return -1;
+    }
+    const ArchetypeRec &arch = exec->archetypes[archetype_id];
+    if (!arch.registered || arch.sortState == nullptr) {
+        return 1;
+    }
+    SortState state;
+    if (hipStreamSynchronize(exec->stream) != hipSuccess ||
+        hipMemcpy(&state, arch.sortState, sizeof(state),
+                  hipMemcpyDeviceToHost) != hipSuccess) {
+        return -2;
+    }
+    out->runs = state.statRuns;
+    out->stay_runs = state.statStayRuns;
+    out->rows_copied = state.statRowsCopied;
+    out->rows_in = state.statRowsIn;
+    out->rows_out = state.statRowsOut;
+    out->tail_rows = state.statTailRows;
+    return 0;
+}
+
 extern "C" uint64_t mwhip_persist_bytes_used(mwhip_exec *exec)
 {
     // the region's bump offset: every constructor pass starts it over, and

@@ -39,6 +39,26 @@ namespace mwhip {
 //               the sorted keys of its surviving rows and of the tail rows
 //               that land in it
 //   gather      as above
+// Stay mode of the compaction chain (SortSite::stayAllowed): most runs move no
+// surviving row of the prefix -- a world that resets destroys its rows and
+// appends as many, which land in the holes -- and copying every column from row
+// i to row i of the twin is then a pass over memory for nothing.
+//   prepare     workgroup 0 also zeroes stayMoved (not the gather's clean-up:
+//               every workgroup of the gather and of finalize reads it)
+//   scatter     workgroup 0 publishes the row counts but does NOT swap the
+//               column pointers: it records them (SortSite::colPtrs).  The tiles
+//               count the surviving prefix rows whose destination is not their
+//               position (stayMoved, one atomic per wavefront that has any) and
+//               record where every tail row goes (SortSite::moveDest)
+//   gather      every workgroup derives the same answer from state the kernel
+//               before it left: stay = stayMoved == 0 && rowsOut <= prefixRows.
+//               Then every moved row comes from the tail and goes to a destroyed
+//               slot of the prefix, no destination is another move's source, and
+//               the moved rows are patched inside the current buffers, pinned
+//               columns included: O(tail) per column, pointers untouched.
+//               Otherwise the full gather runs from the recorded pointers, never
+//               from the header, while one workgroup swaps the header's.
+//   finalize    copies nothing back for a site that stayed
 struct SortState {
     uint32_t bins[4 * 256];         // digit histograms of up to 4 passes
     uint32_t numValid;              // rows whose key != 0xFFFFFFFF
@@ -59,7 +79,10 @@ struct SortState {
     unsigned long long statTailRows;// cumulative rows behind the prefix
     uint32_t landsBlocked;          // runs that still take the sorted-tail path after a
                                     // scatter tile owned more tail rows than it orders in LDS
-    uint32_t reserved_;
+    // stay mode
+    uint32_t stayMoved;             // this run: surviving prefix rows that change position
+    unsigned long long statStayRuns;    // cumulative: compaction runs that stayed in place
+    unsigned long long statRowsCopied;  // cumulative: rows the gather copied per column
 };
 
 struct SortSite {
@@ -82,6 +105,11 @@ struct SortSite {
     int32_t *tileTailStart;         // [numTiles + 1]
     int32_t *tailLand;              // [rows] prefix position each tail row lands at (sorted
                                     // tail order, or raw tail order: SortState::tailByLands)
+    // stay mode (SortState): decided per run on the device when allowed
+    int32_t *moveDest;              // [rows] sorted position of each tail row, same order
+    void **colPtrs;                 // [2 * columns] { buffer, twin } when the chain started
+    uint32_t stayAllowed;           // compaction chain and MADRONA_MWHIP_SORT_STAY != 0
+    uint32_t pad_;
 };
 
 // pseudo-column of a world-sort site: rebuild worldOffsets / worldCounts

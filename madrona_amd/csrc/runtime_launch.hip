@@ -38,10 +38,10 @@ static int ensureSortScratch(mwhip_exec *exec, ArchetypeRec &arch)
     int rc = devAllocT(exec, &arch.sortState, 1);
     if (rc != 0) return rc;
     if (arch.reservedCapacity > arch.capacity) {
-        void **bufs[5] = { (void **)&arch.keysA, (void **)&arch.keysB,
+        void **bufs[6] = { (void **)&arch.keysA, (void **)&arch.keysB,
                            (void **)&arch.idxA, (void **)&arch.idxB,
-                           (void **)&arch.tailLand };
-        for (int i = 0; i < 5; i++) {
+                           (void **)&arch.tailLand, (void **)&arch.moveDest };
+        for (int i = 0; i < 6; i++) {
             rc = vmAlloc(exec, bufs[i], &arch.sortVm[i],
                          (size_t)arch.reservedCapacity * 4,
                          (size_t)arch.capacity * 4, false);
@@ -58,7 +58,11 @@ static int ensureSortScratch(mwhip_exec *exec, ArchetypeRec &arch)
         if (rc != 0) return rc;
         rc = devAllocT(exec, &arch.tailLand, arch.capacity, false);
         if (rc != 0) return rc;
+        rc = devAllocT(exec, &arch.moveDest, arch.capacity, false);
+        if (rc != 0) return rc;
     }
+    rc = devAllocT(exec, &arch.sortColPtrs, 2 * (size_t)std::max(arch.numColumns, 1u));
+    if (rc != 0) return rc;
     // (look-back slots for every tile the table can ever have)
     size_t tiles =
         (arch.reservedCapacity + sortTileSize() - 1) / sortTileSize();
@@ -92,6 +96,9 @@ static int makeSortBatch(mwhip_exec *exec,
     std::vector<SortSite> sites;
     std::vector<GatherColumn> cols;
     bool all_small = envU32("MADRONA_MWHIP_SORT_SMALL", 1) != 0;
+    // MADRONA_MWHIP_SORT_STAY=0: the compaction chain always takes the full
+    // gather (same-box A/B, tests)
+    const bool stay = compact && envU32("MADRONA_MWHIP_SORT_STAY", 1) != 0;
 
     for (auto [archetype_id, component_id] : specs) {
         if (archetype_id >= exec->archetypes.size() ||
@@ -139,6 +146,9 @@ static int makeSortBatch(mwhip_exec *exec,
         site.tileCounts = arch.tileCounts;
         site.tileTailStart = arch.tileTailStart;
         site.tailLand = arch.tailLand;
+        site.moveDest = arch.moveDest;
+        site.colPtrs = arch.sortColPtrs;
+        site.stayAllowed = stay ? 1u : 0u;
         sites.push_back(site);
 
         out->maxCapacity = std::max(out->maxCapacity, arch.capacity);

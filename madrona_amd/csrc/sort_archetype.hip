@@ -48,7 +48,29 @@
 //                    survivors before the end of w's old range + j.  No
 //                    inter-workgroup dependency (the tile counts come from the
 //                    kernel before).  Workgroup 0 publishes.
-//   sortGather / sortFinalize  as above
+//   sortGather / sortFinalize  as above, unless the run STAYS:
+//
+//   Stay mode (decided on the device, per site and per run; off with
+//   MADRONA_MWHIP_SORT_STAY=0).  A world that resets destroys its rows in
+//   place and appends as many: the new rows land in the holes and every
+//   surviving row keeps its position.  Gathering such a table out of place
+//   copies every column from row i to row i.  The scatter tiles therefore
+//   count the surviving prefix rows whose destination is not their position
+//   (SortState::stayMoved) and record where every tail row goes
+//   (SortSite::moveDest), and the scatter's workgroup 0 publishes the row
+//   counts but only RECORDS the column pointers (SortSite::colPtrs) instead
+//   of swapping them.  With (a) stayMoved == 0 and (b) n_out <= prefix rows,
+//   every moved row comes from the tail and goes to a destroyed slot of the
+//   prefix; no destination is another move's source, so the gather patches
+//   the moved rows inside the current buffers in any order -- O(tail) per
+//   column, exported columns included, pointers as they were -- and
+//   sortFinalize copies nothing back.  If (a) or (b) fails the full gather
+//   runs as above from the recorded pointers while one of its workgroups
+//   swaps the header's: no workgroup reads a pointer that is being swapped,
+//   nothing waits for another workgroup, no counter of arrivals.  (b) matters:
+//   with n_out > prefix a tail row can land on a row of the tail that is
+//   still a source.  The radix chain, sortSmall, key sorts and a cold start
+//   (no prefix) always take the full gather.
 //
 // (3) sortSmall -- tables that hold few rows: the whole node in one launch.
 //
@@ -214,11 +236,8 @@ sortHistogram(EcsState *S, const SortSite *sites)
 // gather moves the rows from the old buffers (now columnsAlt) into the current
 // ones.  Pinned (exported) columns keep their address: they are gathered into
 // their twin and copied back by sortFinalize.
-__device__ inline void publishSite(EcsState *S, const SortSite &site,
-                                   TableHdr &tbl, int32_t n)
+__device__ inline void swapColumns(EcsState *S, const SortSite &site, TableHdr &tbl)
 {
-    SortState *state = site.state;
-    const int32_t n_out = site.worldSort ? (int32_t)state->numValid : n;
     for (int32_t c = threadIdx.x; c < tbl.numColumns; c += blockDim.x) {
         if ((tbl.columnFlags[c] & kColumnPinned) == 0u) {
             void *old_buf = tbl.columns[c];
@@ -227,6 +246,24 @@ __device__ inline void publishSite(EcsState *S, const SortSite &site,
             tbl.columnsAlt[c] = old_buf;
             S->colPtr[site.archetype * S->numComponentSlots +
                       tbl.columnComponent[c]] = new_buf;
+        }
+    }
+}
+
+// swap = false (compaction chain with stay mode allowed): whether the rows move
+// to the twins at all is known only when the scatter's last tile is done.  The
+// buffers are recorded instead, and the gather swaps -- or does not.
+__device__ inline void publishSite(EcsState *S, const SortSite &site,
+                                   TableHdr &tbl, int32_t n, bool swap = true)
+{
+    SortState *state = site.state;
+    const int32_t n_out = site.worldSort ? (int32_t)state->numValid : n;
+    if (swap) {
+        swapColumns(S, site, tbl);
+    } else {
+        for (int32_t c = threadIdx.x; c < tbl.numColumns; c += blockDim.x) {
+            site.colPtrs[2 * c] = tbl.columns[c];
+            site.colPtrs[2 * c + 1] = tbl.columnsAlt[c];
         }
     }
     if (threadIdx.x == 0) {
@@ -244,6 +281,33 @@ __device__ inline void publishSite(EcsState *S, const SortSite &site,
         // are stale until then (reference sort_archetype.cpp:1001-1007).
         tbl.needsSort = site.worldSort ? 0u : 1u;
         tbl.sortedRows = site.worldSort ? n_out : 0;
+    }
+}
+
+// Stay mode (runtime_internal.hpp, SortState): no surviving row of the sorted
+// prefix changes position and the sorted table fits in the prefix.  The same
+// answer in every workgroup of the gather and of finalize: the scatter kernel
+// wrote all three values, the next prepare is the first to change one.
+__device__ inline bool siteStays(const SortSite &site, const SortState *state)
+{
+    return site.stayAllowed != 0u && state->stayMoved == 0u &&
+        state->rowsOut <= state->prefixRows;
+}
+
+// Surviving prefix rows of a scatter tile whose destination is not their
+// position: one atomic per wavefront that has any (none in a balanced step).
+// Called by whole wavefronts.
+__device__ inline void noteMovedRows(SortState *state, uint32_t moved)
+{
+    if (ballot64(moved != 0u) == 0ull) {
+        return;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        moved += __shfl_down(moved, d, 64);
+    }
+    if (laneId() == 0) {
+        atomicAdd(&state->stayMoved, moved);
     }
 }
 
@@ -684,7 +748,12 @@ __device__ inline void gatherColumn(EcsState *S, const SortSite &site,
                                     int32_t tid, int32_t stride,
                                     const int32_t *perm_rows = nullptr,
                                     const uint32_t *sorted_keys = nullptr,
-                                    bool published = true);
+                                    bool published = true,
+                                    void *const *recorded = nullptr);
+
+__device__ inline void patchColumn(EcsState *S, const SortSite &site,
+                                   const SortState *state, const GatherColumn &gc,
+                                   int32_t tid, int32_t stride);
 
 // Wide: some column of the batch moves in 16-byte destination chunks
 // (MADRONA_MWHIP_GATHER_WIDE=1).  The word-by-word kernel is a stream of
@@ -718,13 +787,22 @@ sortGather(EcsState *S, const SortSite *sites, const GatherColumn *columns,
         return;
     }
     const int32_t n_out = state->rowsOut;
+    // compaction chain with stay mode allowed: the scatter did not swap the
+    // column pointers, it recorded them
+    void *const *recorded = site.stayAllowed != 0u ? site.colPtrs : nullptr;
+    const bool stay = siteStays(site, state);
 
     // (Row tiles -- a workgroup per 1024 rows of a site moving them in EVERY
     // column with the permutation staged once in LDS -- were built and measured
     // in round 4: slower than contiguous rows per column slice, 291 against
     // 252 us at 65536 Escape-Room worlds on one box, and its three inlined
     // copies of the column routine cost the other modes 30 % as well.  Removed.)
-    if (slice.blocked != 0u && gc.column != kWorldRangesColumn) {
+    if (stay && gc.column != kWorldRangesColumn) {
+        // only the tail rows move, inside the current buffer
+        patchColumn(S, site, state, gc,
+                    (int32_t)(slice.slice * kSortThreads + threadIdx.x),
+                    (int32_t)(slice.numSlices * kSortThreads));
+    } else if (slice.blocked != 0u && gc.column != kWorldRangesColumn) {
         // a contiguous run of rows per workgroup (big tables: every workgroup
         // stays inside a few pages of every buffer it touches instead of
         // striding over all of them)
@@ -734,16 +812,27 @@ sortGather(EcsState *S, const SortSite *sites, const GatherColumn *columns,
         const int32_t row_end = row_begin + per < n_out ? row_begin + per : n_out;
         if (row_begin < row_end) {
             gatherColumn<Wide>(S, site, gc, tbl, row_begin, row_end,
-                               (int32_t)threadIdx.x, (int32_t)kSortThreads);
+                               (int32_t)threadIdx.x, (int32_t)kSortThreads,
+                               nullptr, nullptr, true, recorded);
         }
     } else {
         gatherColumn<Wide>(S, site, gc, tbl, 0, n_out,
                            (int32_t)(slice.slice * kSortThreads + threadIdx.x),
-                           (int32_t)(slice.numSlices * kSortThreads));
+                           (int32_t)(slice.numSlices * kSortThreads),
+                           nullptr, nullptr, true, recorded);
     }
 
     // (the passes are over: their histograms and counters are dead)
     if (gc.column == 0u && slice.slice == 0u) {
+        if (recorded != nullptr && !stay) {
+            // the full gather of a chain that left the swap to it: every
+            // workgroup works from the recorded pointers
+            swapColumns(S, site, tbl);
+        }
+        if (threadIdx.x == 0) {
+            state->statStayRuns += stay ? 1ull : 0ull;
+            state->statRowsCopied += (unsigned long long)(stay ? state->tailLive : n_out);
+        }
         cleanSortState(state);
         // the per-tile landing counters of the compaction chain start every
         // run at zero (whichever way the tail went this time)
@@ -763,7 +852,9 @@ sortGather(EcsState *S, const SortSite *sites, const GatherColumn *columns,
 // sorted_keys: ALL sorted keys if the caller has them closer than the key
 // buffer.  published = false: publishSite has not run yet, rows move from the
 // current buffers into the twins (no caller left since the multi-workgroup
-// small sort was removed in round 5).
+// small sort was removed in round 5).  recorded: { buffer, twin } of every
+// column when the chain started (SortSite::colPtrs): the header's pointers are
+// being swapped by another workgroup and are not read.
 template <bool Wide>
 __device__ inline void gatherColumn(EcsState *S, const SortSite &site,
                                     const GatherColumn &gc, TableHdr &tbl,
@@ -771,7 +862,7 @@ __device__ inline void gatherColumn(EcsState *S, const SortSite &site,
                                     int32_t tid, int32_t stride,
                                     const int32_t *perm_rows,
                                     const uint32_t *sorted_keys,
-                                    bool published)
+                                    bool published, void *const *recorded)
 {
     const bool final_in_b = ((site.numPasses - 1) & 1) != 0;
     const int32_t *perm = perm_rows != nullptr ? perm_rows :
@@ -788,9 +879,16 @@ __device__ inline void gatherColumn(EcsState *S, const SortSite &site,
 
     // swapped already (publishSite): the rows still sit in what is now the
     // twin; pinned columns were not swapped and go the other way
-    const bool pinned = !published || (tbl.columnFlags[col] & kColumnPinned) != 0u;
-    const void *src = pinned ? tbl.columns[col] : tbl.columnsAlt[col];
-    void *dst = pinned ? tbl.columnsAlt[col] : tbl.columns[col];
+    const void *src;
+    void *dst;
+    if (recorded != nullptr) {
+        src = recorded[2 * col];
+        dst = recorded[2 * col + 1];
+    } else {
+        const bool pinned = !published || (tbl.columnFlags[col] & kColumnPinned) != 0u;
+        src = pinned ? tbl.columns[col] : tbl.columnsAlt[col];
+        dst = pinned ? tbl.columnsAlt[col] : tbl.columns[col];
+    }
 
     if (col == 0) {
         // Entity column: 8-byte handles; update the entity store's row
@@ -846,6 +944,85 @@ __device__ inline void gatherColumn(EcsState *S, const SortSite &site,
     }
 }
 
+// Stay mode: the moves of one column.  Move k is tail row k -- raw tail order
+// with the destroyed ones skipped, or the order compactSortTail left
+// (SortState::tailByLands) --, its destination the scatter recorded in
+// moveDest[k].  Sources are rows behind the prefix, destinations destroyed
+// slots of it: no ordering among the moves.
+template <typename WordT>
+__device__ inline void patchWords(WordT *buf, const SortSite &site,
+                                  const int32_t *__restrict__ perm, bool by_lands,
+                                  int32_t prefix, int32_t moves,
+                                  uint32_t words_per_row, unsigned long long inv_magic,
+                                  int32_t tid, int32_t stride)
+{
+    const long long total = (long long)moves * words_per_row;
+    for (long long j = tid; j < total; j += stride) {
+        const uint32_t k = words_per_row == 1u ? (uint32_t)j :
+            (uint32_t)__umul64hi((unsigned long long)j, inv_magic);
+        const uint32_t off = (uint32_t)(j - (long long)k * words_per_row);
+        if (by_lands && site.tailLand[k] < 0) continue;
+        const int32_t dst = site.moveDest[k];
+        const int32_t src = by_lands ? prefix + (int32_t)k : perm[dst];
+        buf[(long long)dst * words_per_row + off] =
+            buf[(long long)src * words_per_row + off];
+    }
+}
+
+__device__ inline void patchColumn(EcsState *S, const SortSite &site,
+                                   const SortState *state, const GatherColumn &gc,
+                                   int32_t tid, int32_t stride)
+{
+    const bool final_in_b = ((site.numPasses - 1) & 1) != 0;
+    const int32_t *perm = final_in_b ? site.idxB : site.idxA;
+    const bool by_lands = state->tailByLands != 0u;
+    const int32_t prefix = state->prefixRows;
+    const int32_t moves = by_lands ? state->rowsIn - prefix : state->tailLive;
+    const uint32_t col = gc.column;
+    void *buf = site.colPtrs[2 * col];
+
+    if (col == 0 || (col == 1 && site.worldSort)) {
+        const uint32_t *sorted = final_in_b ? site.keysB : site.keysA;
+        for (int32_t k = tid; k < moves; k += stride) {
+            if (by_lands && site.tailLand[k] < 0) continue;
+            const int32_t dst = site.moveDest[k];
+            if (col == 0) {
+                // Entity column: the handle, and the entity store's row
+                const int32_t src = by_lands ? prefix + k : perm[dst];
+                Entity *ents = (Entity *)buf;
+                const Entity e = ents[src];
+                ents[dst] = e;
+                if (e.id >= 0) {
+                    S->entities[e.id].loc.row = dst;
+                }
+            } else {
+                // WorldID column: from the sorted keys
+                ((int32_t *)buf)[dst] = (int32_t)sorted[dst];
+            }
+        }
+        return;
+    }
+
+    switch (gc.wordBytes) {
+    case 16:
+        patchWords<Word16>((Word16 *)buf, site, perm, by_lands, prefix, moves,
+                           gc.wordsPerRow, gc.invMagic, tid, stride);
+        break;
+    case 8:
+        patchWords<Word8>((Word8 *)buf, site, perm, by_lands, prefix, moves,
+                          gc.wordsPerRow, gc.invMagic, tid, stride);
+        break;
+    case 4:
+        patchWords<uint32_t>((uint32_t *)buf, site, perm, by_lands, prefix, moves,
+                             gc.wordsPerRow, gc.invMagic, tid, stride);
+        break;
+    default:
+        patchWords<uint8_t>((uint8_t *)buf, site, perm, by_lands, prefix, moves,
+                            gc.wordsPerRow, gc.invMagic, tid, stride);
+        break;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // kernel 4 (only for batches with exported columns): copy-back
 // ---------------------------------------------------------------------------
@@ -863,6 +1040,10 @@ sortFinalize(EcsState *S, const SortSite *sites, const MiscOp *trailing_ops,
     TableHdr &tbl = S->tables[site.archetype];
     SortState *state = site.state;
     if (state->active == 0u) {
+        return;
+    }
+    // (stay mode patched the pinned columns where they are: the twin is stale)
+    if (siteStays(site, state)) {
         return;
     }
 
@@ -1341,6 +1522,9 @@ sortCompactPrepare(EcsState *S, const SortSite *sites)
         state->keyColumn = keys;
         state->prefixRows = prefix;
         state->tailByLands = (active && by_lands) ? 1u : 0u;
+        // (counted by the scatter tiles, read by every workgroup of the gather
+        // and of finalize: cleared here, not by the gather's clean-up)
+        state->stayMoved = 0u;
     }
     if (!active) {
         return;
@@ -1575,6 +1759,7 @@ __device__ inline void compactScatterTile(const SortSite &site, CompactLDS<THREA
     uint32_t live = (uint32_t)excl;             // survivors of the tile before my rows
     uint32_t landed = (uint32_t)(excl >> 32);   // owned tail rows landing before them
 
+    uint32_t moved = 0;
 #pragma unroll
     for (int j = 0; j < ITEMS; j++) {
         landed += land[j];
@@ -1584,9 +1769,11 @@ __device__ inline void compactScatterTile(const SortSite &site, CompactLDS<THREA
                 tail_first + (int32_t)landed;
             out_rows[dest] = mine + j;
             out_keys[dest] = key[j];
+            moved += dest != mine + j ? 1u : 0u;
             live += 1u;
         }
     }
+    noteMovedRows(site.state, moved);
     if (tid == THREADS - 1) {
         lds.liveBefore[kCompactTile] = live;    // the tile's survivors
     }
@@ -1597,12 +1784,14 @@ __device__ inline void compactScatterTile(const SortSite &site, CompactLDS<THREA
             (int32_t)lds.liveBefore[my_at] + my_tail;
         out_rows[dest] = my_row;
         out_keys[dest] = my_world;
+        site.moveDest[my_tail] = dest;
     }
     for (int32_t j = my_tail + THREADS; j < tail_end; j += THREADS) {
         const int32_t dest = live_before_tile +
             (int32_t)lds.liveBefore[landing_at(j)] + j;
         out_rows[dest] = tail_rows[j];
         out_keys[dest] = tail_keys[j];
+        site.moveDest[j] = dest;
     }
     __syncthreads();
 }
@@ -1720,6 +1909,7 @@ __device__ inline void compactScatterTileLands(
         lds.scan);
     uint32_t live = (uint32_t)excl;
     uint32_t landed = (uint32_t)(excl >> 32);
+    uint32_t moved = 0;
 #pragma unroll
     for (int j = 0; j < ITEMS; j++) {
         landed += land[j];
@@ -1729,9 +1919,11 @@ __device__ inline void compactScatterTileLands(
                 (int32_t)landed;
             out_rows[dest] = mine + j;
             out_keys[dest] = key[j];
+            moved += dest != mine + j ? 1u : 0u;
             live += 1u;
         }
     }
+    noteMovedRows(state, moved);
     if (tid == THREADS - 1) {
         lds.liveBefore[kCompactTile] = live;
     }
@@ -1750,6 +1942,7 @@ __device__ inline void compactScatterTileLands(
                 (int32_t)lds.liveBefore[at_of(site.tailLand[j])] + before + r;
             out_rows[dest] = prefix + j;
             out_keys[dest] = (uint32_t)(k >> 32);
+            site.moveDest[j] = dest;
         }
     } else if (in_lds) {
         for (int32_t r = tid; r < own_total; r += THREADS) {
@@ -1759,6 +1952,7 @@ __device__ inline void compactScatterTileLands(
                 (int32_t)lds.liveBefore[at_of(site.tailLand[j])] + before + r;
             out_rows[dest] = prefix + j;
             out_keys[dest] = (uint32_t)(k >> 32);
+            site.moveDest[j] = dest;
         }
     } else {
         // more rows than the tile orders in LDS: rank each by counting the own
@@ -1780,6 +1974,7 @@ __device__ inline void compactScatterTileLands(
                 (int32_t)lds.liveBefore[at_of(land_j)] + before + rank;
             out_rows[dest] = prefix + j;
             out_keys[dest] = w;
+            site.moveDest[j] = dest;
         }
     }
     __syncthreads();
@@ -1840,7 +2035,7 @@ sortCompactScatter(EcsState *S, const SortSite *sites)
             state->numValid = (uint32_t)(survivors + tail_live);
         }
         __syncthreads();
-        publishSite(S, site, tbl, n);
+        publishSite(S, site, tbl, n, site.stayAllowed == 0u);
         __syncthreads();
     }
 

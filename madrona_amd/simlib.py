@@ -111,6 +111,12 @@ class KernelStat(C.Structure):
     ]
 
 
+class SortStats(C.Structure):
+    """mwhip_sort_counters (include/mwhip.h)"""
+    _fields_ = [(name, C.c_uint64) for name in
+                ("runs", "stay_runs", "rows_copied", "rows_in", "rows_out", "tail_rows")]
+
+
 def _torch_runtime_first() -> None:
     """PyTorch-ROCm bundles its own HIP / HSA runtime; a process that loads the
     system runtime first (through our libraries) and torch afterwards ends up
@@ -506,6 +512,28 @@ class Simulator:
 
     def hip_exec(self) -> int:
         return int(self.lib.sim_hip_exec(self.handle) or 0)
+
+    def sort_stats(self) -> Dict[int, Dict[str, int]]:
+        """Cumulative sort-node counters of every table that has been part of
+        a sort node, by archetype id (mwhip_sort_stats; HIP backend): runs,
+        stay_runs (compaction runs that patched the new rows in place),
+        rows_copied (rows the gather copied per column), rows_in, rows_out,
+        tail_rows.  Waits for the executor's stream."""
+        rt = runtime_lib()
+        rt.mwhip_sort_stats.restype = C.c_int32
+        rt.mwhip_sort_stats.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(SortStats)]
+        out = {}
+        archetype = 0
+        while True:
+            st = SortStats()
+            rc = rt.mwhip_sort_stats(self.hip_exec(), archetype, C.byref(st))
+            if rc == -1:
+                return out
+            if rc < 0:
+                raise RuntimeError(f"mwhip_sort_stats({archetype}) -> {rc}")
+            if rc == 0:
+                out[archetype] = {name: int(getattr(st, name)) for name, _ in st._fields_}
+            archetype += 1
 
     def snapshot(self) -> "Snapshot":
         """A new, empty Snapshot of this simulator (HIP backend; raises on the

@@ -1,0 +1,295 @@
+"""GPU: stay mode of the compaction chain (madrona_amd/csrc/sort_archetype.hip):
+a world sort that moves no surviving row of the sorted prefix patches the new
+rows into the holes of the current buffers instead of gathering every column
+into its twin.
+
+sims/sort_stress with flag 32 (Plan), as test_sort_node_edges_gpu.py: two
+PlanResize runs in a row with no world sort between them shrink worlds from
+the back and grow them again, which is the balanced input.  Every sort runs
+once through mwhip_profile with MADRONA_MWHIP_SORT_SMALL=0 and
+MADRONA_MWHIP_SORT_COMPACT=2.  After every sort: all raw columns against
+numpy's stable argsort of the table dumped before it, per-world counts against
+np.bincount, every held handle through the Probe graph, and the path taken from
+the counters of Simulator.sort_stats()."""
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+
+from madrona_amd.simlib import Simulator, hip_lib_path
+from test_sort_node_edges_gpu import (FLAG_PINNED, FLAG_PLAN, KEY_SORT, LOAD_PLAN,
+                                      MAX_ITEMS, PLAN_RESIZE, PROBE, WORLD_SORT, Table,
+                                      _check_probe, _roles)
+
+pytestmark = pytest.mark.gpu
+
+COMPACT_CHAIN = ["sort.compact.prepare", "sort.compact.scatter", "sort.gather"]
+
+
+class Stress:
+    """One sort_stress simulator with `counts` items per world, world-sorted."""
+
+    def __init__(self, monkeypatch, counts, pinned=False, grid="", stay=""):
+        monkeypatch.setenv("MADRONA_MWHIP_SORT_SMALL", "0")
+        monkeypatch.setenv("MADRONA_MWHIP_SORT_COMPACT", "2")
+        monkeypatch.setenv("MADRONA_MWHIP_GATHER_WIDE", "0")
+        monkeypatch.setenv("MADRONA_MWHIP_SORT_CARRIES_MISC", "1")
+        for name, value in (("MADRONA_MWHIP_SORT_MAX_GRID", grid),
+                            ("MADRONA_MWHIP_SORT_STAY", stay)):
+            if value:
+                monkeypatch.setenv(name, value)
+            else:
+                monkeypatch.delenv(name, raising=False)
+        self.counts = np.asarray(counts, dtype=np.int64).copy()
+        self.worlds = len(self.counts)
+        self.case = SimpleNamespace(worlds=self.worlds)
+        self.pinned = pinned
+        flags = FLAG_PLAN | (FLAG_PINNED if pinned else 0)
+        self.sim = Simulator(hip_lib_path("sort_stress"), self.worlds, seed=3, flags=flags)
+
+    def __enter__(self):
+        s = self.sim.__enter__()
+        self.cols = [i for i, (name, _, _) in enumerate(s.columns)
+                     if name.startswith("Item.")]
+        self.key_col = [i for i in self.cols if s.columns[i][0] == "Item.Key"][0]
+        self._write_plan(self.counts)
+        s.run_taskgraph(LOAD_PLAN)
+        self.world_graph = s.taskgraph_graph(WORLD_SORT)
+        self.key_graph = s.taskgraph_graph(KEY_SORT)
+        self.probe_graph = s.taskgraph_graph(PROBE)
+        self.pin_ptr = s.tensor_ptr("item_vec3") if self.pinned else None
+        # (LoadPlan's own compaction left the table world-sorted; a world sort
+        # of it finds nothing to do)
+        s.profile(reps=1, graph=self.world_graph)
+        self.rows = int(self.counts.sum())      # table rows, destroyed included
+        assert self.table().n == self.rows
+        return self
+
+    def __exit__(self, *exc):
+        return self.sim.__exit__(*exc)
+
+    def _write_plan(self, target):
+        plan = np.zeros((self.worlds, 5), dtype=np.int32)
+        plan[:, 0] = target
+        plan[:, 2] = 0x5A3C96E1
+        self.sim.write_tensor("plan", plan)
+
+    def resize(self, target):
+        """PlanResize without a sort: worlds above target destroy from the back
+        (rows stay), worlds below append."""
+        target = np.asarray(target, dtype=np.int64)
+        assert target.min() >= 0 and target.max() <= MAX_ITEMS
+        self._write_plan(target)
+        self.sim.run_taskgraph(PLAN_RESIZE)
+        created = int(np.maximum(target - self.counts, 0).sum())
+        self.rows += created
+        self.counts = target.copy()
+        return created
+
+    def table(self, extra=16):
+        return Table(self.sim, self.cols, self.rows + extra)
+
+    def counters(self):
+        total = {}
+        for st in self.sim.sort_stats().values():
+            for name, v in st.items():
+                total[name] = total.get(name, 0) + v
+        return total
+
+    def sort(self, what, graph=None, key_sort=False):
+        """Runs the sort once and checks the table against numpy.  Returns the
+        kernel roles and what the counters advanced by."""
+        s = self.sim
+        before = self.table()
+        assert before.n == self.rows, (what, before.n, self.rows)
+        c0 = self.counters()
+        stats = s.profile(reps=1, graph=graph or self.world_graph)
+        c1 = self.counters()
+        delta = {name: c1[name] - c0.get(name, 0) for name in c1}
+
+        keys = before.keys if key_sort else before.worlds.view(np.uint32)
+        perm = np.argsort(keys, kind="stable")
+        if not key_sort:
+            perm = perm[keys[perm] != 0xFFFFFFFF]
+        self.rows = len(perm)
+        after = self.table()
+        assert after.n == len(perm), (what, "numRows", after.n, len(perm))
+        after.assert_equals(before, perm, what)
+        if not key_sort:
+            assert (after.worlds >= 0).all(), what
+            _, per_world = s.dump_column(self.key_col, MAX_ITEMS)
+            assert np.array_equal(per_world, self.counts), what
+            assert np.array_equal(per_world,
+                                  np.bincount(after.worlds, minlength=self.worlds)), what
+        if self.pinned:
+            assert s.tensor_ptr("item_vec3") == self.pin_ptr, what
+            exported = s.read_tensor("item_vec3")[: after.n]
+            assert np.array_equal(exported.view(np.uint8).reshape(after.n, 12),
+                                  after.cols["Item.Vec3"]), what
+        s.profile(reps=1, graph=self.probe_graph)
+        _check_probe(s, self.case, after, what)
+        return [r for r, _ in _roles(stats)], delta
+
+    def swap(self, worlds, shrink):
+        """The balanced input: `worlds` lose `shrink` items from the back and
+        get as many new ones.  Returns the rows appended."""
+        target = self.counts.copy()
+        target[worlds] -= shrink
+        assert self.resize(target) == 0
+        target[worlds] += shrink
+        return self.resize(target)
+
+
+def _third(worlds, seed):
+    rng = np.random.default_rng(seed)
+    picked = np.nonzero(rng.random(worlds) < 1 / 3)[0]
+    return picked, rng.integers(1, 7, len(picked))
+
+
+def _assert_stayed(delta, moved, what=""):
+    assert delta["runs"] == 1 and delta["stay_runs"] == 1, (what, delta)
+    assert delta["rows_copied"] == moved, (what, delta)
+
+
+def _assert_full(delta, rows_out, what=""):
+    assert delta["runs"] == 1 and delta["stay_runs"] == 0, (what, delta)
+    assert delta["rows_copied"] == rows_out, (what, delta)
+
+
+@pytest.mark.parametrize("pinned", [False, True], ids=["plain", "pinned"])
+def test_balanced_stays(built, monkeypatch, pinned):
+    counts = np.full(300, 20)
+    picked, shrink = _third(300, 11)
+    dumps = {}
+    for stay in ("", "0"):
+        with Stress(monkeypatch, counts, pinned=pinned, stay=stay) as t:
+            created = t.swap(picked, shrink)
+            assert created == shrink.sum() and t.rows == 6000 + created
+            roles, delta = t.sort(f"balanced stay={stay!r}")
+            assert roles[:3] == COMPACT_CHAIN, roles
+            assert ("sort.finalize" in roles) == pinned, roles
+            if stay == "":
+                _assert_stayed(delta, created)
+            else:
+                _assert_full(delta, 6000)
+            dumps[stay] = t.table().cols
+    # the same bytes either way (entity ids come out of per-world caches that
+    # claim blocks of the global free list with atomics: not the same from one
+    # simulator to the next, and checked against each run's own input above)
+    for name, col in dumps[""].items():
+        if name != "Item.Entity":
+            assert np.array_equal(col, dumps["0"][name]), name
+
+
+def test_one_world_one_row_short_takes_the_full_gather(built, monkeypatch):
+    counts = np.full(300, 20)
+    picked, shrink = _third(300, 12)
+    picked, shrink = picked[picked != 0], shrink[picked != 0]
+    with Stress(monkeypatch, counts) as t:
+        target = t.counts.copy()
+        target[0] -= 1
+        target[picked] -= shrink
+        t.resize(target)
+        target[picked] += shrink
+        t.resize(target)
+        roles, delta = t.sort("world 0 one row short")
+        assert roles[:3] == COMPACT_CHAIN, roles
+        _assert_full(delta, 5999)
+
+
+def test_sorted_table_outgrows_the_prefix(built, monkeypatch):
+    """(a) holds, (b) fails: tail rows land on rows of the tail."""
+    counts = np.full(300, 20)
+    with Stress(monkeypatch, counts) as t:
+        picked = np.arange(0, 299, 3)
+        target = t.counts.copy()
+        target[picked] -= 2
+        t.resize(target)
+        target[picked] += 2
+        target[299] += 2
+        t.resize(target)
+        roles, delta = t.sort("last world grows by 2")
+        assert roles[:3] == COMPACT_CHAIN, roles
+        _assert_full(delta, 6002)
+
+
+def test_dead_tail_has_nothing_to_move(built, monkeypatch):
+    counts = np.full(300, 20)
+    picked, _ = _third(300, 13)
+    with Stress(monkeypatch, counts) as t:
+        target = t.counts.copy()
+        target[picked] += 3
+        assert t.resize(target) == 3 * len(picked)
+        target[picked] -= 3
+        t.resize(target)
+        assert t.rows == 6000 + 3 * len(picked)
+        roles, delta = t.sort("dead tail")
+        assert roles[:3] == COMPACT_CHAIN, roles
+        _assert_stayed(delta, 0)
+        assert t.rows == 6000
+
+
+def test_tile_edge_with_grid_rounds(built, monkeypatch):
+    """19 items per world: world 107 holds rows 2033..2051, the six rows it
+    loses straddle the tile edge at row 2048, and their replacements land in
+    the second tile but go to holes of both.  One workgroup does every tile."""
+    counts = np.full(300, 19)
+    picked, shrink = _third(300, 14)
+    keep = picked != 107
+    picked, shrink = np.append(picked[keep], 107), np.append(shrink[keep], 6)
+    with Stress(monkeypatch, counts, grid="1") as t:
+        created = t.swap(picked, shrink)
+        roles, delta = t.sort("tile edge, grid 1")
+        assert roles[:3] == COMPACT_CHAIN, roles
+        _assert_stayed(delta, created)
+
+
+def test_sorted_tail_path_stays(built, monkeypatch):
+    """A tail longer than an eighth of the prefix goes through the one-workgroup
+    tail sort instead of the landing points."""
+    counts = np.full(100, 20)
+    with Stress(monkeypatch, counts) as t:
+        created = t.swap(np.arange(100), 4)
+        assert created == 400 and created * 8 > 2000
+        roles, delta = t.sort("sorted tail")
+        assert roles[:3] == COMPACT_CHAIN, roles
+        _assert_stayed(delta, 400)
+
+
+def test_modes_alternate_on_one_table(built, monkeypatch):
+    counts = np.full(300, 20)
+    with Stress(monkeypatch, counts, pinned=True) as t:
+        picked, shrink = _third(300, 15)
+        created = t.swap(picked, shrink)
+        _, delta = t.sort("stay 1")
+        _assert_stayed(delta, created, "stay 1")
+
+        target = t.counts.copy()
+        target[5] -= 1
+        t.resize(target)
+        _, delta = t.sort("full")
+        _assert_full(delta, 5999, "full")
+
+        picked, shrink = _third(300, 16)
+        created = t.swap(picked, shrink)
+        _, delta = t.sort("stay 2")
+        _assert_stayed(delta, created, "stay 2")
+
+        roles, delta = t.sort("key sort", graph=t.key_graph, key_sort=True)
+        assert roles[0] == "sort.histogram", roles
+        _assert_full(delta, 5999, "key sort")
+
+        # (scrambled across worlds: no sorted prefix to stay in)
+        roles, delta = t.sort("world sort after the key sort")
+        assert roles[:3] == COMPACT_CHAIN, roles
+        _assert_full(delta, 5999, "world sort after the key sort")
+
+        # (the key sort left every world's rows in key order, while PlanResize
+        # destroys the items a world made last: those rows now lie anywhere in
+        # the world's range, and the survivors behind them do move.  Replacing
+        # whole worlds is balanced whatever the order inside them.)
+        picked = np.arange(3, 300, 10)
+        created = t.swap(picked, t.counts[picked])
+        assert created == 600 and created * 8 < 5999
+        _, delta = t.sort("stay 3")
+        _assert_stayed(delta, created, "stay 3")

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded(); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
+#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded() and mwhip_digest_*() / mwhip_set_step_digest() (a per-world hash of chosen columns computed on the device); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
 
 typedef struct mwhip_exec mwhip_exec; /* opaque; == MWCudaExecutor::Impl */
 
@@ -618,6 +618,75 @@ typedef struct mwhip_snapshot_segment {
 } mwhip_snapshot_segment;
 int32_t mwhip_snapshot_segments(mwhip_exec *exec, uint64_t snapshot,
                                 mwhip_snapshot_segment *out, uint32_t max_out);
+
+/* State digests (added under ABI 9): D[g][w], a 64-bit hash per world w of a
+ * chosen set of columns, computed by one kernel into a small device buffer
+ * (madrona_amd/digest_ref.py is the same arithmetic in numpy).
+ * A PLAN is an ordered list of columns (archetype_id, component_id), numbered
+ * by position p = 0, 1, ...; Entity (component 0) and WorldID (component 1) may
+ * be listed like any other.  The columns of one archetype form a GROUP (they
+ * need not be adjacent in the plan); groups are ordered by their first column,
+ * a group's tag t is the plan position of that column, and a group's columns
+ * are taken in plan order.  All arithmetic is on uint64, modulo 2^64:
+ *   K1 = 0x9E3779B97F4A7C15  K2 = 0xBF58476D1CE4E5B9  K3 = 0x94D049BB133111EB
+ *   fin(x):       x ^= x >> 30; x *= K2; x ^= x >> 27; x *= K3; x ^= x >> 31
+ *   absorb(h, v): h = (h ^ v) * K1;  h ^= h >> 32
+ *   row(g, r):    h = fin(t_g + K1)
+ *                 for each column c of group g, in plan order:
+ *                     h = absorb(h, p_c)
+ *                     for each little-endian 32-bit word v of the row's cell in
+ *                             c (the cell zero-padded up to a multiple of 4 bytes):
+ *                         h = absorb(h, v)
+ *                 return fin(h)
+ *   D[g][w] = sum of row(g, r) over the rows r < numRows of g's table whose
+ *             WorldID == w
+ * Rows destroyed in place (WorldID < 0) add nothing.  D[g][w] is a function of
+ * the MULTISET of world w's rows in the table: it does not depend on where the
+ * rows sit, on which side of a column's twin buffers is current, on other
+ * worlds or on whether the table is sorted -- and it does not see the ORDER of
+ * a world's rows.  A cell swapped between two rows of one world is seen (a
+ * row's columns are chained).  Row counts and column addresses are read on the
+ * device when the kernel runs, so the asynchronous form is stream-ordered behind
+ * the replays queued before it, and a digest made before a table grew stays
+ * valid.  The buffer is zeroed in the same stream-ordered sequence.
+ *
+ * mwhip_digest_buffer: device address of uint64 D[groups][worlds] (owned by the
+ * executor, valid until the digest is destroyed), NULL for an unknown handle.
+ * mwhip_digest_group: archetype id and tag of group `group`.
+ * mwhip_set_step_digest: every replay of every STEP graph of the executor
+ * (packed ones included; render graphs are untouched) recomputes that digest,
+ * zeroing included, behind all of its task-graph nodes and before its pack node
+ * and its output rings -- an output ring whose src is mwhip_digest_buffer() so
+ * records the digest of step k in slot k.  0: none.  Lives in the executor, not
+ * in a graph: waits for the stream and rebuilds the launch graphs (handles stay
+ * valid; rebuilds on table growth keep it).  mwhip_profile lists the launches
+ * with roles "digest.zero" and "digest"; the latter's algo_bytes are the bytes
+ * of the listed cells of the live rows.  Destroying the step digest unsets it.
+ * Handles are unique in the process; mwhip_destroy frees what is left.
+ * Errors (non-zero, text in mwhip_last_error(), nothing changed): an unknown
+ * handle or one of another executor ("digest N is not one of this executor's";
+ * looked up first, so also with a null executor), n == 0, an archetype that is
+ * not registered, a component the archetype does not have, the same column
+ * listed twice, more than MWHIP_DIGEST_MAX_COLUMNS columns or
+ * MWHIP_DIGEST_MAX_GROUPS groups.  (No reference counterpart.) */
+#define MWHIP_DIGEST_MAX_COLUMNS 256
+#define MWHIP_DIGEST_MAX_GROUPS 64
+typedef struct mwhip_digest_column {
+    uint32_t archetype_id;
+    uint32_t component_id;
+} mwhip_digest_column;
+int mwhip_digest_create(mwhip_exec *exec, const mwhip_digest_column *columns,
+                        uint32_t n, uint64_t *digest_out);
+void mwhip_digest_destroy(mwhip_exec *exec, uint64_t digest);
+/* waits for the executor's stream */
+int mwhip_digest_compute(mwhip_exec *exec, uint64_t digest);
+/* queued on the executor's stream behind the replays queued so far */
+int mwhip_digest_compute_async(mwhip_exec *exec, uint64_t digest);
+void *mwhip_digest_buffer(mwhip_exec *exec, uint64_t digest, uint32_t *groups_out,
+                          uint32_t *worlds_out);
+int mwhip_digest_group(mwhip_exec *exec, uint64_t digest, uint32_t group,
+                       uint32_t *archetype_out, uint32_t *tag_out);
+int mwhip_set_step_digest(mwhip_exec *exec, uint64_t digest);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,8 @@
 // (runtime.hip: the C ABI; runtime_state.hip: device state, world construction,
 // table growth; runtime_launch.hip: launch lists and step graphs;
 // runtime_kernels.hip: the runtime's own small kernels; snapshot.hip: saving
-// and restoring all world state).  Not installed.
+// and restoring all world state; digest.hip: per-world state digests).  Not
+// installed.
 #pragma once
 #include "runtime_internal.hpp"
 #include <madrona/tracing.hpp>
@@ -258,6 +259,7 @@ struct LaunchGraph {
 extern MWHIP_RT __thread std::vector<void *> *t_allocScope;   // (runtime_state.hip)
 
 struct mwhip_snapshot_rec;      // (snapshot.hip)
+struct mwhip_digest_rec;        // (digest.hip)
 
 struct mwhip_exec {
     mwhip_state_config cfg {};
@@ -367,6 +369,11 @@ struct mwhip_exec {
 
     // mwhip_snapshot_create: by handle, freed with the executor (freeSnapshots)
     std::unordered_map<uint64_t, mwhip_snapshot_rec *> snapshots;
+
+    // mwhip_digest_create: by handle, freed with the executor (freeDigests);
+    // mwhip_set_step_digest: the one every step replay recomputes (0: none)
+    std::unordered_map<uint64_t, mwhip_digest_rec *> digests;
+    uint64_t stepDigest = 0;
 };
 
 // ---- functions one translation unit defines and another calls ----------------------
@@ -418,6 +425,14 @@ MWHIP_RT void writeDeviceTrace(mwhip_exec *exec);
       // (runtime_state.hip)
 MWHIP_RT void freeSnapshots(mwhip_exec *exec);
       // (snapshot.hip)
+MWHIP_RT void freeDigests(mwhip_exec *exec);
+      // (digest.hip)
+MWHIP_RT int stepDigestLaunches(mwhip_exec *exec, std::vector<KernelLaunch> &out);
+      // (digest.hip)
+MWHIP_RT int stepDigestCellBytes(mwhip_exec *exec, double *out);
+      // (digest.hip)
+MWHIP_RT int rebuildAllLaunchGraphs(mwhip_exec *exec);
+      // (runtime.hip)
 
 template <typename T>
 inline int devAllocT(mwhip_exec *exec, T **out, size_t count, bool zero = true)

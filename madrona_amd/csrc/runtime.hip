@@ -628,6 +628,7 @@ extern "C" void mwhip_destroy(mwhip_exec *exec)
         releaseLaunchGraph(*kv.second);
     }
     freeSnapshots(exec);
+    freeDigests(exec);
     for (void *p : exec->allocations) {
         (void)hipFree(p);
     }
@@ -1058,7 +1059,7 @@ extern "C" int mwhip_build_launch_graph_with_pack(
     return 0;
 }
 
-static int rebuildAllLaunchGraphs(mwhip_exec *exec)
+MWHIP_RT int rebuildAllLaunchGraphs(mwhip_exec *exec)
 {
     HIPCHK(hipStreamSynchronize(exec->stream));
     for (auto &kv : exec->launchGraphs) {
@@ -1557,6 +1558,13 @@ extern "C" int32_t mwhip_profile(mwhip_exec *exec, uint64_t graph, uint32_t reps
 
             const KernelLaunch &k = lg.launches[i];
             total_bytes[i] += k.fixedBytes;
+            if (strcmp(k.role, "digest") == 0) {
+                // the cells of the live rows it hashed, counted by the kernel
+                double cell_bytes = 0;
+                rc = stepDigestCellBytes(exec, &cell_bytes);
+                if (rc != 0) return rc;
+                total_bytes[i] += cell_bytes;
+            }
             if (k.kind == MWHIP_NODE_KERNEL &&
                     k.countMode == MWHIP_COUNT_QUERY_ROWS) {
                 // rows at the start of the step (steady-state approximation)

@@ -1072,6 +1072,16 @@ MWHIP_RT int instantiateLaunchGraph(mwhip_exec *exec,
         lg->launches.insert(lg->launches.end() - 1, render.begin(), render.end());
     }
 
+    // the step digest (mwhip_set_step_digest): recomputed by every replay of a
+    // step graph behind all of its task-graph nodes, so that the pack node and
+    // the output rings see this step's values
+    if (!lg->isRender) {
+        std::vector<KernelLaunch> digest;
+        rc = stepDigestLaunches(exec, digest);
+        if (rc != 0) return rc;
+        lg->launches.insert(lg->launches.end() - 1, digest.begin(), digest.end());
+    }
+
     if (pack_from != nullptr && pack_from->hasPack) {
         lg->hasPack = true;
         lg->pack = pack_from->pack;

@@ -245,6 +245,86 @@ private:
 friend class MWCudaExecutor;
 };
 
+// One column of a digest's plan: (archetype id, component id), e.g.
+// { TypeTracker::typeID<Agent>(), TypeTracker::typeID<Position>() }.
+struct DigestColumn {
+    uint32_t archetypeID;
+    uint32_t componentID;
+};
+static_assert(sizeof(DigestColumn) == sizeof(mwhip_digest_column));
+
+// A 64-bit hash per world of a chosen list of columns, one row of them per
+// table the list names, computed by one kernel into a device buffer
+// uint64 [numGroups()][worlds] (mwhip_digest_*, include/mwhip.h: the exact
+// definition).  It is a hash of the multiset of each world's rows: blind to the
+// order of a world's rows, to where they sit and to other worlds.  An extension
+// of this backend.  Belongs to the executor that made it and must not outlive it.
+class MWHipDigest {
+public:
+    MWHipDigest() : exec_(nullptr), digest_(0) {}
+    MWHipDigest(const MWHipDigest &) = delete;
+    MWHipDigest(MWHipDigest &&o) : exec_(o.exec_), digest_(o.digest_)
+    {
+        o.exec_ = nullptr;
+        o.digest_ = 0;
+    }
+
+    ~MWHipDigest()
+    {
+        if (exec_ != nullptr) {
+            mwhip_digest_destroy(exec_, digest_);
+        }
+    }
+
+    MWHipDigest &operator=(MWHipDigest &&o)
+    {
+        if (this != &o) {
+            if (exec_ != nullptr) {
+                mwhip_digest_destroy(exec_, digest_);
+            }
+            exec_ = o.exec_;
+            digest_ = o.digest_;
+            o.exec_ = nullptr;
+            o.digest_ = 0;
+        }
+        return *this;
+    }
+
+    // waits for the executor's stream
+    void compute() { req(mwhip_digest_compute(exec_, digest_), "compute"); }
+    // queued on the executor's stream behind the replays queued so far
+    void computeAsync() { req(mwhip_digest_compute_async(exec_, digest_), "computeAsync"); }
+    // uint64 [numGroups()][worlds] on the device, owned by the executor
+    void *devicePtr() const { return mwhip_digest_buffer(exec_, digest_, nullptr, nullptr); }
+    uint32_t numGroups() const
+    {
+        uint32_t groups = 0;
+        (void)mwhip_digest_buffer(exec_, digest_, &groups, nullptr);
+        return groups;
+    }
+
+    uint64_t handle() const { return digest_; }
+
+private:
+    MWHipDigest(mwhip_exec *exec, uint64_t digest)
+        : exec_(exec), digest_(digest)
+    {}
+
+    static void req(int rc, const char *what)
+    {
+        if (rc != 0) {
+            fprintf(stderr, "madrona_amd: digest %s failed (%d): %s\n", what, rc,
+                    mwhip_last_error());
+            abort();
+        }
+    }
+
+    mwhip_exec *exec_;
+    uint64_t digest_;
+
+friend class MWCudaExecutor;
+};
+
 namespace detail {
 
 // A renderer's MeshBVHData / MaterialData (host or device memory) as the
@@ -531,6 +611,23 @@ public:
         uint64_t snapshot = 0;
         req(mwhip_snapshot_create(exec_, &snapshot), "makeSnapshot");
         return MWHipSnapshot(exec_, snapshot);
+    }
+
+    // a digest of the listed columns of this executor's worlds (see MWHipDigest)
+    MWHipDigest makeDigest(Span<const DigestColumn> columns)
+    {
+        uint64_t digest = 0;
+        req(mwhip_digest_create(exec_, (const mwhip_digest_column *)columns.data(),
+            (uint32_t)columns.size(), &digest), "makeDigest");
+        return MWHipDigest(exec_, digest);
+    }
+
+    // every replay of a step graph recomputes `digest` behind its task-graph
+    // nodes and before its pack node and output rings; nullptr: none
+    void setStepDigest(const MWHipDigest *digest)
+    {
+        req(mwhip_set_step_digest(exec_, digest != nullptr ? digest->digest_ : 0),
+            "setStepDigest");
     }
 
     // Device-resident rings (extensions of this backend, include/mwhip.h).

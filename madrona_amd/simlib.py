@@ -13,6 +13,8 @@ from typing import Dict, List, Tuple
 
 import numpy as np
 
+from . import digest_ref
+
 REPO_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIP_BUILD_DIR = os.path.join(REPO_ROOT, "madrona_amd",
                              os.environ.get("MADRONA_HIP_BUILD_DIR", "_build"))
@@ -94,6 +96,11 @@ def _bind(lib: C.CDLL) -> None:
     lib.sim_hip_render_graph.argtypes = [C.c_void_p]
     lib.sim_hip_step_graph.restype = C.c_uint64
     lib.sim_hip_step_graph.argtypes = [C.c_void_p]
+    # (a simulator library built before state digests does not have it)
+    if hasattr(lib, "sim_hip_column_ids"):
+        lib.sim_hip_column_ids.restype = C.c_int
+        lib.sim_hip_column_ids.argtypes = [C.c_void_p, C.c_uint32,
+                                           C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
 
 
 class KernelStat(C.Structure):
@@ -109,6 +116,11 @@ class KernelStat(C.Structure):
         ("node_index", C.c_uint32),
         ("pad_", C.c_uint32),
     ]
+
+
+class DigestColumn(C.Structure):
+    """mwhip_digest_column (include/mwhip.h)"""
+    _fields_ = [("archetype_id", C.c_uint32), ("component_id", C.c_uint32)]
 
 
 class SortStats(C.Structure):
@@ -172,6 +184,21 @@ def runtime_lib() -> C.CDLL:
         fn.argtypes = [C.c_void_p, C.c_uint64]
     lib.mwhip_snapshot_bytes.restype = C.c_uint64
     lib.mwhip_snapshot_bytes.argtypes = [C.c_void_p, C.c_uint64]
+    lib.mwhip_digest_create.restype = C.c_int
+    lib.mwhip_digest_create.argtypes = [C.c_void_p, C.POINTER(DigestColumn), C.c_uint32,
+                                        C.POINTER(C.c_uint64)]
+    lib.mwhip_digest_destroy.restype = None
+    lib.mwhip_digest_destroy.argtypes = [C.c_void_p, C.c_uint64]
+    for fn in (lib.mwhip_digest_compute, lib.mwhip_digest_compute_async,
+               lib.mwhip_set_step_digest):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_uint64]
+    lib.mwhip_digest_buffer.restype = C.c_void_p
+    lib.mwhip_digest_buffer.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32),
+                                        C.POINTER(C.c_uint32)]
+    lib.mwhip_digest_group.restype = C.c_int
+    lib.mwhip_digest_group.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32,
+                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     return lib
 
 
@@ -361,6 +388,157 @@ class Trajectory:
         self.close()
 
 
+class StateDigest:
+    """A 64-bit hash per world of a list of dump-list columns, one row of
+    hashes per table the list names (madrona_amd/digest_ref.py is the exact
+    definition; mwhip_digest_*, include/mwhip.h, computes it on the device).
+    compute() returns a numpy uint64 [groups, worlds] on either backend, and the
+    same call gives the same numbers on both: on the HIP backend one kernel
+    hashes the tables where they are (sorted or not), on the reference backend
+    digest_ref is evaluated over dump_all().  It is a hash of the multiset of a
+    world's rows in each table: blind to the order of a world's rows.  Columns
+    that hold pointers differ between executors: list value columns only.
+    HIP backend only: compute_async() queues the computation on the executor's
+    stream behind the replays queued so far, `tensor` is a zero-copy torch int64
+    view [groups, worlds] of the device buffer, every_step() makes every replay
+    of a step graph recompute the digest (before its output rings: a ring over
+    `buffer_ptr` records the digest of every step).  close() frees it;
+    Simulator.close() orphans what is left."""
+
+    def __init__(self, sim: "Simulator", columns=None):
+        names = [c[0] for c in sim._columns]
+        if columns is None:
+            columns = list(range(len(names)))
+        self._indices: List[int] = []
+        for col in columns:
+            idx = names.index(col) if isinstance(col, str) else int(col)
+            if not 0 <= idx < len(names):
+                raise IndexError(f"digest(): no dump-list column {col!r}")
+            self._indices.append(idx)
+        if not self._indices:
+            raise ValueError("digest(): no columns")
+        if len(set(self._indices)) != len(self._indices):
+            raise ValueError("digest(): a column is listed twice")
+        self._sim = sim
+        self._tables = [names[i].split(".", 1)[0] for i in self._indices]
+        self.num_worlds = sim.num_worlds
+        self.handle = 0
+        self._exec = 0
+        self._rt = None
+        self._tensor = None
+        self._every_step = False
+        if sim.backend != "hip":
+            self.groups = [key for key, _, _ in digest_ref.plan_groups(self._tables)]
+            return
+        if not hasattr(sim.lib, "sim_hip_column_ids"):
+            raise RuntimeError("this simulator library has no sim_hip_column_ids: rebuild it")
+        self._rt = runtime_lib()
+        self._exec = sim.hip_exec()
+        plan = (DigestColumn * len(self._indices))()
+        for p, idx in enumerate(self._indices):
+            arch, comp = C.c_uint32(0), C.c_uint32(0)
+            if sim.lib.sim_hip_column_ids(sim.handle, idx, C.byref(arch), C.byref(comp)) != 0:
+                raise RuntimeError(f"sim_hip_column_ids({idx}) failed")
+            plan[p] = DigestColumn(arch.value, comp.value)
+        handle = C.c_uint64(0)
+        self._check(self._rt.mwhip_digest_create(self._exec, plan, len(self._indices),
+                                                 C.byref(handle)), "mwhip_digest_create")
+        self.handle = int(handle.value)
+        num_groups, num_worlds = C.c_uint32(0), C.c_uint32(0)
+        self.buffer_ptr = int(self._rt.mwhip_digest_buffer(
+            self._exec, self.handle, C.byref(num_groups), C.byref(num_worlds)) or 0)
+        assert num_worlds.value == self.num_worlds
+        # the archetype names, from the plan column that opens each group
+        self.groups = []
+        for g in range(num_groups.value):
+            arch, tag = C.c_uint32(0), C.c_uint32(0)
+            self._check(self._rt.mwhip_digest_group(self._exec, self.handle, g,
+                                                    C.byref(arch), C.byref(tag)),
+                        "mwhip_digest_group")
+            self.groups.append(self._tables[tag.value])
+
+    def _check(self, rc: int, what: str) -> None:
+        if rc != 0:
+            raise RuntimeError(f"{what} -> {rc}: {self._rt.mwhip_last_error().decode()}")
+
+    def _live(self) -> int:
+        if self._sim is None:
+            raise RuntimeError("this digest is closed (or its simulator is)")
+        if self._rt is None:
+            raise RuntimeError("only compute() works on the reference backend: "
+                               "this needs the HIP backend")
+        return self.handle
+
+    def _orphan(self) -> None:
+        """Simulator.close(): the executor has freed (or is about to free) it."""
+        self.handle = 0
+        self._exec = 0
+        self._sim = None
+        self._tensor = None
+
+    def compute(self) -> np.ndarray:
+        """uint64 [groups, worlds]; waits for the executor's stream."""
+        if self._sim is None:
+            raise RuntimeError("this digest is closed (or its simulator is)")
+        if self._rt is None:
+            sim = self._sim
+            return digest_ref.digest_of_dump(
+                self._tables, [sim.dump_column(i) for i in self._indices], self.num_worlds)
+        self._check(self._rt.mwhip_digest_compute(self._exec, self._live()),
+                    "mwhip_digest_compute")
+        return self.read()
+
+    def read(self) -> np.ndarray:
+        """The device buffer as it is (what the last compute, compute_async or
+        step left), uint64 [groups, worlds]; waits for the executor's stream."""
+        self._live()
+        self._sim.sync()
+        return self.tensor.cpu().numpy().view(np.uint64)
+
+    def compute_async(self) -> None:
+        handle = self._live()
+        self._check(self._rt.mwhip_digest_compute_async(self._exec, handle),
+                    "mwhip_digest_compute_async")
+
+    @property
+    def tensor(self):
+        """torch int64 [groups, worlds] over the device buffer (no copy)."""
+        self._live()
+        if self._tensor is None:
+            import torch
+
+            from .tensor import DeviceColumn
+            self._tensor = torch.as_tensor(
+                DeviceColumn(self.buffer_ptr, np.int64, (len(self.groups), self.num_worlds)),
+                device=torch.device("cuda", self._sim.gpu_id))
+        return self._tensor
+
+    def every_step(self, on: bool = True) -> None:
+        """Every replay of a step graph recomputes this digest (waits for the
+        stream and rebuilds the launch graphs); on=False turns it off again."""
+        handle = self._live()
+        if not on and not self._every_step:
+            return
+        self._check(self._rt.mwhip_set_step_digest(self._exec, handle if on else 0),
+                    "mwhip_set_step_digest")
+        self._every_step = bool(on)
+        # (the rebuilt graphs are looked up by the same handles)
+
+    def close(self) -> None:
+        if self._sim is not None:
+            if self.handle:
+                self._rt.mwhip_digest_destroy(self._exec, self.handle)
+            if self in self._sim._digests:
+                self._sim._digests.remove(self)
+        self._orphan()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class Simulator:
     """One simulator instance behind the C API (either backend)."""
 
@@ -386,6 +564,7 @@ class Simulator:
         self._async = None
         self._snapshots: List["Snapshot"] = []
         self._trajectories: List["Trajectory"] = []
+        self._digests: List["StateDigest"] = []
         self._tensor_info: Dict[str, Tuple[int, np.dtype, Tuple[int, ...], bool]] = {}
         for i in range(self.lib.sim_num_tensors(self.handle)):
             info = SimTensorInfo()
@@ -410,6 +589,10 @@ class Simulator:
             for traj in self._trajectories:
                 traj._orphan()
             self._trajectories.clear()
+            # ... and frees its digests
+            for dig in self._digests:
+                dig._orphan()
+            self._digests.clear()
             self.lib.sim_destroy(self.handle)
             self.handle = None
 
@@ -543,6 +726,14 @@ class Simulator:
         snap = Snapshot(self)
         self._snapshots.append(snap)
         return snap
+
+    def digest(self, columns=None) -> "StateDigest":
+        """A StateDigest over `columns` of the dump list (names or indices, in
+        that order; default: the whole dump list in its order).  Either
+        backend: see StateDigest for what the reference backend offers."""
+        dig = StateDigest(self, columns)
+        self._digests.append(dig)
+        return dig
 
     def record(self, names: List[str], steps: int, on_render: bool = False) -> "Trajectory":
         """Records the exported tensors `names` on the device from the next

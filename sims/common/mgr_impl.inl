@@ -514,6 +514,21 @@ int64_t sim_column_dump_raw(SimHandle *h, uint32_t idx, void *dst,
 #endif
 }
 
+int sim_hip_column_ids(SimHandle *h, uint32_t idx, uint32_t *archetype,
+                       uint32_t *component)
+{
+#ifdef SIM_BACKEND_REF_CPU
+    (void)h; (void)idx; (void)archetype; (void)component;
+    return -1;
+#else
+    if (idx >= h->columns.cols.size()) return -1;
+    const auto &c = h->columns.cols[idx];
+    *archetype = c.archetypeID;
+    *component = c.componentID;
+    return 0;
+#endif
+}
+
 uint64_t sim_hip_step_graph(SimHandle *h)
 {
 #ifdef SIM_BACKEND_REF_CPU

@@ -74,6 +74,11 @@ SIM_API int sim_hip_run_taskgraph(SimHandle *h, uint32_t taskgraph_id);
 SIM_API uint64_t sim_hip_taskgraph_graph(SimHandle *h, uint32_t taskgraph_id);
 SIM_API int64_t sim_column_dump_raw(SimHandle *h, uint32_t idx, void *dst,
                                     uint64_t dst_bytes);
+/* HIP backend only (-1 on the reference, or for an index past the dump list):
+ * the archetype and component ids of dump-list column idx, as
+ * mwhip_digest_create and the other per-column calls of mwhip.h take them. */
+SIM_API int sim_hip_column_ids(SimHandle *h, uint32_t idx, uint32_t *archetype,
+                               uint32_t *component);
 
 /* The meshes and materials the simulator hands to the batch ray caster (for the
  * tests' oracle).  Any pointer may be NULL; returns the number of objects (0:

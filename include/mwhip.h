@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded() and mwhip_digest_*() / mwhip_set_step_digest() (a per-world hash of chosen columns computed on the device); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
+#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded() and mwhip_digest_*() / mwhip_set_step_digest() (a per-world hash of chosen columns computed on the device) and mwhip_view_*() / mwhip_set_step_view() (padded per-world tensors of a table's columns); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
 
 typedef struct mwhip_exec mwhip_exec; /* opaque; == MWCudaExecutor::Impl */
 
@@ -687,6 +687,71 @@ void *mwhip_digest_buffer(mwhip_exec *exec, uint64_t digest, uint32_t *groups_ou
 int mwhip_digest_group(mwhip_exec *exec, uint64_t digest, uint32_t group,
                        uint32_t *archetype_out, uint32_t *tag_out);
 int mwhip_set_step_digest(mwhip_exec *exec, uint64_t digest);
+
+/* World views (added under ABI 9): a dense, zero-padded, world-major copy of
+ * chosen columns of ONE table, written by one kernel where the table is
+ * (madrona_amd/view_ref.py is the same definition in numpy).
+ * A view names one archetype a, an ordered list of n of its components and
+ * max_rows >= 1; Entity (component 0) and WorldID (component 1) may be listed
+ * like any other.  With W = the executor's number of worlds, a compute reads the
+ * table's row count and column addresses on the device at the time the kernel
+ * runs and leaves
+ *   count[w]   (int32) the rows r < numRows of the table whose WorldID cell
+ *              equals w: the full count, NOT clipped to max_rows;
+ *   V_c[w][j]  for each listed column c, the cell of the j-th such row in table
+ *              order (ascending r), for j < min(count[w], max_rows);
+ *   zero bytes for every j from there up to max_rows.
+ * So: every compute writes the buffers in full, padding included (what an
+ * earlier compute or a caller left there never shows); rows beyond max_rows are
+ * dropped, and count[w] > max_rows tells the caller that some were; rows
+ * destroyed in place (WorldID < 0) belong to no world.  The result does not
+ * depend on which side of a column's twin buffers is current, on whether
+ * worldOffsets / worldCounts are current, or on whether the table has a sorted
+ * prefix, holes in it, rows appended behind it, or was last sorted by another
+ * key: a row is placed by its own WorldID cell.  After a full step of a
+ * world-sorted table the view is the reference CPU backend's per-world table,
+ * padded.  The asynchronous form is stream-ordered behind the replays queued
+ * before it, and a view made before a table grew stays valid.
+ *
+ * mwhip_view_buffer: device address of uint8 V_c[W][max_rows][cell_bytes] of
+ * listed column `column` (position in the list), 256-byte aligned, owned by the
+ * executor and valid until the view is destroyed; NULL for an unknown handle or
+ * a column index out of range.  mwhip_view_counts: int32 count[W], likewise.
+ * mwhip_set_step_view(on != 0): every replay of every STEP graph of the
+ * executor (packed ones included; render graphs are untouched) recomputes the
+ * view behind all of its task-graph nodes (and behind the step digest) and
+ * before its pack node and its output rings -- an output ring whose src is
+ * mwhip_view_buffer() so records [K][W][max_rows][cell_bytes] of ragged data
+ * with nothing but graph launches on the stream.  Up to MWHIP_MAX_STEP_VIEWS
+ * step views, ONE launch for all of them; mwhip_profile lists it with role
+ * "view", algo_bytes = bytes written (the buffers and counts in full) + bytes
+ * read (the listed cells of the rows copied and the WorldID cell of every row
+ * counted).  on == 0 takes it out again.  The set lives in the executor, not in
+ * a graph: changing it waits for the stream and rebuilds the launch graphs
+ * (handles stay valid; rebuilds on table growth keep it).  Destroying a step
+ * view unsets it.  Views are derived state: snapshots do not save them (a
+ * restore followed by a compute gives the restored worlds' view).  Handles are
+ * unique in the process; mwhip_destroy frees what is left.
+ * Errors (non-zero, text in mwhip_last_error(), nothing changed): an unknown
+ * handle or one of another executor ("view N is not one of this executor's";
+ * looked up first, so also with a null executor), n == 0 or
+ * n > MWHIP_VIEW_MAX_COLUMNS, max_rows == 0, an archetype that is not
+ * registered, a component the archetype does not have, a component listed
+ * twice, a ninth step view, buffers that cannot be allocated.
+ * (No reference counterpart.) */
+#define MWHIP_VIEW_MAX_COLUMNS 32
+#define MWHIP_MAX_STEP_VIEWS 8
+int mwhip_view_create(mwhip_exec *exec, uint32_t archetype_id, const uint32_t *component_ids,
+                      uint32_t n, uint32_t max_rows, uint64_t *view_out);
+void mwhip_view_destroy(mwhip_exec *exec, uint64_t view);
+/* waits for the executor's stream */
+int mwhip_view_compute(mwhip_exec *exec, uint64_t view);
+/* queued on the executor's stream behind the replays queued so far */
+int mwhip_view_compute_async(mwhip_exec *exec, uint64_t view);
+void *mwhip_view_buffer(mwhip_exec *exec, uint64_t view, uint32_t column,
+                        uint64_t *bytes_out, uint32_t *cell_bytes_out);
+int32_t *mwhip_view_counts(mwhip_exec *exec, uint64_t view);
+int mwhip_set_step_view(mwhip_exec *exec, uint64_t view, int on);
 
 #ifdef __cplusplus
 }

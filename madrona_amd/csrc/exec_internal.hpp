@@ -2,8 +2,8 @@
 // (runtime.hip: the C ABI; runtime_state.hip: device state, world construction,
 // table growth; runtime_launch.hip: launch lists and step graphs;
 // runtime_kernels.hip: the runtime's own small kernels; snapshot.hip: saving
-// and restoring all world state; digest.hip: per-world state digests).  Not
-// installed.
+// and restoring all world state; digest.hip: per-world state digests; world_view.hip:
+// padded per-world views of a table's columns).  Not installed.
 #pragma once
 #include "runtime_internal.hpp"
 #include <madrona/tracing.hpp>
@@ -260,6 +260,7 @@ extern MWHIP_RT __thread std::vector<void *> *t_allocScope;   // (runtime_state.
 
 struct mwhip_snapshot_rec;      // (snapshot.hip)
 struct mwhip_digest_rec;        // (digest.hip)
+struct mwhip_view_rec;          // (world_view.hip)
 
 struct mwhip_exec {
     mwhip_state_config cfg {};
@@ -374,6 +375,11 @@ struct mwhip_exec {
     // mwhip_set_step_digest: the one every step replay recomputes (0: none)
     std::unordered_map<uint64_t, mwhip_digest_rec *> digests;
     uint64_t stepDigest = 0;
+
+    // mwhip_view_create: by handle, freed with the executor (freeViews);
+    // mwhip_set_step_view: those every step replay recomputes, in one launch
+    std::unordered_map<uint64_t, mwhip_view_rec *> views;
+    std::vector<uint64_t> stepViews;
 };
 
 // ---- functions one translation unit defines and another calls ----------------------
@@ -431,6 +437,12 @@ MWHIP_RT int stepDigestLaunches(mwhip_exec *exec, std::vector<KernelLaunch> &out
       // (digest.hip)
 MWHIP_RT int stepDigestCellBytes(mwhip_exec *exec, double *out);
       // (digest.hip)
+MWHIP_RT void freeViews(mwhip_exec *exec);
+      // (world_view.hip)
+MWHIP_RT int stepViewLaunches(mwhip_exec *exec, std::vector<KernelLaunch> &out);
+      // (world_view.hip)
+MWHIP_RT int stepViewReadBytes(mwhip_exec *exec, double *out);
+      // (world_view.hip)
 MWHIP_RT int rebuildAllLaunchGraphs(mwhip_exec *exec);
       // (runtime.hip)
 

@@ -629,6 +629,7 @@ extern "C" void mwhip_destroy(mwhip_exec *exec)
     }
     freeSnapshots(exec);
     freeDigests(exec);
+    freeViews(exec);
     for (void *p : exec->allocations) {
         (void)hipFree(p);
     }
@@ -1564,6 +1565,13 @@ extern "C" int32_t mwhip_profile(mwhip_exec *exec, uint64_t graph, uint32_t reps
                 rc = stepDigestCellBytes(exec, &cell_bytes);
                 if (rc != 0) return rc;
                 total_bytes[i] += cell_bytes;
+            }
+            if (strcmp(k.role, "view") == 0) {
+                // what the step views read: from the counts they just left
+                double read_bytes = 0;
+                rc = stepViewReadBytes(exec, &read_bytes);
+                if (rc != 0) return rc;
+                total_bytes[i] += read_bytes;
             }
             if (k.kind == MWHIP_NODE_KERNEL &&
                     k.countMode == MWHIP_COUNT_QUERY_ROWS) {

@@ -1082,6 +1082,15 @@ MWHIP_RT int instantiateLaunchGraph(mwhip_exec *exec,
         lg->launches.insert(lg->launches.end() - 1, digest.begin(), digest.end());
     }
 
+    // the step views (mwhip_set_step_view): one launch for all of them, at the
+    // same place and for the same reason
+    if (!lg->isRender) {
+        std::vector<KernelLaunch> views;
+        rc = stepViewLaunches(exec, views);
+        if (rc != 0) return rc;
+        lg->launches.insert(lg->launches.end() - 1, views.begin(), views.end());
+    }
+
     if (pack_from != nullptr && pack_from->hasPack) {
         lg->hasPack = true;
         lg->pack = pack_from->pack;

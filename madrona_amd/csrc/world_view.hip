@@ -1,0 +1,587 @@
+// libmadrona_hip.so -- world views: a dense, zero-padded, world-major copy of
+// chosen columns of one table, [worlds][max_rows][cell bytes] per column plus an
+// int32 count per world, written where the table is (mwhip_view_*,
+// include/mwhip.h; madrona_amd/view_ref.py is the definition).
+//
+// A view owns a device-resident PLAN -- the table header, per column the header
+// slot its base address is read from (the sort swaps a column with its twin),
+// the cell bytes and the column's slab of the view -- and one allocation that
+// holds the slabs and the counts.  Row counts, the sorted prefix and column
+// bases are read on the device when the kernel runs: no host round trip, and a
+// plan made before a table grew is still right after.
+//   worldViewKernel   a TEAM of T = min(64, next power of two >= max_rows) lanes
+//                     owns one world, a wavefront 64 / T consecutive worlds;
+//                     wavefronts stride over the (view, 64 / T worlds) items of
+//                     up to MWHIP_MAX_STEP_VIEWS views passed by value.
+// A team
+//   1. reads the WorldID cells of its world's range of the sorted prefix
+//      ([worldOffsets[w], +worldCounts[w]) clipped to [0, sortedRows)) and
+//      counts those equal to w;
+//   2. if all of them are: copies each column's cells of the range as ONE byte
+//      range (they are contiguous in the table and in the view), 16 bytes per
+//      lane where source and destination agree modulo 16, dwords where they
+//      agree modulo 4, bytes otherwise; if not (rows destroyed in place): goes
+//      through the range again, a row per lane, rank = live rows before it
+//      (a ballot masked to the team + popcount);
+//   3. scans the WorldID cells of [sortedRows, numRows) in order -- nothing
+//      when the table has no rows behind its prefix, the whole table when it
+//      has no prefix -- and appends the rows of its world, a row per lane;
+//   4. zeroes what is left of its slabs and stores count[w].
+// A row is placed by its own WorldID cell; worldOffsets / worldCounts /
+// sortedRows only say where to look, and every output index is w < numWorlds
+// and rank < max_rows by construction.  A team writes nothing but its own
+// world's slabs: no atomics, no spin-waits, no workgroup waits for another, no
+// LDS.  (copyChunk of copy_chunk.hpp moves a chunk with a whole workgroup; a
+// team is a part of a wavefront, so only its vector types are shared.)
+#include "exec_internal.hpp"
+#include "copy_chunk.hpp"
+
+namespace {
+
+constexpr uint32_t kViewThreads = 256;
+constexpr uint32_t kViewWaves = kViewThreads / 64u;
+
+struct ViewPlanColumn {
+    void *const *slot;      // &hdr->columns[c] on the device
+    char *dst;              // [numWorlds][maxRows][cellBytes]
+    uint32_t cellBytes;
+    uint32_t pad_;
+};
+
+struct ViewPlan {
+    const TableHdr *hdr;    // on the device
+    int32_t *counts;        // [numWorlds]
+    uint32_t numWorlds;
+    uint32_t maxRows;
+    uint32_t numColumns;
+    uint32_t teamLanes;     // T: a power of two, 1 .. 64
+    ViewPlanColumn columns[MWHIP_VIEW_MAX_COLUMNS];
+};
+
+// by value in the kernel-argument segment, like OutputRingArgs
+struct ViewArgs {
+    uint32_t numViews;
+    uint32_t items[MWHIP_MAX_STEP_VIEWS];       // wavefront work items of each view
+    const ViewPlan *plans[MWHIP_MAX_STEP_VIEWS];
+};
+
+using madrona::mwhip::CopyU4;
+using madrona::mwhip::GlobalU4;
+using madrona::mwhip::GlobalU32;
+using madrona::mwhip::GlobalU8;
+
+// n bytes by the T lanes of a team (t: lane in the team)
+__device__ inline void teamCopy(char *dst, const char *src, uint64_t n, uint32_t t, uint32_t T)
+{
+    const uint64_t d = (uint64_t)dst, s = (uint64_t)src;
+    GlobalU8 *d8 = (GlobalU8 *)d;
+    const GlobalU8 *s8 = (const GlobalU8 *)s;
+    uint64_t done = 0;
+    if (((d ^ s) & 15ull) == 0ull) {
+        uint64_t head = (16ull - (d & 15ull)) & 15ull;
+        head = head < n ? head : n;
+        for (uint64_t i = t; i < head; i += T) d8[i] = s8[i];
+        const uint64_t num_vec = (n - head) >> 4;
+        GlobalU4 *d4 = (GlobalU4 *)(d + head);
+        const GlobalU4 *s4 = (const GlobalU4 *)(s + head);
+        for (uint64_t i = t; i < num_vec; i += T) d4[i] = s4[i];
+        done = head + (num_vec << 4);
+    } else if (((d ^ s) & 3ull) == 0ull) {
+        uint64_t head = (4ull - (d & 3ull)) & 3ull;
+        head = head < n ? head : n;
+        for (uint64_t i = t; i < head; i += T) d8[i] = s8[i];
+        const uint64_t num_words = (n - head) >> 2;
+        GlobalU32 *d1 = (GlobalU32 *)(d + head);
+        const GlobalU32 *s1 = (const GlobalU32 *)(s + head);
+        for (uint64_t i = t; i < num_words; i += T) d1[i] = s1[i];
+        done = head + (num_words << 2);
+    }
+    for (uint64_t i = done + t; i < n; i += T) d8[i] = s8[i];
+}
+
+// n zero bytes by the T lanes of a team
+__device__ inline void teamZero(char *dst, uint64_t n, uint32_t t, uint32_t T)
+{
+    const uint64_t d = (uint64_t)dst;
+    GlobalU8 *d8 = (GlobalU8 *)d;
+    uint64_t head = (16ull - (d & 15ull)) & 15ull;
+    head = head < n ? head : n;
+    for (uint64_t i = t; i < head; i += T) d8[i] = (uint8_t)0;
+    const uint64_t num_vec = (n - head) >> 4;
+    GlobalU4 *d4 = (GlobalU4 *)(d + head);
+    const CopyU4 zero = { 0u, 0u, 0u, 0u };
+    for (uint64_t i = t; i < num_vec; i += T) d4[i] = zero;
+    for (uint64_t i = head + (num_vec << 4) + t; i < n; i += T) d8[i] = (uint8_t)0;
+}
+
+// one cell by one lane
+__device__ inline void cellCopy(char *dst, const char *src, uint32_t bytes)
+{
+    const uint64_t d = (uint64_t)dst, s = (uint64_t)src;
+    if (((d | s) & 15ull) == 0ull && bytes % 16u == 0u) {
+        GlobalU4 *d4 = (GlobalU4 *)d;
+        const GlobalU4 *s4 = (const GlobalU4 *)s;
+        for (uint32_t i = 0; i < bytes / 16u; i++) d4[i] = s4[i];
+    } else if (((d | s) & 3ull) == 0ull && bytes % 4u == 0u) {
+        GlobalU32 *d1 = (GlobalU32 *)d;
+        const GlobalU32 *s1 = (const GlobalU32 *)s;
+        for (uint32_t i = 0; i < bytes / 4u; i++) d1[i] = s1[i];
+    } else {
+        GlobalU8 *d8 = (GlobalU8 *)d;
+        const GlobalU8 *s8 = (const GlobalU8 *)s;
+        for (uint32_t i = 0; i < bytes; i++) d8[i] = s8[i];
+    }
+}
+
+// Rows [from, to) of the table, T at a time: those whose WorldID cell is w are
+// appended to world w's slabs behind the `have` rows already there (rows past
+// maxRows are counted, not copied).  from, to, w and have are the same in every
+// lane of a team.  Returns the rows found.
+__device__ inline uint32_t teamRows(const ViewPlan *plan, const int32_t *world_col,
+                                    int32_t from, int32_t to, uint32_t w, uint32_t have,
+                                    uint32_t t, uint32_t T, uint32_t team_shift,
+                                    unsigned long long team_bits)
+{
+    const uint32_t max_rows = plan->maxRows;
+    const uint32_t num_columns = plan->numColumns;
+    uint32_t found = 0;
+    for (int32_t base = from; base < to; base += (int32_t)T) {
+        const int32_t r = base + (int32_t)t;
+        const bool is = r < to && world_col[r] == (int32_t)w;
+        const unsigned long long m = (__ballot(is) >> team_shift) & team_bits;
+        const uint32_t rank =
+            have + found + (uint32_t)__builtin_popcountll(m & ((1ull << t) - 1ull));
+        if (is && rank < max_rows) {
+            const uint64_t out_row = (uint64_t)w * max_rows + rank;
+            for (uint32_t c = 0; c < num_columns; c++) {
+                const ViewPlanColumn col = plan->columns[c];
+                const char *src = (const char *)*col.slot;
+                cellCopy(col.dst + out_row * col.cellBytes,
+                         src + (uint64_t)(uint32_t)r * col.cellBytes, col.cellBytes);
+            }
+        }
+        found += (uint32_t)__builtin_popcountll(m);
+    }
+    return found;
+}
+
+// one wavefront, 64 / T consecutive worlds of one view
+__device__ inline void viewWave(const ViewPlan *plan, uint32_t item, uint32_t lane)
+{
+    const uint32_t T = plan->teamLanes;
+    const uint32_t num_worlds = plan->numWorlds;
+    const uint32_t max_rows = plan->maxRows;
+    const uint32_t num_columns = plan->numColumns;
+    const uint32_t team = lane / T;
+    const uint32_t t = lane & (T - 1u);
+    const uint32_t team_shift = team * T;
+    const unsigned long long team_bits = T >= 64u ? ~0ull : (1ull << T) - 1ull;
+    const uint32_t w = item * (64u / T) + team;
+    const bool valid = w < num_worlds;
+
+    const TableHdr *hdr = plan->hdr;
+    // (appends wait for the rows they take to be mapped: numRows rows are there,
+    // as for digestKernel; the header's capacity word may lag behind a growth)
+    int32_t n = hdr->numRows;
+    n = n > 0 ? n : 0;
+    int32_t prefix = hdr->sortedRows;
+    if (prefix < 0 || prefix > n) {
+        prefix = 0;         // whatever truncated the table: everything is "tail"
+    }
+    const int32_t *world_col = (const int32_t *)hdr->columns[1];
+
+    // where world w's rows of the sorted prefix are (a hint: each row is still
+    // tested against its own WorldID cell)
+    int32_t lo = 0, hi = 0;
+    if (valid && prefix > 0) {
+        const int32_t off = hdr->worldOffsets[w];
+        const int32_t cnt = hdr->worldCounts[w];
+        lo = off > 0 ? (off < prefix ? off : prefix) : 0;
+        if (cnt > 0) {
+            const int64_t end = (int64_t)off + cnt;
+            hi = end < (int64_t)prefix ? (int32_t)end : prefix;
+        }
+        hi = hi > lo ? hi : lo;
+    }
+
+    // 1. the live rows of the range
+    uint32_t live = 0;
+    for (int32_t base = lo; base < hi; base += (int32_t)T) {
+        const int32_t r = base + (int32_t)t;
+        const bool is = r < hi && world_col[r] == (int32_t)w;
+        live += (uint32_t)__builtin_popcountll((__ballot(is) >> team_shift) & team_bits);
+    }
+
+    // 2. copy them
+    if (live == (uint32_t)(hi - lo)) {
+        const uint32_t k = live < max_rows ? live : max_rows;
+        if (k != 0u) {
+            for (uint32_t c = 0; c < num_columns; c++) {
+                const ViewPlanColumn col = plan->columns[c];
+                const char *src = (const char *)*col.slot;
+                teamCopy(col.dst + (uint64_t)w * max_rows * col.cellBytes,
+                         src + (uint64_t)(uint32_t)lo * col.cellBytes,
+                         (uint64_t)k * col.cellBytes, t, T);
+            }
+        }
+    } else {
+        (void)teamRows(plan, world_col, lo, hi, w, 0u, t, T, team_shift, team_bits);
+    }
+
+    // 3. the rows behind the prefix (decided here, per table, from the header)
+    uint32_t count = live;
+    if (valid) {
+        count += teamRows(plan, world_col, prefix, n, w, live, t, T, team_shift, team_bits);
+    }
+
+    // 4. padding and count
+    if (valid) {
+        const uint32_t k = count < max_rows ? count : max_rows;
+        if (k < max_rows) {
+            for (uint32_t c = 0; c < num_columns; c++) {
+                const ViewPlanColumn col = plan->columns[c];
+                teamZero(col.dst + ((uint64_t)w * max_rows + k) * col.cellBytes,
+                         (uint64_t)(max_rows - k) * col.cellBytes, t, T);
+            }
+        }
+        if (t == 0u) {
+            plan->counts[w] = (int32_t)count;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kViewThreads)
+worldViewKernel(ViewArgs args)
+{
+    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t total = 0;
+#pragma unroll
+    for (uint32_t v = 0; v < MWHIP_MAX_STEP_VIEWS; v++) {
+        if (v < args.numViews) total += args.items[v];
+    }
+    for (uint32_t item = blockIdx.x * kViewWaves + wave; item < total;
+         item += gridDim.x * kViewWaves) {
+        // the view this item belongs to (constant indices: the arguments stay
+        // in scalar registers)
+        const ViewPlan *plan = nullptr;
+        uint32_t rel = item;
+#pragma unroll
+        for (uint32_t v = 0; v < MWHIP_MAX_STEP_VIEWS; v++) {
+            if (plan == nullptr && v < args.numViews) {
+                if (rel < args.items[v]) {
+                    plan = args.plans[v];
+                } else {
+                    rel -= args.items[v];
+                }
+            }
+        }
+        if (plan != nullptr) {
+            viewWave(plan, rel, lane);
+        }
+    }
+}
+
+}
+
+// ---------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------
+struct mwhip_view_rec {
+    uint64_t handle = 0;
+    uint32_t numWorlds = 0;
+    uint32_t maxRows = 0;
+    uint32_t items = 0;         // wavefront work items
+    uint32_t rowBytes = 0;      // of the listed cells
+    std::vector<uint32_t> cellBytes;
+    std::vector<char *> slabs;  // into bufDev
+    int32_t *countsDev = nullptr;
+    ViewPlan *planDev = nullptr;
+    char *bufDev = nullptr;     // the slabs (256-byte aligned each), then the counts
+};
+
+namespace {
+
+// handles are unique in the process: one of another executor is never found
+std::atomic<uint64_t> g_nextView { 1 };
+
+void releaseView(mwhip_view_rec &view)
+{
+    if (view.planDev != nullptr) (void)hipFree(view.planDev);
+    if (view.bufDev != nullptr) (void)hipFree(view.bufDev);
+    view.planDev = nullptr;
+    view.bufDev = nullptr;
+}
+
+mwhip_view_rec *findView(mwhip_exec *exec, uint64_t handle)
+{
+    if (exec == nullptr) return nullptr;
+    auto it = exec->views.find(handle);
+    return it == exec->views.end() ? nullptr : it->second;
+}
+
+int unknownView(uint64_t handle)
+{
+    return fail(-3, "view %llu is not one of this executor's", (unsigned long long)handle);
+}
+
+dim3 viewGrid(mwhip_exec *exec, uint32_t items)
+{
+    const uint32_t blocks = (items + kViewWaves - 1u) / kViewWaves;
+    return dim3(std::max(std::min(blocks, std::max(exec->numCUs, 1u) * 16u), 1u), 1, 1);
+}
+
+int queueView(mwhip_exec *exec, mwhip_view_rec &view)
+{
+    ViewArgs args {};
+    args.numViews = 1;
+    args.items[0] = view.items;
+    args.plans[0] = view.planDev;
+    hipLaunchKernelGGL(worldViewKernel, viewGrid(exec, view.items), dim3(kViewThreads), 0,
+                       exec->stream, args);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+}
+
+MWHIP_RT void freeViews(mwhip_exec *exec)
+{
+    for (auto &kv : exec->views) {
+        releaseView(*kv.second);
+        delete kv.second;
+    }
+    exec->views.clear();
+    exec->stepViews.clear();
+}
+
+// The ONE launch that recomputes every step view inside a replay
+// (instantiateLaunchGraph); none when no step view is set.
+MWHIP_RT int stepViewLaunches(mwhip_exec *exec, std::vector<KernelLaunch> &out)
+{
+    ViewArgs args {};
+    uint32_t items = 0;
+    double written = 0;
+    for (uint64_t handle : exec->stepViews) {
+        mwhip_view_rec *view = findView(exec, handle);
+        if (view == nullptr || args.numViews >= MWHIP_MAX_STEP_VIEWS) continue;
+        args.items[args.numViews] = view->items;
+        args.plans[args.numViews] = view->planDev;
+        args.numViews += 1;
+        items += view->items;
+        written += (double)view->numWorlds * ((double)view->maxRows * view->rowBytes + 4.0);
+    }
+    if (args.numViews == 0) return 0;
+
+    KernelLaunch k;
+    static_assert(sizeof(ViewArgs) <= sizeof(k.argStorage));
+    k.fn = (const void *)&worldViewKernel;
+    k.grid = viewGrid(exec, items);
+    k.block = dim3(kViewThreads, 1, 1);
+    k.setArgs(args);
+    k.name = "view";
+    k.role = "view";
+    k.kind = MWHIP_NODE_RECYCLE;
+    k.fixedBytes = written;     // (mwhip_profile adds what was read: stepViewReadBytes)
+    out.push_back(k);
+    return 0;
+}
+
+// Bytes the step views' last run read: the listed cells of the rows it copied
+// and the WorldID cells of the rows it counted (mwhip_profile).  Stream idle.
+MWHIP_RT int stepViewReadBytes(mwhip_exec *exec, double *out)
+{
+    *out = 0;
+    std::vector<int32_t> counts;
+    for (uint64_t handle : exec->stepViews) {
+        mwhip_view_rec *view = findView(exec, handle);
+        if (view == nullptr) continue;
+        counts.resize(view->numWorlds);
+        HIPCHK(hipMemcpy(counts.data(), view->countsDev, counts.size() * sizeof(int32_t),
+                         hipMemcpyDeviceToHost));
+        for (int32_t count : counts) {
+            const double rows = (double)std::max(count, 0);
+            *out += std::min(rows, (double)view->maxRows) * view->rowBytes + rows * 4.0;
+        }
+    }
+    return 0;
+}
+
+extern "C" int mwhip_view_create(mwhip_exec *exec, uint32_t archetype_id,
+                                 const uint32_t *component_ids, uint32_t n,
+                                 uint32_t max_rows, uint64_t *view_out)
+{
+    // (every refusal comes before anything is allocated)
+    if (exec == nullptr || !exec->stateBuilt || view_out == nullptr) {
+        return fail(-2, "view_create: no executor state");
+    }
+    if (n == 0 || component_ids == nullptr) {
+        return fail(-2, "view_create: no columns (n == 0)");
+    }
+    if (n > MWHIP_VIEW_MAX_COLUMNS) {
+        return fail(-2, "view_create: %u columns (at most %u)", n,
+                    (uint32_t)MWHIP_VIEW_MAX_COLUMNS);
+    }
+    if (max_rows == 0) {
+        return fail(-2, "view_create: max_rows == 0");
+    }
+    if (archetype_id >= exec->archetypes.size() || !exec->archetypes[archetype_id].registered) {
+        return fail(-2, "view_create: archetype %u is not registered", archetype_id);
+    }
+    const ArchetypeRec &arch = exec->archetypes[archetype_id];
+    std::vector<int> columns(n);
+    for (uint32_t p = 0; p < n; p++) {
+        columns[p] = findColumn(arch, component_ids[p]);
+        if (columns[p] < 0) {
+            return fail(-2, "view_create: column %u: archetype %u has no component %u",
+                        p, archetype_id, component_ids[p]);
+        }
+        for (uint32_t q = 0; q < p; q++) {
+            if (component_ids[q] == component_ids[p]) {
+                return fail(-2, "view_create: component %u is listed twice "
+                            "(positions %u and %u)", component_ids[p], q, p);
+            }
+        }
+    }
+
+    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
+    std::unique_ptr<mwhip_view_rec> view(new mwhip_view_rec {});
+    view->handle = g_nextView.fetch_add(1);
+    view->numWorlds = exec->cfg.num_worlds;
+    view->maxRows = max_rows;
+    uint32_t team = 1;
+    while (team < 64u && team < max_rows) team <<= 1;
+    const uint32_t per_wave = 64u / team;
+    view->items = (view->numWorlds + per_wave - 1u) / per_wave;
+
+    // the slabs, 256-byte aligned each, then the counts
+    std::vector<uint64_t> offsets(n);
+    uint64_t total = 0;
+    for (uint32_t p = 0; p < n; p++) {
+        const uint32_t cell = arch.colBytes[(size_t)columns[p]];
+        view->cellBytes.push_back(cell);
+        view->rowBytes += cell;
+        offsets[p] = total;
+        const uint64_t bytes = (uint64_t)view->numWorlds * max_rows * cell;
+        total += (bytes + 255ull) & ~255ull;
+    }
+    const uint64_t counts_at = total;
+    total += ((uint64_t)view->numWorlds * sizeof(int32_t) + 255ull) & ~255ull;
+
+    if (hipMalloc((void **)&view->bufDev, total) != hipSuccess ||
+            hipMalloc((void **)&view->planDev, sizeof(ViewPlan)) != hipSuccess ||
+            hipMemset(view->bufDev, 0, total) != hipSuccess) {
+        (void)hipGetLastError();    // (not left for the next launch check to find)
+        releaseView(*view);
+        return fail(-10, "view_create: no device memory for %llu bytes (%u worlds x %u rows "
+                    "x %u bytes)", (unsigned long long)total, view->numWorlds, max_rows,
+                    view->rowBytes);
+    }
+    view->countsDev = (int32_t *)(view->bufDev + counts_at);
+
+    ViewPlan plan {};
+    TableHdr *hdr = exec->hostState.tables + archetype_id;  // (a device address: never read here)
+    plan.hdr = hdr;
+    plan.counts = view->countsDev;
+    plan.numWorlds = view->numWorlds;
+    plan.maxRows = max_rows;
+    plan.numColumns = n;
+    plan.teamLanes = team;
+    for (uint32_t p = 0; p < n; p++) {
+        view->slabs.push_back(view->bufDev + offsets[p]);
+        plan.columns[p] = { &hdr->columns[columns[p]], view->slabs[p], view->cellBytes[p], 0u };
+    }
+    if (hipMemcpy(view->planDev, &plan, sizeof(plan), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        releaseView(*view);
+        return fail(-10, "view_create: the plan could not be copied to the device");
+    }
+    const uint64_t handle = view->handle;
+    exec->views[handle] = view.release();
+    *view_out = handle;
+    return 0;
+}
+
+extern "C" int mwhip_set_step_view(mwhip_exec *exec, uint64_t view, int on)
+{
+    if (findView(exec, view) == nullptr) return unknownView(view);
+    std::vector<uint64_t> &step_views = exec->stepViews;
+    const auto at = std::find(step_views.begin(), step_views.end(), view);
+    if ((at != step_views.end()) == (on != 0)) return 0;
+    if (on != 0 && step_views.size() >= MWHIP_MAX_STEP_VIEWS) {
+        return fail(-2, "set_step_view: %u step views are set already (at most %u)",
+                    (uint32_t)step_views.size(), (uint32_t)MWHIP_MAX_STEP_VIEWS);
+    }
+    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
+    HIPCHK(hipStreamSynchronize(exec->stream));
+    const std::vector<uint64_t> before = step_views;
+    if (on != 0) {
+        step_views.push_back(view);
+    } else {
+        step_views.erase(at);
+    }
+    int rc = rebuildAllLaunchGraphs(exec);
+    if (rc != 0) exec->stepViews = before;
+    return rc;
+}
+
+extern "C" void mwhip_view_destroy(mwhip_exec *exec, uint64_t handle)
+{
+    mwhip_view_rec *view = findView(exec, handle);
+    if (view == nullptr) return;
+    (void)hipSetDevice(exec->cfg.gpu_id);
+    // (the step graphs must stop naming its buffers before they go)
+    (void)mwhip_set_step_view(exec, handle, 0);
+    (void)hipStreamSynchronize(exec->stream);
+    releaseView(*view);
+    delete view;
+    exec->views.erase(handle);
+}
+
+extern "C" int mwhip_view_compute(mwhip_exec *exec, uint64_t handle)
+{
+    mwhip_view_rec *view = findView(exec, handle);
+    if (view == nullptr) return unknownView(handle);
+    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
+    int rc = queueView(exec, *view);
+    if (rc != 0) return rc;
+    HIPCHK(hipStreamSynchronize(exec->stream));
+    return 0;
+}
+
+extern "C" int mwhip_view_compute_async(mwhip_exec *exec, uint64_t handle)
+{
+    mwhip_view_rec *view = findView(exec, handle);
+    if (view == nullptr) return unknownView(handle);
+    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
+    return queueView(exec, *view);
+}
+
+extern "C" void *mwhip_view_buffer(mwhip_exec *exec, uint64_t handle, uint32_t column,
+                                   uint64_t *bytes_out, uint32_t *cell_bytes_out)
+{
+    mwhip_view_rec *view = findView(exec, handle);
+    if (view == nullptr) {
+        (void)unknownView(handle);
+        return nullptr;
+    }
+    if (column >= view->slabs.size()) {
+        (void)fail(-2, "view_buffer: column %u of %u", column, (uint32_t)view->slabs.size());
+        return nullptr;
+    }
+    if (bytes_out != nullptr) {
+        *bytes_out = (uint64_t)view->numWorlds * view->maxRows * view->cellBytes[column];
+    }
+    if (cell_bytes_out != nullptr) *cell_bytes_out = view->cellBytes[column];
+    return view->slabs[column];
+}
+
+extern "C" int32_t *mwhip_view_counts(mwhip_exec *exec, uint64_t handle)
+{
+    mwhip_view_rec *view = findView(exec, handle);
+    if (view == nullptr) {
+        (void)unknownView(handle);
+        return nullptr;
+    }
+    return view->countsDev;
+}

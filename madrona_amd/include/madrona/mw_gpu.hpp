@@ -20,6 +20,7 @@
 #include <madrona/types.hpp>
 #include <madrona/math.hpp>
 #include <madrona/render/cuda_batch_render_assets.hpp>
+#include <madrona/py/utils.hpp>
 
 #include <mwhip.h>
 
@@ -325,6 +326,100 @@ private:
 friend class MWCudaExecutor;
 };
 
+// A dense, zero-padded, world-major copy of chosen columns of one table:
+// per listed column uint8 [worlds][maxRows()][cell bytes] on the device, plus
+// int32 [worlds] row counts (not clipped to maxRows()), written in full by one
+// kernel where the table is, sorted or not (mwhip_view_*, include/mwhip.h: the
+// exact definition).  An extension of this backend.  Belongs to the executor
+// that made it and must not outlive it.
+class MWHipWorldView {
+public:
+    MWHipWorldView() : exec_(nullptr), view_(0), max_rows_(0), gpu_id_(0) {}
+    MWHipWorldView(const MWHipWorldView &) = delete;
+    MWHipWorldView(MWHipWorldView &&o)
+        : exec_(o.exec_), view_(o.view_), max_rows_(o.max_rows_), gpu_id_(o.gpu_id_)
+    {
+        o.exec_ = nullptr;
+        o.view_ = 0;
+    }
+
+    ~MWHipWorldView()
+    {
+        if (exec_ != nullptr) {
+            mwhip_view_destroy(exec_, view_);
+        }
+    }
+
+    MWHipWorldView &operator=(MWHipWorldView &&o)
+    {
+        if (this != &o) {
+            if (exec_ != nullptr) {
+                mwhip_view_destroy(exec_, view_);
+            }
+            exec_ = o.exec_;
+            view_ = o.view_;
+            max_rows_ = o.max_rows_;
+            gpu_id_ = o.gpu_id_;
+            o.exec_ = nullptr;
+            o.view_ = 0;
+        }
+        return *this;
+    }
+
+    // waits for the executor's stream
+    void compute() { req(mwhip_view_compute(exec_, view_), "compute"); }
+    // queued on the executor's stream behind the replays queued so far
+    void computeAsync() { req(mwhip_view_compute_async(exec_, view_), "computeAsync"); }
+
+    // uint8 [worlds][maxRows()][cell bytes] of listed column `column`
+    // (position in the list given to makeWorldView), owned by the executor
+    py::Tensor columnTensor(uint32_t column) const
+    {
+        uint64_t bytes = 0;
+        uint32_t cell = 0;
+        void *ptr = mwhip_view_buffer(exec_, view_, column, &bytes, &cell);
+        req(ptr != nullptr ? 0 : -1, "columnTensor");
+        const int64_t dims[3] = { (int64_t)mwhip_num_worlds(exec_), (int64_t)max_rows_,
+                                  (int64_t)cell };
+        return py::Tensor(ptr, py::TensorElementType::UInt8, Span<const int64_t>(dims, 3),
+                          Optional<int>::make((int)gpu_id_));
+    }
+
+    // int32 [worlds]: each world's rows in the table (may exceed maxRows())
+    py::Tensor countsTensor() const
+    {
+        void *ptr = mwhip_view_counts(exec_, view_);
+        req(ptr != nullptr ? 0 : -1, "countsTensor");
+        const int64_t dims[1] = { (int64_t)mwhip_num_worlds(exec_) };
+        return py::Tensor(ptr, py::TensorElementType::Int32, Span<const int64_t>(dims, 1),
+                          Optional<int>::make((int)gpu_id_));
+    }
+
+    uint32_t maxRows() const { return max_rows_; }
+    uint64_t handle() const { return view_; }
+
+private:
+    MWHipWorldView(mwhip_exec *exec, uint64_t view, uint32_t max_rows, int32_t gpu_id)
+        : exec_(exec), view_(view), max_rows_(max_rows), gpu_id_(gpu_id)
+    {}
+
+    static void req(int rc, const char *what)
+    {
+        if (rc != 0) {
+            fprintf(stderr, "madrona_amd: world view %s failed (%d): %s\n", what, rc,
+                    mwhip_last_error());
+            abort();
+        }
+    }
+
+    mwhip_exec *exec_;
+    uint64_t view_;
+    uint32_t max_rows_;
+    int32_t gpu_id_;
+
+friend class MWCudaExecutor;
+};
+
 namespace detail {
 
 // A renderer's MeshBVHData / MaterialData (host or device memory) as the
@@ -446,14 +541,14 @@ class MWCudaExecutor {
 public:
     static CUcontext initCUDA(int gpu_id) { return CUcontext { gpu_id }; }
 
-    MWCudaExecutor() : exec_(nullptr), num_taskgraphs_(0) {}
+    MWCudaExecutor() : exec_(nullptr), num_taskgraphs_(0), gpu_id_(0) {}
 
     MWCudaExecutor(const StateConfig &state_cfg,
                    const CompileConfig &,
                    CUcontext ctx,
                    Optional<CudaBatchRenderConfig> render_cfg =
                        Optional<CudaBatchRenderConfig>::none())
-        : exec_(nullptr), num_taskgraphs_(state_cfg.numTaskGraphs)
+        : exec_(nullptr), num_taskgraphs_(state_cfg.numTaskGraphs), gpu_id_(ctx.gpuID)
     {
         mwhip_state_config cfg {};
         mwhip_render_geometry geometry {};
@@ -520,7 +615,7 @@ public:
 
     MWCudaExecutor(const MWCudaExecutor &) = delete;
     MWCudaExecutor(MWCudaExecutor &&o)
-        : exec_(o.exec_), num_taskgraphs_(o.num_taskgraphs_)
+        : exec_(o.exec_), num_taskgraphs_(o.num_taskgraphs_), gpu_id_(o.gpu_id_)
     {
         o.exec_ = nullptr;
     }
@@ -540,6 +635,7 @@ public:
             }
             exec_ = o.exec_;
             num_taskgraphs_ = o.num_taskgraphs_;
+            gpu_id_ = o.gpu_id_;
             o.exec_ = nullptr;
         }
         return *this;
@@ -630,6 +726,26 @@ public:
             "setStepDigest");
     }
 
+    // a padded per-world view of `components` of archetype `archetype`'s table,
+    // max_rows rows per world (see MWHipWorldView)
+    MWHipWorldView makeWorldView(uint32_t archetype, Span<const uint32_t> components,
+                                 uint32_t max_rows)
+    {
+        uint64_t view = 0;
+        req(mwhip_view_create(exec_, archetype, components.data(),
+            (uint32_t)components.size(), max_rows, &view), "makeWorldView");
+        return MWHipWorldView(exec_, view, max_rows, gpu_id_);
+    }
+
+    // on: every replay of a step graph recomputes `view` behind its task-graph
+    // nodes and before its pack node and output rings (up to
+    // MWHIP_MAX_STEP_VIEWS views, one launch for all); off: no longer
+    void setStepView(const MWHipWorldView *view, bool on)
+    {
+        req(mwhip_set_step_view(exec_, view != nullptr ? view->view_ : 0, on ? 1 : 0),
+            "setStepView");
+    }
+
     // Device-resident rings (extensions of this backend, include/mwhip.h).
     // The k-th replay of a step graph after the call starts by copying slot
     // k % num_slots of `ring` (whole dwords) into `dst`, normally an exported
@@ -677,6 +793,7 @@ private:
 
     mwhip_exec *exec_;
     uint32_t num_taskgraphs_;
+    int32_t gpu_id_;
 };
 
 using MWHipExecutor = MWCudaExecutor;

@@ -199,6 +199,21 @@ def runtime_lib() -> C.CDLL:
     lib.mwhip_digest_group.restype = C.c_int
     lib.mwhip_digest_group.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32,
                                        C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    lib.mwhip_view_create.restype = C.c_int
+    lib.mwhip_view_create.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32),
+                                      C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+    lib.mwhip_view_destroy.restype = None
+    lib.mwhip_view_destroy.argtypes = [C.c_void_p, C.c_uint64]
+    for fn in (lib.mwhip_view_compute, lib.mwhip_view_compute_async):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_uint64]
+    lib.mwhip_view_buffer.restype = C.c_void_p
+    lib.mwhip_view_buffer.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32,
+                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    lib.mwhip_view_counts.restype = C.c_void_p
+    lib.mwhip_view_counts.argtypes = [C.c_void_p, C.c_uint64]
+    lib.mwhip_set_step_view.restype = C.c_int
+    lib.mwhip_set_step_view.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
     return lib
 
 
@@ -539,6 +554,160 @@ class StateDigest:
         self.close()
 
 
+class WorldView:
+    """A dense, zero-padded, world-major copy of columns of ONE table on the
+    device: per column uint8 [worlds, max_rows, cell_bytes], plus int32 [worlds]
+    row counts that are NOT clipped to max_rows (counts[w] > max_rows: rows were
+    dropped).  madrona_amd/view_ref.py is the exact definition; mwhip_view_*,
+    include/mwhip.h, computes it with one kernel where the table is, sorted or
+    not.  HIP backend only.  compute() waits for the executor's stream,
+    compute_async() queues behind the replays queued so far; tensor(name) and
+    `counts` are zero-copy torch tensors over the device buffers, which every
+    compute rewrites in full; every_step() makes every replay of a step graph
+    recompute the view (before its output rings: a ring over buffer_ptr(name)
+    records [K, worlds, max_rows, ...]).  close() frees it; Simulator.close()
+    orphans what is left."""
+
+    def __init__(self, sim: "Simulator", table: str, columns, max_rows: int):
+        names = [c[0] for c in sim._columns]
+        of_table = [n for n in names if n.split(".", 1)[0] == table]
+        if not of_table:
+            raise KeyError(f"world_view(): no table {table!r} in the dump list")
+        if columns is None:
+            columns = of_table
+        columns = list(columns)
+        for name in columns:
+            if name not in of_table:
+                raise KeyError(f"world_view(): {name!r} is not a column of table {table!r}")
+        if not columns:
+            raise ValueError("world_view(): no columns")
+        if len(set(columns)) != len(columns):
+            raise ValueError("world_view(): a column is listed twice")
+        if not hasattr(sim.lib, "sim_hip_column_ids"):
+            raise RuntimeError("this simulator library has no sim_hip_column_ids: rebuild it")
+        self._sim = sim
+        self.table = table
+        self.columns = columns
+        self.max_rows = int(max_rows)
+        self.num_worlds = sim.num_worlds
+        self._rt = runtime_lib()
+        self._exec = sim.hip_exec()
+        self._tensors = {}
+        self._every_step = False
+        self.handle = 0
+        archetypes = set()
+        comps = (C.c_uint32 * len(columns))()
+        for p, name in enumerate(columns):
+            arch, comp = C.c_uint32(0), C.c_uint32(0)
+            if sim.lib.sim_hip_column_ids(sim.handle, names.index(name), C.byref(arch),
+                                          C.byref(comp)) != 0:
+                raise RuntimeError(f"sim_hip_column_ids({name}) failed")
+            archetypes.add(arch.value)
+            comps[p] = comp.value
+        assert len(archetypes) == 1, archetypes
+        self.archetype = archetypes.pop()
+        handle = C.c_uint64(0)
+        self._check(self._rt.mwhip_view_create(
+            self._exec, self.archetype, comps, len(columns),
+            min(max(self.max_rows, 0), 0xFFFFFFFF), C.byref(handle)), "mwhip_view_create")
+        self.handle = int(handle.value)
+        self._buffers = {}
+        for p, name in enumerate(columns):
+            nbytes, cell = C.c_uint64(0), C.c_uint32(0)
+            ptr = self._rt.mwhip_view_buffer(self._exec, self.handle, p, C.byref(nbytes),
+                                             C.byref(cell))
+            assert ptr and nbytes.value == self.num_worlds * self.max_rows * cell.value
+            self._buffers[name] = (int(ptr), int(cell.value))
+        self.counts_ptr = int(self._rt.mwhip_view_counts(self._exec, self.handle) or 0)
+
+    def _check(self, rc: int, what: str) -> None:
+        if rc != 0:
+            raise RuntimeError(f"{what} -> {rc}: {self._rt.mwhip_last_error().decode()}")
+
+    def _live(self) -> int:
+        if self._sim is None:
+            raise RuntimeError("this world view is closed (or its simulator is)")
+        return self.handle
+
+    def _orphan(self) -> None:
+        """Simulator.close(): the executor has freed (or is about to free) it."""
+        self.handle = 0
+        self._exec = 0
+        self._sim = None
+        self._tensors = {}
+
+    def compute(self) -> "WorldView":
+        """Rewrites every buffer and the counts; waits for the executor's stream."""
+        self._check(self._rt.mwhip_view_compute(self._exec, self._live()),
+                    "mwhip_view_compute")
+        return self
+
+    def compute_async(self) -> None:
+        self._check(self._rt.mwhip_view_compute_async(self._exec, self._live()),
+                    "mwhip_view_compute_async")
+
+    def buffer_ptr(self, name: str) -> int:
+        """Device address of column `name`'s [worlds, max_rows, cell_bytes] bytes."""
+        self._live()
+        return self._buffers[name][0]
+
+    def cell_bytes(self, name: str) -> int:
+        return self._buffers[name][1]
+
+    def _wrap(self, key, ptr, dtype, shape):
+        if key not in self._tensors:
+            import torch
+
+            from .tensor import DeviceColumn
+            self._tensors[key] = torch.as_tensor(
+                DeviceColumn(ptr, dtype, shape),
+                device=torch.device("cuda", self._sim.gpu_id))
+        return self._tensors[key]
+
+    def tensor(self, name: str, dtype=None):
+        """torch uint8 [worlds, max_rows, cell_bytes] over the device buffer of
+        column `name` (no copy), or, with a numpy dtype, [worlds, max_rows,
+        cell_bytes // itemsize] of that type."""
+        self._live()
+        ptr, cell = self._buffers[name]
+        dt = np.dtype(np.uint8 if dtype is None else dtype)
+        if cell % dt.itemsize != 0:
+            raise TypeError(f"{name}: cells of {cell} bytes do not hold whole {dt} items")
+        return self._wrap((name, dt.str), ptr, dt.type,
+                          (self.num_worlds, self.max_rows, cell // dt.itemsize))
+
+    @property
+    def counts(self):
+        """torch int32 [worlds] over the device buffer (no copy): each world's
+        rows in the table, which may exceed max_rows."""
+        self._live()
+        return self._wrap(("", "counts"), self.counts_ptr, np.int32, (self.num_worlds,))
+
+    def every_step(self, on: bool = True) -> None:
+        """Every replay of a step graph recomputes this view (waits for the
+        stream and rebuilds the launch graphs); on=False turns it off again."""
+        handle = self._live()
+        if not on and not self._every_step:
+            return
+        self._check(self._rt.mwhip_set_step_view(self._exec, handle, 1 if on else 0),
+                    "mwhip_set_step_view")
+        self._every_step = bool(on)
+
+    def close(self) -> None:
+        if self._sim is not None:
+            if self.handle:
+                self._rt.mwhip_view_destroy(self._exec, self.handle)
+            if self in self._sim._views:
+                self._sim._views.remove(self)
+        self._orphan()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class Simulator:
     """One simulator instance behind the C API (either backend)."""
 
@@ -565,6 +734,7 @@ class Simulator:
         self._snapshots: List["Snapshot"] = []
         self._trajectories: List["Trajectory"] = []
         self._digests: List["StateDigest"] = []
+        self._views: List["WorldView"] = []
         self._tensor_info: Dict[str, Tuple[int, np.dtype, Tuple[int, ...], bool]] = {}
         for i in range(self.lib.sim_num_tensors(self.handle)):
             info = SimTensorInfo()
@@ -593,6 +763,10 @@ class Simulator:
             for dig in self._digests:
                 dig._orphan()
             self._digests.clear()
+            # ... and its world views
+            for view in self._views:
+                view._orphan()
+            self._views.clear()
             self.lib.sim_destroy(self.handle)
             self.handle = None
 
@@ -734,6 +908,17 @@ class Simulator:
         dig = StateDigest(self, columns)
         self._digests.append(dig)
         return dig
+
+    def world_view(self, table: str, columns=None, max_rows: int = 0) -> "WorldView":
+        """A WorldView of `columns` (names as in `columns`, e.g. "Item.Vec3";
+        default: every dump-list column of the table) of table `table`, padded
+        to max_rows rows per world.  HIP backend; raises on the reference
+        backend, which has no executor to ask."""
+        if self.backend != "hip":
+            raise RuntimeError(f"world views need the HIP backend, this is {self.backend!r}")
+        view = WorldView(self, table, columns, max_rows)
+        self._views.append(view)
+        return view
 
     def record(self, names: List[str], steps: int, on_render: bool = False) -> "Trajectory":
         """Records the exported tensors `names` on the device from the next

@@ -1,5 +1,5 @@
 // One workgroup moves one chunk of device memory: what the snapshot kernels
-// (snapshot.hip) and the output rings (outputRingKernel, runtime_kernels.hip)
+// (snapshot.hip) and the output rings (outputRingKernel, output_ring.hip)
 // do per (segment, chunk) pair.  Device code of libmadrona_hip.so; not installed.
 #pragma once
 #include <cstdint>

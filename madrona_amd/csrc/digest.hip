@@ -262,32 +262,19 @@ struct mwhip_digest_rec {
     std::vector<uint32_t> groupTag;
     DigestPlan *planDev = nullptr;
     unsigned long long *outDev = nullptr;   // D, then the cell-byte counter
+
+    ~mwhip_digest_rec()
+    {
+        if (planDev != nullptr) (void)hipFree(planDev);
+        if (outDev != nullptr) (void)hipFree(outDev);
+    }
 };
 
 namespace {
 
-// handles are unique in the process: one of another executor is never found
-std::atomic<uint64_t> g_nextDigest { 1 };
-
-void releaseDigest(mwhip_digest_rec &dig)
-{
-    if (dig.planDev != nullptr) (void)hipFree(dig.planDev);
-    if (dig.outDev != nullptr) (void)hipFree(dig.outDev);
-    dig.planDev = nullptr;
-    dig.outDev = nullptr;
-}
-
 mwhip_digest_rec *findDigest(mwhip_exec *exec, uint64_t handle)
 {
-    if (exec == nullptr) return nullptr;
-    auto it = exec->digests.find(handle);
-    return it == exec->digests.end() ? nullptr : it->second;
-}
-
-int unknownDigest(uint64_t handle)
-{
-    return fail(-3, "digest %llu is not one of this executor's",
-                (unsigned long long)handle);
+    return findObject(exec != nullptr ? &exec->digests : nullptr, handle);
 }
 
 uint32_t digestWords(const mwhip_digest_rec &dig)
@@ -304,24 +291,36 @@ int queueDigest(mwhip_exec *exec, mwhip_digest_rec &dig)
     return 0;
 }
 
+int computeDigest(mwhip_exec *exec, uint64_t digest, bool wait)
+{
+    mwhip_digest_rec *dig = findDigest(exec, digest);
+    if (dig == nullptr) return unknownObject("digest", digest);
+    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
+    return finishQueued(exec, queueDigest(exec, *dig), wait);
 }
 
-MWHIP_RT void freeDigests(mwhip_exec *exec)
+// Bytes of the cells the step digest's last run hashed (KernelLaunch::measuredBytes).
+int stepDigestCellBytes(mwhip_exec *exec, double *out)
 {
-    for (auto &kv : exec->digests) {
-        releaseDigest(*kv.second);
-        delete kv.second;
-    }
-    exec->digests.clear();
-    exec->stepDigest = 0;
-}
-
-// The two launches that recompute the step digest inside a replay
-// (instantiateLaunchGraph); none when no step digest is set.
-MWHIP_RT int stepDigestLaunches(mwhip_exec *exec, std::vector<KernelLaunch> &out)
-{
-    mwhip_digest_rec *dig = findDigest(exec, exec->stepDigest);
+    *out = 0;
+    mwhip_digest_rec *dig = findDigest(exec, exec->extras.stepDigest);
     if (dig == nullptr) return 0;
+    unsigned long long bytes = 0;
+    HIPCHK(hipMemcpy(&bytes, dig->outDev + (size_t)dig->numGroups * dig->numWorlds,
+                     sizeof(bytes), hipMemcpyDeviceToHost));
+    *out = (double)bytes;
+    return 0;
+}
+
+}
+
+// Tail stage: the two launches that recompute the step digest inside a step
+// replay; none when no step digest is set.
+MWHIP_RT int stepDigestStage(mwhip_exec *exec, const LaunchGraph &lg,
+                             std::vector<KernelLaunch> &out)
+{
+    mwhip_digest_rec *dig = findDigest(exec, exec->extras.stepDigest);
+    if (lg.isRender || dig == nullptr) return 0;
     const uint32_t words = digestWords(*dig);
 
     KernelLaunch zero;
@@ -344,20 +343,9 @@ MWHIP_RT int stepDigestLaunches(mwhip_exec *exec, std::vector<KernelLaunch> &out
     k.name = "digest";
     k.role = "digest";
     k.kind = MWHIP_NODE_RECYCLE;
+    // the cells of the live rows it hashed, counted by the kernel
+    k.measuredBytes = &stepDigestCellBytes;
     out.push_back(k);
-    return 0;
-}
-
-// Bytes of the cells the step digest's last run hashed (mwhip_profile).  Stream idle.
-MWHIP_RT int stepDigestCellBytes(mwhip_exec *exec, double *out)
-{
-    *out = 0;
-    mwhip_digest_rec *dig = findDigest(exec, exec->stepDigest);
-    if (dig == nullptr) return 0;
-    unsigned long long bytes = 0;
-    HIPCHK(hipMemcpy(&bytes, dig->outDev + (size_t)dig->numGroups * dig->numWorlds,
-                     sizeof(bytes), hipMemcpyDeviceToHost));
-    *out = (double)bytes;
     return 0;
 }
 
@@ -375,6 +363,9 @@ extern "C" int mwhip_digest_create(mwhip_exec *exec, const mwhip_digest_column *
         return fail(-2, "digest_create: %u columns (at most %u)", n,
                     (uint32_t)MWHIP_DIGEST_MAX_COLUMNS);
     }
+    std::vector<ResolvedColumn> resolved;
+    int rc = resolveColumns(exec, "digest_create", cols, n, resolved);
+    if (rc != 0) return rc;
     struct HostGroup {
         uint32_t archetype, tag, rowBytes;
         std::vector<DigestPlanColumn> columns;
@@ -383,22 +374,6 @@ extern "C" int mwhip_digest_create(mwhip_exec *exec, const mwhip_digest_column *
     const EcsState &hs = exec->hostState;
     for (uint32_t p = 0; p < n; p++) {
         const uint32_t a = cols[p].archetype_id;
-        if (a >= exec->archetypes.size() || !exec->archetypes[a].registered) {
-            return fail(-2, "digest_create: column %u names archetype %u, which is "
-                        "not registered", p, a);
-        }
-        const ArchetypeRec &arch = exec->archetypes[a];
-        const int c = findColumn(arch, cols[p].component_id);
-        if (c < 0) {
-            return fail(-2, "digest_create: column %u: archetype %u has no component %u",
-                        p, a, cols[p].component_id);
-        }
-        for (uint32_t q = 0; q < p; q++) {
-            if (cols[q].archetype_id == a && cols[q].component_id == cols[p].component_id) {
-                return fail(-2, "digest_create: column (%u, %u) is listed twice "
-                            "(positions %u and %u)", a, cols[p].component_id, q, p);
-            }
-        }
         auto at = std::find_if(groups.begin(), groups.end(),
             [a](const HostGroup &g) { return g.archetype == a; });
         if (at == groups.end()) {
@@ -409,14 +384,12 @@ extern "C" int mwhip_digest_create(mwhip_exec *exec, const mwhip_digest_column *
             groups.push_back({ a, p, 0u, {} });
             at = groups.end() - 1;
         }
-        TableHdr *hdr = hs.tables + a;      // (a device address: never read here)
-        at->columns.push_back({ &hdr->columns[c], arch.colBytes[(size_t)c], p });
-        at->rowBytes += arch.colBytes[(size_t)c];
+        at->columns.push_back({ resolved[p].slot, resolved[p].cellBytes, p });
+        at->rowBytes += resolved[p].cellBytes;
     }
 
     HIPCHK(hipSetDevice(exec->cfg.gpu_id));
     std::unique_ptr<mwhip_digest_rec> dig(new mwhip_digest_rec {});
-    dig->handle = g_nextDigest.fetch_add(1);
     dig->numGroups = (uint32_t)groups.size();
     dig->numWorlds = exec->cfg.num_worlds;
 
@@ -445,60 +418,45 @@ extern "C" int mwhip_digest_create(mwhip_exec *exec, const mwhip_digest_column *
             hipMemcpy(dig->planDev, meta.data(), meta.size(),
                       hipMemcpyHostToDevice) != hipSuccess ||
             hipMemset(dig->outDev, 0, (size_t)digestWords(*dig) * 8u) != hipSuccess) {
-        releaseDigest(*dig);
-        return fail(-10, "digest_create: no device memory for the plan and %u x %u words",
-                    dig->numGroups, dig->numWorlds);
+        return CREATE_FAILED(dig, "digest_create: no device memory for the plan and "
+                             "%u x %u words", (uint32_t)groups.size(), exec->cfg.num_worlds);
     }
-    const uint64_t handle = dig->handle;
-    exec->digests[handle] = dig.release();
-    *digest_out = handle;
+    *digest_out = exec->digests.insert(std::move(dig));
     return 0;
 }
 
 extern "C" int mwhip_set_step_digest(mwhip_exec *exec, uint64_t digest)
 {
-    if (digest != 0 && findDigest(exec, digest) == nullptr) return unknownDigest(digest);
+    if (digest != 0 && findDigest(exec, digest) == nullptr) {
+        return unknownObject("digest", digest);
+    }
     if (exec == nullptr) return fail(-2, "set_step_digest: no executor");
-    if (exec->stepDigest == digest) return 0;
-    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
-    HIPCHK(hipStreamSynchronize(exec->stream));
-    const uint64_t before = exec->stepDigest;
-    exec->stepDigest = digest;
-    int rc = rebuildAllLaunchGraphs(exec);
-    if (rc != 0) exec->stepDigest = before;
-    return rc;
+    if (exec->extras.stepDigest == digest) return 0;
+    return changeReplayExtras(exec, [digest](ReplayExtras &extras) {
+        extras.stepDigest = digest;
+        return 0;
+    });
 }
 
 extern "C" void mwhip_digest_destroy(mwhip_exec *exec, uint64_t digest)
 {
-    mwhip_digest_rec *dig = findDigest(exec, digest);
-    if (dig == nullptr) return;
+    if (findDigest(exec, digest) == nullptr) return;
     (void)hipSetDevice(exec->cfg.gpu_id);
-    // (the step graphs must stop naming its buffers before they go)
-    if (exec->stepDigest == digest) (void)mwhip_set_step_digest(exec, 0);
+    // (the step graphs must stop naming its buffers before they go; if they
+    // could not be rebuilt without it, it stays until mwhip_destroy)
+    if (exec->extras.stepDigest == digest && mwhip_set_step_digest(exec, 0) != 0) return;
     (void)hipStreamSynchronize(exec->stream);
-    releaseDigest(*dig);
-    delete dig;
     exec->digests.erase(digest);
 }
 
 extern "C" int mwhip_digest_compute(mwhip_exec *exec, uint64_t digest)
 {
-    mwhip_digest_rec *dig = findDigest(exec, digest);
-    if (dig == nullptr) return unknownDigest(digest);
-    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
-    int rc = queueDigest(exec, *dig);
-    if (rc != 0) return rc;
-    HIPCHK(hipStreamSynchronize(exec->stream));
-    return 0;
+    return computeDigest(exec, digest, true);
 }
 
 extern "C" int mwhip_digest_compute_async(mwhip_exec *exec, uint64_t digest)
 {
-    mwhip_digest_rec *dig = findDigest(exec, digest);
-    if (dig == nullptr) return unknownDigest(digest);
-    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
-    return queueDigest(exec, *dig);
+    return computeDigest(exec, digest, false);
 }
 
 extern "C" void *mwhip_digest_buffer(mwhip_exec *exec, uint64_t digest,
@@ -506,7 +464,7 @@ extern "C" void *mwhip_digest_buffer(mwhip_exec *exec, uint64_t digest,
 {
     mwhip_digest_rec *dig = findDigest(exec, digest);
     if (dig == nullptr) {
-        (void)unknownDigest(digest);
+        (void)unknownObject("digest", digest);
         return nullptr;
     }
     if (groups_out != nullptr) *groups_out = dig->numGroups;
@@ -518,7 +476,7 @@ extern "C" int mwhip_digest_group(mwhip_exec *exec, uint64_t digest, uint32_t gr
                                   uint32_t *archetype_out, uint32_t *tag_out)
 {
     mwhip_digest_rec *dig = findDigest(exec, digest);
-    if (dig == nullptr) return unknownDigest(digest);
+    if (dig == nullptr) return unknownObject("digest", digest);
     if (group >= dig->numGroups) {
         return fail(-2, "digest_group: group %u of %u", group, dig->numGroups);
     }

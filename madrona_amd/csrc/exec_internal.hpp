@@ -1,9 +1,10 @@
 // Host-side internals shared by the translation units of libmadrona_hip.so
 // (runtime.hip: the C ABI; runtime_state.hip: device state, world construction,
 // table growth; runtime_launch.hip: launch lists and step graphs;
-// runtime_kernels.hip: the runtime's own small kernels; snapshot.hip: saving
-// and restoring all world state; digest.hip: per-world state digests; world_view.hip:
-// padded per-world views of a table's columns).  Not installed.
+// runtime_kernels.hip: the runtime's own small kernels; output_ring.hip: the
+// output rings; snapshot.hip: saving and restoring all world state; digest.hip:
+// per-world state digests; world_view.hip: padded per-world views of a table's
+// columns).  Not installed.
 #pragma once
 #include "runtime_internal.hpp"
 #include <madrona/tracing.hpp>
@@ -29,7 +30,7 @@
 #define MWHIP_RT __attribute__((visibility("hidden")))
 
 // ---- errors (runtime.hip) -------------------------------------------------------
-MWHIP_RT int fail(int code, const char *fmt, ...);
+MWHIP_RT int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 
 #define HIPCHK(expr) \
     do { \
@@ -74,23 +75,6 @@ struct PackArgs {
     uint32_t numRows;
 };
 
-// every output ring of one kind (mwhip_set_output_ring), the kernel argument of
-// outputRingKernel
-struct OutputRingArgs {
-    struct Ring {
-        const char *src;
-        char *ring;
-        uint64_t slotBytes;
-        uint32_t numSlots;
-        uint32_t firstReplay;   // replays of the kind completed when the ring was set
-    };
-    Ring rings[MWHIP_MAX_OUTPUT_RINGS];
-    uint64_t totalChunks;       // 16 KiB chunks over all rings
-    uint32_t numRings;
-    uint32_t counterWord;       // kStepReplayWord / kRenderReplayWord
-};
-constexpr uint64_t kOutputRingChunk = 16u << 10;    // == kCopyChunk (copy_chunk.hpp)
-
 // layout of the pinned health record (int32 words)
 constexpr uint32_t kStatsRows = 2;                          // [kMaxArchetypes]
 constexpr uint32_t kStatsGate = 2 + kMaxArchetypes;         // profiling gate flag
@@ -113,7 +97,6 @@ MWHIP_RT const void *gateKernelFn();
 MWHIP_RT const void *benchWindowMarkerFn();
 MWHIP_RT const void *packRowsKernelFn();
 MWHIP_RT const void *inputRingKernelFn();
-MWHIP_RT const void *outputRingKernelFn();
 #ifdef MADRONA_TRACING
 MWHIP_RT const void *traceMarkKernelFn();
 #endif
@@ -258,9 +241,42 @@ struct LaunchGraph {
 // other translation units)
 extern MWHIP_RT __thread std::vector<void *> *t_allocScope;   // (runtime_state.hip)
 
+// (needs MWHIP_RT and fail() from above; defines what mwhip_exec holds below)
+#include "exec_objects.hpp"
 struct mwhip_snapshot_rec;      // (snapshot.hip)
 struct mwhip_digest_rec;        // (digest.hip)
 struct mwhip_view_rec;          // (world_view.hip)
+
+// What a replay carries besides its task graphs.  Every launch graph is built
+// from it (the input rings open a step graph, the rest are tail stages:
+// instantiateLaunchGraph), so it changes only through changeReplayExtras.
+struct ReplayExtras {
+    // mwhip_set_input_ring
+    struct InputRing {
+        uint32_t *dst;
+        const uint32_t *ring;
+        uint32_t slotWords;
+        uint32_t numSlots;
+        uint32_t firstReplay;   // replays completed when the ring was set
+    };
+    std::vector<InputRing> inputRings;
+
+    // mwhip_set_output_ring: at most MWHIP_MAX_OUTPUT_RINGS over both kinds
+    struct OutputRing {
+        const char *src;
+        char *ring;
+        uint64_t slotBytes;
+        uint32_t numSlots;
+        uint32_t firstReplay;   // replays of the kind completed when the ring was set
+        uint32_t when;          // MWHIP_RING_ON_STEP / MWHIP_RING_ON_RENDER
+    };
+    std::vector<OutputRing> outputRings;
+
+    // mwhip_set_step_digest: the one every step replay recomputes (0: none)
+    uint64_t stepDigest = 0;
+    // mwhip_set_step_view: those every step replay recomputes, in one launch
+    std::vector<uint64_t> stepViews;
+};
 
 struct mwhip_exec {
     mwhip_state_config cfg {};
@@ -319,22 +335,7 @@ struct mwhip_exec {
     bool checkAfterRun = true;
     bool sortCarriesMisc = true;    // MADRONA_MWHIP_SORT_CARRIES_MISC
 
-    // mwhip_set_input_ring
-    struct InputRing {
-        uint32_t *dst;
-        const uint32_t *ring;
-        uint32_t slotWords;
-        uint32_t numSlots;
-        uint32_t firstReplay;   // replays completed when the ring was set
-    };
-    std::vector<InputRing> inputRings;
-
-    // mwhip_set_output_ring: at most MWHIP_MAX_OUTPUT_RINGS over both kinds
-    struct OutputRing {
-        OutputRingArgs::Ring ring;
-        uint32_t when;          // MWHIP_RING_ON_STEP / MWHIP_RING_ON_RENDER
-    };
-    std::vector<OutputRing> outputRings;
+    ReplayExtras extras;
 
     // MADRONA_TRACING builds: the device event log (mw_gpu/tracing.hpp), the
     // records of the first steps, the names funcID indexes
@@ -368,18 +369,11 @@ struct mwhip_exec {
     BvhNode *tlasNodes = nullptr;
     PreparedInstance *preparedInstances = nullptr;
 
-    // mwhip_snapshot_create: by handle, freed with the executor (freeSnapshots)
-    std::unordered_map<uint64_t, mwhip_snapshot_rec *> snapshots;
-
-    // mwhip_digest_create: by handle, freed with the executor (freeDigests);
-    // mwhip_set_step_digest: the one every step replay recomputes (0: none)
-    std::unordered_map<uint64_t, mwhip_digest_rec *> digests;
-    uint64_t stepDigest = 0;
-
-    // mwhip_view_create: by handle, freed with the executor (freeViews);
-    // mwhip_set_step_view: those every step replay recomputes, in one launch
-    std::unordered_map<uint64_t, mwhip_view_rec *> views;
-    std::vector<uint64_t> stepViews;
+    // executor objects by handle (exec_objects.hpp): mwhip_snapshot_create,
+    // mwhip_digest_create, mwhip_view_create; what is left goes with the executor
+    ExecObjectTable<mwhip_snapshot_rec> snapshots;
+    ExecObjectTable<mwhip_digest_rec> digests;
+    ExecObjectTable<mwhip_view_rec> views;
 };
 
 // ---- functions one translation unit defines and another calls ----------------------
@@ -429,20 +423,16 @@ MWHIP_RT int collectDeviceTrace(mwhip_exec *exec);
       // (runtime_state.hip)
 MWHIP_RT void writeDeviceTrace(mwhip_exec *exec);
       // (runtime_state.hip)
-MWHIP_RT void freeSnapshots(mwhip_exec *exec);
-      // (snapshot.hip)
-MWHIP_RT void freeDigests(mwhip_exec *exec);
+// tail stages of a replay (TailStage, runtime_launch.hip)
+MWHIP_RT int stepDigestStage(mwhip_exec *exec, const LaunchGraph &lg,
+                             std::vector<KernelLaunch> &out);
       // (digest.hip)
-MWHIP_RT int stepDigestLaunches(mwhip_exec *exec, std::vector<KernelLaunch> &out);
-      // (digest.hip)
-MWHIP_RT int stepDigestCellBytes(mwhip_exec *exec, double *out);
-      // (digest.hip)
-MWHIP_RT void freeViews(mwhip_exec *exec);
+MWHIP_RT int stepViewStage(mwhip_exec *exec, const LaunchGraph &lg,
+                           std::vector<KernelLaunch> &out);
       // (world_view.hip)
-MWHIP_RT int stepViewLaunches(mwhip_exec *exec, std::vector<KernelLaunch> &out);
-      // (world_view.hip)
-MWHIP_RT int stepViewReadBytes(mwhip_exec *exec, double *out);
-      // (world_view.hip)
+MWHIP_RT int outputRingStage(mwhip_exec *exec, const LaunchGraph &lg,
+                             std::vector<KernelLaunch> &out);
+      // (output_ring.hip)
 MWHIP_RT int rebuildAllLaunchGraphs(mwhip_exec *exec);
       // (runtime.hip)
 
@@ -452,3 +442,19 @@ inline int devAllocT(mwhip_exec *exec, T **out, size_t count, bool zero = true)
     return devAlloc(exec, (void **)out, count * sizeof(T), zero);
 }
 
+// The one way exec->extras changes: `change` edits it (non-zero: refused), every
+// launch graph is rebuilt from the result, and if either fails the executor
+// keeps what it had -- it never claims a ring, digest or view that its graphs do
+// not carry, or the reverse.  (Callers return early when there is nothing to
+// change: no rebuild.)
+template <typename Change>
+inline int changeReplayExtras(mwhip_exec *exec, Change &&change)
+{
+    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
+    HIPCHK(hipStreamSynchronize(exec->stream));
+    const ReplayExtras before = exec->extras;
+    int rc = change(exec->extras);
+    if (rc == 0) rc = rebuildAllLaunchGraphs(exec);
+    if (rc != 0) exec->extras = before;
+    return rc;
+}

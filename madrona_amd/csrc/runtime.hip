@@ -246,6 +246,43 @@ MWHIP_RT int findColumn(const ArchetypeRec &arch, uint32_t component_id)
     return -1;
 }
 
+// ---- executor objects (exec_objects.hpp) ----
+MWHIP_RT int resolveColumns(mwhip_exec *exec, const char *what,
+                            const mwhip_digest_column *columns, uint32_t n,
+                            std::vector<ResolvedColumn> &out)
+{
+    out.assign(n, ResolvedColumn {});
+    for (uint32_t p = 0; p < n; p++) {
+        const uint32_t a = columns[p].archetype_id;
+        const uint32_t component = columns[p].component_id;
+        if (a >= exec->archetypes.size() || !exec->archetypes[a].registered) {
+            return fail(-2, "%s: column %u: archetype %u is not registered", what, p, a);
+        }
+        const ArchetypeRec &arch = exec->archetypes[a];
+        const int c = findColumn(arch, component);
+        if (c < 0) {
+            return fail(-2, "%s: column %u: archetype %u has no component %u", what, p, a,
+                        component);
+        }
+        for (uint32_t q = 0; q < p; q++) {
+            if (columns[q].archetype_id == a && columns[q].component_id == component) {
+                return fail(-2, "%s: archetype %u: component %u is listed twice "
+                            "(positions %u and %u)", what, a, component, q, p);
+            }
+        }
+        TableHdr *hdr = exec->hostState.tables + a;     // (a device address: never read here)
+        out[p] = { c, &hdr->columns[c], arch.colBytes[(size_t)c] };
+    }
+    return 0;
+}
+
+MWHIP_RT int finishQueued(mwhip_exec *exec, int rc, bool wait)
+{
+    if (rc != 0 || !wait) return rc;
+    HIPCHK(hipStreamSynchronize(exec->stream));
+    return 0;
+}
+
 extern "C" void *mwhip_export_column(mwhip_exec *exec, uint32_t archetype_id,
                                      uint32_t component_id, int32_t slot)
 {
@@ -627,9 +664,9 @@ extern "C" void mwhip_destroy(mwhip_exec *exec)
     for (auto &kv : exec->launchGraphs) {
         releaseLaunchGraph(*kv.second);
     }
-    freeSnapshots(exec);
-    freeDigests(exec);
-    freeViews(exec);
+    exec->snapshots.clear();
+    exec->digests.clear();
+    exec->views.clear();
     for (void *p : exec->allocations) {
         (void)hipFree(p);
     }
@@ -1083,117 +1120,36 @@ extern "C" uint32_t mwhip_device_cus(const mwhip_exec *exec)
 extern "C" int mwhip_set_input_ring(mwhip_exec *exec, void *dst, const void *ring,
                                     uint64_t slot_bytes, uint32_t num_slots)
 {
+    // (every refusal comes before anything changes or is waited for)
     if (dst == nullptr) {
         return fail(-2, "set_input_ring: no destination");
     }
-    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
-    auto &rings = exec->inputRings;
-    rings.erase(std::remove_if(rings.begin(), rings.end(),
-        [dst](const mwhip_exec::InputRing &r) { return r.dst == dst; }), rings.end());
+    auto same = [dst](const ReplayExtras::InputRing &r) { return r.dst == dst; };
     if (ring != nullptr) {
         if (num_slots == 0 || slot_bytes == 0 || slot_bytes % 4 != 0 ||
                 slot_bytes / 4 > 0xFFFFFFFFull) {
             return fail(-2, "set_input_ring: %llu bytes x %u slots (whole dwords, "
                         "at least one slot)", (unsigned long long)slot_bytes, num_slots);
         }
-        if (rings.size() >= 4) {
+        const auto &set = exec->extras.inputRings;
+        // (a ring of dst is replaced, not added)
+        if (set.size() - (size_t)std::count_if(set.begin(), set.end(), same) >= 4) {
             return fail(-2, "set_input_ring: at most 4 rings");
         }
+    }
+    return changeReplayExtras(exec, [=](ReplayExtras &extras) {
+        auto &rings = extras.inputRings;
+        rings.erase(std::remove_if(rings.begin(), rings.end(), same), rings.end());
+        if (ring == nullptr) return 0;
         // (every replay of every STEP graph of the executor counts; render
         // graphs do not)
-        HIPCHK(hipStreamSynchronize(exec->stream));
         uint32_t done = 0;
         HIPCHK(hipMemcpy(&done, exec->replaySignal + kStepReplayWord, sizeof(done),
                          hipMemcpyDeviceToHost));
         rings.push_back({ (uint32_t *)dst, (const uint32_t *)ring,
                           (uint32_t)(slot_bytes / 4), num_slots, done });
-    }
-    return rebuildAllLaunchGraphs(exec);
-}
-
-static std::vector<mwhip_exec::OutputRing>::iterator
-findOutputRing(mwhip_exec *exec, const void *src, uint32_t when)
-{
-    auto &rings = exec->outputRings;
-    return std::find_if(rings.begin(), rings.end(),
-        [src, when](const mwhip_exec::OutputRing &r) {
-            return (const void *)r.ring.src == src && r.when == when;
-        });
-}
-
-static int completedReplays(mwhip_exec *exec, uint32_t when, uint32_t *out)
-{
-    HIPCHK(hipStreamSynchronize(exec->stream));
-    HIPCHK(hipMemcpy(out, exec->replaySignal +
-        (when == MWHIP_RING_ON_RENDER ? kRenderReplayWord : kStepReplayWord),
-        sizeof(*out), hipMemcpyDeviceToHost));
-    return 0;
-}
-
-extern "C" int mwhip_set_output_ring(mwhip_exec *exec, const void *src, void *ring,
-                                     uint64_t slot_bytes, uint32_t num_slots,
-                                     uint32_t when)
-{
-    // (every refusal comes before anything changes)
-    if (src == nullptr) {
-        return fail(-2, "set_output_ring: no source");
-    }
-    if (when != MWHIP_RING_ON_STEP && when != MWHIP_RING_ON_RENDER) {
-        return fail(-2, "set_output_ring: when = %u (MWHIP_RING_ON_STEP or "
-                    "MWHIP_RING_ON_RENDER)", when);
-    }
-    if (ring != nullptr && (num_slots == 0 || slot_bytes == 0)) {
-        return fail(-2, "set_output_ring: %llu bytes x %u slots (at least one of "
-                    "each)", (unsigned long long)slot_bytes, num_slots);
-    }
-    if (exec == nullptr) {
-        return fail(-2, "set_output_ring: no executor");
-    }
-    auto &rings = exec->outputRings;
-    auto at = findOutputRing(exec, src, when);
-    if (ring != nullptr && at == rings.end() &&
-            rings.size() >= MWHIP_MAX_OUTPUT_RINGS) {
-        return fail(-2, "set_output_ring: at most %u rings",
-                    (uint32_t)MWHIP_MAX_OUTPUT_RINGS);
-    }
-    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
-    if (ring == nullptr) {
-        if (at == rings.end()) return 0;
-        rings.erase(at);
-    } else {
-        // (every replay of every graph of that kind counts from here on)
-        uint32_t done = 0;
-        int rc = completedReplays(exec, when, &done);
-        if (rc != 0) return rc;
-        const mwhip_exec::OutputRing fresh {
-            { (const char *)src, (char *)ring, slot_bytes, num_slots, done }, when };
-        if (at != rings.end()) {
-            *at = fresh;
-        } else {
-            rings.push_back(fresh);
-        }
-    }
-    return rebuildAllLaunchGraphs(exec);
-}
-
-extern "C" int mwhip_output_ring_recorded(mwhip_exec *exec, const void *src,
-                                          uint32_t when, uint64_t *replays_out)
-{
-    if (exec == nullptr || replays_out == nullptr) {
-        return fail(-2, "output_ring_recorded: no executor / no result");
-    }
-    auto at = findOutputRing(exec, src, when);
-    if (at == exec->outputRings.end()) {
-        return fail(-2, "output_ring_recorded: no output ring of kind %u on %p",
-                    when, src);
-    }
-    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
-    uint32_t done = 0;
-    int rc = completedReplays(exec, when, &done);
-    if (rc != 0) return rc;
-    // (the device counts in 32 bits and wraps; so does the difference)
-    *replays_out = (uint32_t)(done - at->ring.firstReplay);
-    return 0;
+        return 0;
+    });
 }
 
 // Another stream waits for every replay queued so far WITHOUT touching the
@@ -1559,19 +1515,11 @@ extern "C" int32_t mwhip_profile(mwhip_exec *exec, uint64_t graph, uint32_t reps
 
             const KernelLaunch &k = lg.launches[i];
             total_bytes[i] += k.fixedBytes;
-            if (strcmp(k.role, "digest") == 0) {
-                // the cells of the live rows it hashed, counted by the kernel
-                double cell_bytes = 0;
-                rc = stepDigestCellBytes(exec, &cell_bytes);
+            if (k.measuredBytes != nullptr) {
+                double measured = 0;
+                rc = k.measuredBytes(exec, &measured);
                 if (rc != 0) return rc;
-                total_bytes[i] += cell_bytes;
-            }
-            if (strcmp(k.role, "view") == 0) {
-                // what the step views read: from the counts they just left
-                double read_bytes = 0;
-                rc = stepViewReadBytes(exec, &read_bytes);
-                if (rc != 0) return rc;
-                total_bytes[i] += read_bytes;
+                total_bytes[i] += measured;
             }
             if (k.kind == MWHIP_NODE_KERNEL &&
                     k.countMode == MWHIP_COUNT_QUERY_ROWS) {

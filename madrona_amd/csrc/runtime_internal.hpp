@@ -220,6 +220,9 @@ struct KernelLaunch {
     uint32_t archetype = 0xFFFFFFFFu;
     uint32_t bytesPerRow = 0;
     double fixedBytes = 0;          // algorithmic bytes of a launch that has no rows
+    // ... and those only the device knows (the rows it met): read back after
+    // the launch has run, stream idle (mwhip_profile adds them to fixedBytes)
+    int (*measuredBytes)(mwhip_exec *exec, double *out) = nullptr;
     uint32_t ioDeclared = 0;        // bytesPerRow from a declared read / write set
     uint32_t nodeIndex = 0xFFFFFFFFu;   // position of the node in its task graph's order
     uint32_t countMode = 0;

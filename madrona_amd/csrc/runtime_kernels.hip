@@ -9,7 +9,6 @@
 // and graph construction are host code, every node is its own kernel, and a
 // step is one hipGraph replay on the executor's private stream.
 #include "exec_internal.hpp"
-#include "copy_chunk.hpp"
 
 // ---- this translation unit: the small device kernels the runtime owns ----
 
@@ -243,46 +242,6 @@ inputRingKernel(EcsState *S, uint32_t *dst, const uint32_t *ring,
     }
 }
 
-// Last kernel before the health kernel of a graph whose kind has output rings
-// (mwhip_set_output_ring): every ring of that kind in ONE launch.  Ring r's
-// source goes to slot (replays of this kind since the ring was set) % num_slots
-// of its ring; the counter is the one the input rings read (step graphs) or the
-// render replays' own (render graphs), bumped by the health kernel that follows,
-// so both ring kinds see the same k inside a replay.  Workgroups stride over
-// the (ring, 16 KiB chunk) pairs: rings share the grid by the bytes they move.
-// A slot's alignment depends on k * slot_bytes, so copyChunk picks the width
-// (16 B, 4 B, 1 B) per replay, here.  One relaxed load, plain vector loads and
-// stores, no LDS.  (args: by value in the kernel-argument segment, like PackArgs.)
-static_assert(kOutputRingChunk == kCopyChunk && kCopyThreads == 256);
-__global__ void __launch_bounds__(kCopyThreads)
-outputRingKernel(EcsState *S, OutputRingArgs args)
-{
-    TraceScope trace_scope(S);
-    const uint32_t replay = __builtin_amdgcn_readfirstlane(
-        __hip_atomic_load(S->replayCounter + args.counterWord, __ATOMIC_RELAXED,
-                          __HIP_MEMORY_SCOPE_AGENT));
-    for (uint64_t work = blockIdx.x; work < args.totalChunks; work += gridDim.x) {
-        // the ring this chunk belongs to (a ring has at least one chunk)
-        uint32_t r = 0;
-        uint64_t first = 0;
-        for (;;) {
-            const uint64_t chunks =
-                (args.rings[r].slotBytes + kCopyChunk - 1u) / kCopyChunk;
-            if (work < first + chunks || r + 1u >= args.numRings) break;
-            first += chunks;
-            r++;
-        }
-        const OutputRingArgs::Ring ring = args.rings[r];
-        const uint64_t off = (work - first) * kCopyChunk;
-        if (off >= ring.slotBytes) continue;    // (cannot happen: totalChunks counts them)
-        const uint64_t left = ring.slotBytes - off;
-        const uint32_t n = left < kCopyChunk ? (uint32_t)left : kCopyChunk;
-        const uint32_t slot = (replay - ring.firstReplay) % ring.numSlots;
-        copyChunk(ring.ring + (uint64_t)slot * ring.slotBytes + off,
-                  ring.src + off, n);
-    }
-}
-
 #ifdef MADRONA_TRACING
 // One thread in front of every kernel of a traced graph (mw_gpu/tracing.hpp):
 // calibration starts a step's log, nodeStart names the kernel whose
@@ -390,7 +349,6 @@ const void *gateKernelFn() { return (const void *)&gateKernel; }
 const void *benchWindowMarkerFn() { return (const void *)&benchWindowMarker; }
 const void *packRowsKernelFn() { return (const void *)&packRowsKernel; }
 const void *inputRingKernelFn() { return (const void *)&inputRingKernel; }
-const void *outputRingKernelFn() { return (const void *)&outputRingKernel; }
 #ifdef MADRONA_TRACING
 const void *traceMarkKernelFn() { return (const void *)&traceMarkKernel; }
 #endif

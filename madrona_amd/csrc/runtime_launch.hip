@@ -363,7 +363,7 @@ static int buildLaunchList(mwhip_exec *exec, const std::vector<uint32_t> &tg_ids
         if (rc != 0) return rc;
     }
     if (!lg.isRender) {
-        for (const mwhip_exec::InputRing &ring : exec->inputRings) {
+        for (const ReplayExtras::InputRing &ring : exec->extras.inputRings) {
             KernelLaunch k;
             k.fn = inputRingKernelFn();
             k.grid = dim3(std::min<uint32_t>((ring.slotWords + 255u) / 256u, 1024u), 1, 1);
@@ -1031,6 +1031,48 @@ static void buildLaunchDeps(LaunchGraph &lg)
     }
 }
 
+// ---- the tail of a replay ----
+// What a replay does behind its task-graph nodes and in front of its health
+// kernel: each stage appends the launches the graph needs of it (none is fine).
+using TailStage = int (*)(mwhip_exec *exec, const LaunchGraph &lg,
+                          std::vector<KernelLaunch> &out);
+
+// a render graph's TLAS build + ray caster
+static int renderStage(mwhip_exec *exec, const LaunchGraph &lg, std::vector<KernelLaunch> &out)
+{
+    return lg.isRender ? renderLaunches(exec, out) : 0;
+}
+
+// the optional pack node: exported columns into a send buffer
+static int packStage(mwhip_exec *, const LaunchGraph &lg, std::vector<KernelLaunch> &out)
+{
+    if (!lg.hasPack) return 0;
+    KernelLaunch k;
+    k.fn = packRowsKernelFn();
+    const uint64_t total = (uint64_t)lg.pack.numRows * lg.pack.recordWords;
+    k.grid = dim3((uint32_t)std::min<uint64_t>(
+        std::max<uint64_t>((total + 255) / 256, 1), 4096), 1, 1);
+    k.block = dim3(256, 1, 1);
+    k.setArgs(lg.pack, (uint32_t *)lg.packDst);
+    k.name = "pack";
+    k.role = "pack.rows";
+    k.kind = MWHIP_NODE_RECYCLE;
+    out.push_back(k);
+    return 0;
+}
+
+// THE ORDER IS A CONTRACT.  What derives tensors from the step's state (the
+// render pass, the step digest, the step views) comes first, so that what
+// carries tensors away (the pack node, the output rings) sees this step's
+// values: a ring over a view's buffer records the view of the same replay.
+static constexpr TailStage kTailStages[] = {
+    renderStage,        // render graphs
+    stepDigestStage,    // step graphs, mwhip_set_step_digest (digest.hip)
+    stepViewStage,      // step graphs, mwhip_set_step_view (world_view.hip)
+    packStage,          // mwhip_build_launch_graph_with_pack
+    outputRingStage,    // the graph's kind, mwhip_set_output_ring (output_ring.hip)
+};
+
 MWHIP_RT int instantiateLaunchGraph(mwhip_exec *exec,
                                   const std::vector<uint32_t> &ids,
                                   const std::string &stat_name,
@@ -1064,82 +1106,17 @@ MWHIP_RT int instantiateLaunchGraph(mwhip_exec *exec,
     int rc = buildLaunchList(exec, ids, *lg);
     if (rc != 0) return rc;
 
-    if (lg->isRender) {
-        // TLAS build + ray caster, before the health kernel
-        std::vector<KernelLaunch> render;
-        rc = renderLaunches(exec, render);
-        if (rc != 0) return rc;
-        lg->launches.insert(lg->launches.end() - 1, render.begin(), render.end());
-    }
-
-    // the step digest (mwhip_set_step_digest): recomputed by every replay of a
-    // step graph behind all of its task-graph nodes, so that the pack node and
-    // the output rings see this step's values
-    if (!lg->isRender) {
-        std::vector<KernelLaunch> digest;
-        rc = stepDigestLaunches(exec, digest);
-        if (rc != 0) return rc;
-        lg->launches.insert(lg->launches.end() - 1, digest.begin(), digest.end());
-    }
-
-    // the step views (mwhip_set_step_view): one launch for all of them, at the
-    // same place and for the same reason
-    if (!lg->isRender) {
-        std::vector<KernelLaunch> views;
-        rc = stepViewLaunches(exec, views);
-        if (rc != 0) return rc;
-        lg->launches.insert(lg->launches.end() - 1, views.begin(), views.end());
-    }
-
     if (pack_from != nullptr && pack_from->hasPack) {
         lg->hasPack = true;
         lg->pack = pack_from->pack;
         lg->packDst = pack_from->packDst;
-
-        KernelLaunch k;
-        k.fn = packRowsKernelFn();
-        const uint64_t total =
-            (uint64_t)lg->pack.numRows * lg->pack.recordWords;
-        k.grid = dim3((uint32_t)std::min<uint64_t>(
-            std::max<uint64_t>((total + 255) / 256, 1), 4096), 1, 1);
-        k.block = dim3(256, 1, 1);
-        k.setArgs(lg->pack, (uint32_t *)lg->packDst);
-        k.name = "pack";
-        k.role = "pack.rows";
-        k.kind = MWHIP_NODE_RECYCLE;
-        // before the health kernel that closes every replay
-        lg->launches.insert(lg->launches.end() - 1, k);
     }
-
-    // the output rings of this graph's kind: one launch for all of them, the
-    // replay's last act before its health kernel (behind the pack node)
-    {
-        const uint32_t when = lg->isRender ? MWHIP_RING_ON_RENDER : MWHIP_RING_ON_STEP;
-        OutputRingArgs args {};
-        args.counterWord = lg->isRender ? kRenderReplayWord : kStepReplayWord;
-        uint64_t bytes = 0;
-        for (const mwhip_exec::OutputRing &out_ring : exec->outputRings) {
-            if (out_ring.when != when) continue;
-            args.rings[args.numRings++] = out_ring.ring;
-            args.totalChunks += (out_ring.ring.slotBytes + kOutputRingChunk - 1) /
-                kOutputRingChunk;
-            bytes += out_ring.ring.slotBytes;
-        }
-        if (args.numRings != 0) {
-            KernelLaunch k;
-            static_assert(sizeof(void *) + sizeof(OutputRingArgs) <=
-                          sizeof(k.argStorage));
-            k.fn = outputRingKernelFn();
-            k.grid = dim3((uint32_t)std::min<uint64_t>(args.totalChunks,
-                                                       8ull * exec->numCUs), 1, 1);
-            k.block = dim3(256, 1, 1);
-            k.setArgs(exec->stateDev, args);
-            k.name = "ring";
-            k.role = lg->isRender ? "ring.out.render" : "ring.out";
-            k.kind = MWHIP_NODE_RECYCLE;
-            k.fixedBytes = 2.0 * (double)bytes;     // read + written
-            lg->launches.insert(lg->launches.end() - 1, k);
-        }
+    // the tail: in front of the health kernel that closes every replay
+    for (TailStage stage : kTailStages) {
+        std::vector<KernelLaunch> launches;
+        rc = stage(exec, *lg, launches);
+        if (rc != 0) return rc;
+        lg->launches.insert(lg->launches.end() - 1, launches.begin(), launches.end());
     }
 
 #ifdef MADRONA_TRACING

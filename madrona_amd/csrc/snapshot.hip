@@ -266,22 +266,16 @@ struct mwhip_snapshot_rec {
     SnapReport *report = nullptr;       // pinned, device-visible
     SnapReport *reportDev = nullptr;    // ... and its device address
     uint32_t savesQueued = 0;
+
+    ~mwhip_snapshot_rec()
+    {
+        if (metaDev != nullptr) (void)hipFree(metaDev);
+        if (dataDev != nullptr) (void)hipFree(dataDev);
+        if (report != nullptr) (void)hipHostFree(report);
+    }
 };
 
 namespace {
-
-// handles are unique in the process: one of another executor is never found
-std::atomic<uint64_t> g_nextSnapshot { 1 };
-
-void releaseSnapshot(mwhip_snapshot_rec &snap)
-{
-    if (snap.metaDev != nullptr) (void)hipFree(snap.metaDev);
-    if (snap.dataDev != nullptr) (void)hipFree(snap.dataDev);
-    if (snap.report != nullptr) (void)hipHostFree(snap.report);
-    snap.metaDev = nullptr;
-    snap.dataDev = nullptr;
-    snap.report = nullptr;
-}
 
 bool isRenderOutput(const mwhip_exec *exec, uint32_t archetype, uint32_t component)
 {
@@ -402,15 +396,7 @@ int sizeSnapshot(mwhip_exec *exec, mwhip_snapshot_rec &snap)
 
 mwhip_snapshot_rec *findSnapshot(mwhip_exec *exec, uint64_t handle)
 {
-    if (exec == nullptr) return nullptr;
-    auto it = exec->snapshots.find(handle);
-    return it == exec->snapshots.end() ? nullptr : it->second;
-}
-
-int unknownSnapshot(uint64_t handle)
-{
-    return fail(-3, "snapshot %llu is not one of this executor's",
-                (unsigned long long)handle);
+    return findObject(exec != nullptr ? &exec->snapshots : nullptr, handle);
 }
 
 uint32_t snapGrid(const mwhip_exec *exec)
@@ -475,15 +461,20 @@ int queueRestore(mwhip_exec *exec, mwhip_snapshot_rec &snap)
     return 0;
 }
 
+
+int restoreSnapshot(mwhip_exec *exec, uint64_t snapshot, bool wait)
+{
+    mwhip_snapshot_rec *snap = findSnapshot(exec, snapshot);
+    if (snap == nullptr) return unknownObject("snapshot", snapshot);
+    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
+    if (wait) {
+        HIPCHK(hipStreamSynchronize(exec->stream));
+    }
+    int rc = restorable(*snap);
+    if (rc != 0) return rc;
+    return finishQueued(exec, queueRestore(exec, *snap), wait);
 }
 
-MWHIP_RT void freeSnapshots(mwhip_exec *exec)
-{
-    for (auto &kv : exec->snapshots) {
-        releaseSnapshot(*kv.second);
-        delete kv.second;
-    }
-    exec->snapshots.clear();
 }
 
 extern "C" int mwhip_snapshot_create(mwhip_exec *exec, uint64_t *snapshot_out)
@@ -493,87 +484,62 @@ extern "C" int mwhip_snapshot_create(mwhip_exec *exec, uint64_t *snapshot_out)
     }
     HIPCHK(hipSetDevice(exec->cfg.gpu_id));
     HIPCHK(hipStreamSynchronize(exec->stream));
+    // (a snapshot that is not finished frees what it has when it goes)
     std::unique_ptr<mwhip_snapshot_rec> snap(new mwhip_snapshot_rec {});
-    snap->handle = g_nextSnapshot.fetch_add(1);
     HIPCHK(hipHostMalloc((void **)&snap->report, sizeof(SnapReport), hipHostMallocMapped));
     memset(snap->report, 0, sizeof(SnapReport));
     if (hipHostGetDevicePointer((void **)&snap->reportDev, snap->report, 0) != hipSuccess) {
-        releaseSnapshot(*snap);
         return fail(-10, "snapshot_create: no device address for pinned memory");
     }
     int rc = sizeSnapshot(exec, *snap);
-    if (rc != 0) {
-        releaseSnapshot(*snap);
-        return rc;
-    }
-    // (the right side of an assignment is evaluated first: release() would
-    // leave nothing to read the handle from)
-    const uint64_t handle = snap->handle;
-    exec->snapshots[handle] = snap.release();
-    *snapshot_out = handle;
+    if (rc != 0) return rc;
+    *snapshot_out = exec->snapshots.insert(std::move(snap));
     return 0;
 }
 
 extern "C" void mwhip_snapshot_destroy(mwhip_exec *exec, uint64_t snapshot)
 {
-    mwhip_snapshot_rec *snap = findSnapshot(exec, snapshot);
-    if (snap == nullptr) return;
+    if (findSnapshot(exec, snapshot) == nullptr) return;
     (void)hipSetDevice(exec->cfg.gpu_id);
     (void)hipStreamSynchronize(exec->stream);
-    releaseSnapshot(*snap);
-    delete snap;
     exec->snapshots.erase(snapshot);
 }
 
 extern "C" int mwhip_snapshot_save(mwhip_exec *exec, uint64_t snapshot)
 {
     mwhip_snapshot_rec *snap = findSnapshot(exec, snapshot);
-    if (snap == nullptr) return unknownSnapshot(snapshot);
+    if (snap == nullptr) return unknownObject("snapshot", snapshot);
     HIPCHK(hipSetDevice(exec->cfg.gpu_id));
     // a replay boundary: every row there is lies in mapped memory, and the
     // snapshot gets room for all of that -- no high-water mark to keep
     HIPCHK(hipStreamSynchronize(exec->stream));
     int rc = sizeSnapshot(exec, *snap);
     if (rc != 0) return rc;
-    rc = queueSave(exec, *snap);
+    rc = finishQueued(exec, queueSave(exec, *snap), true);
     if (rc != 0) return rc;
-    HIPCHK(hipStreamSynchronize(exec->stream));
     if (snap->report->overflowed != 0u) {
         return fail(-4, "snapshot_save: a segment outgrew the memory mapped for it");
     }
     return 0;
 }
 
+// (into the room the snapshot has)
 extern "C" int mwhip_snapshot_save_async(mwhip_exec *exec, uint64_t snapshot)
 {
     mwhip_snapshot_rec *snap = findSnapshot(exec, snapshot);
-    if (snap == nullptr) return unknownSnapshot(snapshot);
+    if (snap == nullptr) return unknownObject("snapshot", snapshot);
     HIPCHK(hipSetDevice(exec->cfg.gpu_id));
     return queueSave(exec, *snap);
 }
 
 extern "C" int mwhip_snapshot_restore(mwhip_exec *exec, uint64_t snapshot)
 {
-    mwhip_snapshot_rec *snap = findSnapshot(exec, snapshot);
-    if (snap == nullptr) return unknownSnapshot(snapshot);
-    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
-    HIPCHK(hipStreamSynchronize(exec->stream));
-    int rc = restorable(*snap);
-    if (rc != 0) return rc;
-    rc = queueRestore(exec, *snap);
-    if (rc != 0) return rc;
-    HIPCHK(hipStreamSynchronize(exec->stream));
-    return 0;
+    return restoreSnapshot(exec, snapshot, true);
 }
 
 extern "C" int mwhip_snapshot_restore_async(mwhip_exec *exec, uint64_t snapshot)
 {
-    mwhip_snapshot_rec *snap = findSnapshot(exec, snapshot);
-    if (snap == nullptr) return unknownSnapshot(snapshot);
-    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
-    int rc = restorable(*snap);
-    if (rc != 0) return rc;
-    return queueRestore(exec, *snap);
+    return restoreSnapshot(exec, snapshot, false);
 }
 
 extern "C" uint64_t mwhip_snapshot_bytes(mwhip_exec *exec, uint64_t snapshot)
@@ -589,7 +555,7 @@ extern "C" int32_t mwhip_snapshot_segments(mwhip_exec *exec, uint64_t snapshot,
                                            mwhip_snapshot_segment *out, uint32_t max_out)
 {
     mwhip_snapshot_rec *snap = findSnapshot(exec, snapshot);
-    if (snap == nullptr) return unknownSnapshot(snapshot);
+    if (snap == nullptr) return unknownObject("snapshot", snapshot);
     if (snap->savesQueued == 0) return 0;
     HIPCHK(hipSetDevice(exec->cfg.gpu_id));
     HIPCHK(hipStreamSynchronize(exec->stream));

@@ -298,31 +298,19 @@ struct mwhip_view_rec {
     int32_t *countsDev = nullptr;
     ViewPlan *planDev = nullptr;
     char *bufDev = nullptr;     // the slabs (256-byte aligned each), then the counts
+
+    ~mwhip_view_rec()
+    {
+        if (planDev != nullptr) (void)hipFree(planDev);
+        if (bufDev != nullptr) (void)hipFree(bufDev);
+    }
 };
 
 namespace {
 
-// handles are unique in the process: one of another executor is never found
-std::atomic<uint64_t> g_nextView { 1 };
-
-void releaseView(mwhip_view_rec &view)
-{
-    if (view.planDev != nullptr) (void)hipFree(view.planDev);
-    if (view.bufDev != nullptr) (void)hipFree(view.bufDev);
-    view.planDev = nullptr;
-    view.bufDev = nullptr;
-}
-
 mwhip_view_rec *findView(mwhip_exec *exec, uint64_t handle)
 {
-    if (exec == nullptr) return nullptr;
-    auto it = exec->views.find(handle);
-    return it == exec->views.end() ? nullptr : it->second;
-}
-
-int unknownView(uint64_t handle)
-{
-    return fail(-3, "view %llu is not one of this executor's", (unsigned long long)handle);
+    return findObject(exec != nullptr ? &exec->views : nullptr, handle);
 }
 
 dim3 viewGrid(mwhip_exec *exec, uint32_t items)
@@ -343,26 +331,46 @@ int queueView(mwhip_exec *exec, mwhip_view_rec &view)
     return 0;
 }
 
+int computeView(mwhip_exec *exec, uint64_t handle, bool wait)
+{
+    mwhip_view_rec *view = findView(exec, handle);
+    if (view == nullptr) return unknownObject("view", handle);
+    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
+    return finishQueued(exec, queueView(exec, *view), wait);
 }
 
-MWHIP_RT void freeViews(mwhip_exec *exec)
+// Bytes the step views' last run read: the listed cells of the rows it copied
+// and the WorldID cells of the rows it counted (KernelLaunch::measuredBytes).
+int stepViewReadBytes(mwhip_exec *exec, double *out)
 {
-    for (auto &kv : exec->views) {
-        releaseView(*kv.second);
-        delete kv.second;
+    *out = 0;
+    std::vector<int32_t> counts;
+    for (uint64_t handle : exec->extras.stepViews) {
+        mwhip_view_rec *view = findView(exec, handle);
+        if (view == nullptr) continue;
+        counts.resize(view->numWorlds);
+        HIPCHK(hipMemcpy(counts.data(), view->countsDev, counts.size() * sizeof(int32_t),
+                         hipMemcpyDeviceToHost));
+        for (int32_t count : counts) {
+            const double rows = (double)std::max(count, 0);
+            *out += std::min(rows, (double)view->maxRows) * view->rowBytes + rows * 4.0;
+        }
     }
-    exec->views.clear();
-    exec->stepViews.clear();
+    return 0;
 }
 
-// The ONE launch that recomputes every step view inside a replay
-// (instantiateLaunchGraph); none when no step view is set.
-MWHIP_RT int stepViewLaunches(mwhip_exec *exec, std::vector<KernelLaunch> &out)
+}
+
+// Tail stage: the ONE launch that recomputes every step view inside a step
+// replay; none when no step view is set.
+MWHIP_RT int stepViewStage(mwhip_exec *exec, const LaunchGraph &lg,
+                           std::vector<KernelLaunch> &out)
 {
+    if (lg.isRender) return 0;
     ViewArgs args {};
     uint32_t items = 0;
     double written = 0;
-    for (uint64_t handle : exec->stepViews) {
+    for (uint64_t handle : exec->extras.stepViews) {
         mwhip_view_rec *view = findView(exec, handle);
         if (view == nullptr || args.numViews >= MWHIP_MAX_STEP_VIEWS) continue;
         args.items[args.numViews] = view->items;
@@ -382,28 +390,10 @@ MWHIP_RT int stepViewLaunches(mwhip_exec *exec, std::vector<KernelLaunch> &out)
     k.name = "view";
     k.role = "view";
     k.kind = MWHIP_NODE_RECYCLE;
-    k.fixedBytes = written;     // (mwhip_profile adds what was read: stepViewReadBytes)
+    k.fixedBytes = written;
+    // what the step views read: from the counts they just left
+    k.measuredBytes = &stepViewReadBytes;
     out.push_back(k);
-    return 0;
-}
-
-// Bytes the step views' last run read: the listed cells of the rows it copied
-// and the WorldID cells of the rows it counted (mwhip_profile).  Stream idle.
-MWHIP_RT int stepViewReadBytes(mwhip_exec *exec, double *out)
-{
-    *out = 0;
-    std::vector<int32_t> counts;
-    for (uint64_t handle : exec->stepViews) {
-        mwhip_view_rec *view = findView(exec, handle);
-        if (view == nullptr) continue;
-        counts.resize(view->numWorlds);
-        HIPCHK(hipMemcpy(counts.data(), view->countsDev, counts.size() * sizeof(int32_t),
-                         hipMemcpyDeviceToHost));
-        for (int32_t count : counts) {
-            const double rows = (double)std::max(count, 0);
-            *out += std::min(rows, (double)view->maxRows) * view->rowBytes + rows * 4.0;
-        }
-    }
     return 0;
 }
 
@@ -425,28 +415,16 @@ extern "C" int mwhip_view_create(mwhip_exec *exec, uint32_t archetype_id,
     if (max_rows == 0) {
         return fail(-2, "view_create: max_rows == 0");
     }
-    if (archetype_id >= exec->archetypes.size() || !exec->archetypes[archetype_id].registered) {
-        return fail(-2, "view_create: archetype %u is not registered", archetype_id);
-    }
-    const ArchetypeRec &arch = exec->archetypes[archetype_id];
-    std::vector<int> columns(n);
+    std::vector<mwhip_digest_column> listed(n);
     for (uint32_t p = 0; p < n; p++) {
-        columns[p] = findColumn(arch, component_ids[p]);
-        if (columns[p] < 0) {
-            return fail(-2, "view_create: column %u: archetype %u has no component %u",
-                        p, archetype_id, component_ids[p]);
-        }
-        for (uint32_t q = 0; q < p; q++) {
-            if (component_ids[q] == component_ids[p]) {
-                return fail(-2, "view_create: component %u is listed twice "
-                            "(positions %u and %u)", component_ids[p], q, p);
-            }
-        }
+        listed[p] = { archetype_id, component_ids[p] };
     }
+    std::vector<ResolvedColumn> columns;
+    int rc = resolveColumns(exec, "view_create", listed.data(), n, columns);
+    if (rc != 0) return rc;
 
     HIPCHK(hipSetDevice(exec->cfg.gpu_id));
     std::unique_ptr<mwhip_view_rec> view(new mwhip_view_rec {});
-    view->handle = g_nextView.fetch_add(1);
     view->numWorlds = exec->cfg.num_worlds;
     view->maxRows = max_rows;
     uint32_t team = 1;
@@ -458,7 +436,7 @@ extern "C" int mwhip_view_create(mwhip_exec *exec, uint32_t archetype_id,
     std::vector<uint64_t> offsets(n);
     uint64_t total = 0;
     for (uint32_t p = 0; p < n; p++) {
-        const uint32_t cell = arch.colBytes[(size_t)columns[p]];
+        const uint32_t cell = columns[p].cellBytes;
         view->cellBytes.push_back(cell);
         view->rowBytes += cell;
         offsets[p] = total;
@@ -468,93 +446,73 @@ extern "C" int mwhip_view_create(mwhip_exec *exec, uint32_t archetype_id,
     const uint64_t counts_at = total;
     total += ((uint64_t)view->numWorlds * sizeof(int32_t) + 255ull) & ~255ull;
 
-    if (hipMalloc((void **)&view->bufDev, total) != hipSuccess ||
-            hipMalloc((void **)&view->planDev, sizeof(ViewPlan)) != hipSuccess ||
-            hipMemset(view->bufDev, 0, total) != hipSuccess) {
-        (void)hipGetLastError();    // (not left for the next launch check to find)
-        releaseView(*view);
-        return fail(-10, "view_create: no device memory for %llu bytes (%u worlds x %u rows "
-                    "x %u bytes)", (unsigned long long)total, view->numWorlds, max_rows,
-                    view->rowBytes);
+    bool ok = hipMalloc((void **)&view->bufDev, total) == hipSuccess &&
+        hipMalloc((void **)&view->planDev, sizeof(ViewPlan)) == hipSuccess &&
+        hipMemset(view->bufDev, 0, total) == hipSuccess;
+    if (ok) {
+        view->countsDev = (int32_t *)(view->bufDev + counts_at);
+        ViewPlan plan {};
+        plan.hdr = exec->hostState.tables + archetype_id;   // (a device address: never read here)
+        plan.counts = view->countsDev;
+        plan.numWorlds = view->numWorlds;
+        plan.maxRows = max_rows;
+        plan.numColumns = n;
+        plan.teamLanes = team;
+        for (uint32_t p = 0; p < n; p++) {
+            view->slabs.push_back(view->bufDev + offsets[p]);
+            plan.columns[p] = { columns[p].slot, view->slabs[p], view->cellBytes[p], 0u };
+        }
+        ok = hipMemcpy(view->planDev, &plan, sizeof(plan), hipMemcpyHostToDevice) == hipSuccess;
     }
-    view->countsDev = (int32_t *)(view->bufDev + counts_at);
-
-    ViewPlan plan {};
-    TableHdr *hdr = exec->hostState.tables + archetype_id;  // (a device address: never read here)
-    plan.hdr = hdr;
-    plan.counts = view->countsDev;
-    plan.numWorlds = view->numWorlds;
-    plan.maxRows = max_rows;
-    plan.numColumns = n;
-    plan.teamLanes = team;
-    for (uint32_t p = 0; p < n; p++) {
-        view->slabs.push_back(view->bufDev + offsets[p]);
-        plan.columns[p] = { &hdr->columns[columns[p]], view->slabs[p], view->cellBytes[p], 0u };
+    if (!ok) {
+        return CREATE_FAILED(view, "view_create: no device memory for the plan and %llu "
+                             "bytes (%u worlds x %u rows)", (unsigned long long)total,
+                             exec->cfg.num_worlds, max_rows);
     }
-    if (hipMemcpy(view->planDev, &plan, sizeof(plan), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipGetLastError();
-        releaseView(*view);
-        return fail(-10, "view_create: the plan could not be copied to the device");
-    }
-    const uint64_t handle = view->handle;
-    exec->views[handle] = view.release();
-    *view_out = handle;
+    *view_out = exec->views.insert(std::move(view));
     return 0;
 }
 
 extern "C" int mwhip_set_step_view(mwhip_exec *exec, uint64_t view, int on)
 {
-    if (findView(exec, view) == nullptr) return unknownView(view);
-    std::vector<uint64_t> &step_views = exec->stepViews;
-    const auto at = std::find(step_views.begin(), step_views.end(), view);
-    if ((at != step_views.end()) == (on != 0)) return 0;
+    if (findView(exec, view) == nullptr) return unknownObject("view", view);
+    const std::vector<uint64_t> &step_views = exec->extras.stepViews;
+    const bool is_on = std::find(step_views.begin(), step_views.end(), view) != step_views.end();
+    if (is_on == (on != 0)) return 0;
     if (on != 0 && step_views.size() >= MWHIP_MAX_STEP_VIEWS) {
         return fail(-2, "set_step_view: %u step views are set already (at most %u)",
                     (uint32_t)step_views.size(), (uint32_t)MWHIP_MAX_STEP_VIEWS);
     }
-    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
-    HIPCHK(hipStreamSynchronize(exec->stream));
-    const std::vector<uint64_t> before = step_views;
-    if (on != 0) {
-        step_views.push_back(view);
-    } else {
-        step_views.erase(at);
-    }
-    int rc = rebuildAllLaunchGraphs(exec);
-    if (rc != 0) exec->stepViews = before;
-    return rc;
+    return changeReplayExtras(exec, [view, on](ReplayExtras &extras) {
+        std::vector<uint64_t> &views = extras.stepViews;
+        if (on != 0) {
+            views.push_back(view);
+        } else {
+            views.erase(std::find(views.begin(), views.end(), view));
+        }
+        return 0;
+    });
 }
 
 extern "C" void mwhip_view_destroy(mwhip_exec *exec, uint64_t handle)
 {
-    mwhip_view_rec *view = findView(exec, handle);
-    if (view == nullptr) return;
+    if (findView(exec, handle) == nullptr) return;
     (void)hipSetDevice(exec->cfg.gpu_id);
-    // (the step graphs must stop naming its buffers before they go)
-    (void)mwhip_set_step_view(exec, handle, 0);
+    // (the step graphs must stop naming its buffers before they go; if they
+    // could not be rebuilt without it, it stays until mwhip_destroy)
+    if (mwhip_set_step_view(exec, handle, 0) != 0) return;
     (void)hipStreamSynchronize(exec->stream);
-    releaseView(*view);
-    delete view;
     exec->views.erase(handle);
 }
 
 extern "C" int mwhip_view_compute(mwhip_exec *exec, uint64_t handle)
 {
-    mwhip_view_rec *view = findView(exec, handle);
-    if (view == nullptr) return unknownView(handle);
-    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
-    int rc = queueView(exec, *view);
-    if (rc != 0) return rc;
-    HIPCHK(hipStreamSynchronize(exec->stream));
-    return 0;
+    return computeView(exec, handle, true);
 }
 
 extern "C" int mwhip_view_compute_async(mwhip_exec *exec, uint64_t handle)
 {
-    mwhip_view_rec *view = findView(exec, handle);
-    if (view == nullptr) return unknownView(handle);
-    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
-    return queueView(exec, *view);
+    return computeView(exec, handle, false);
 }
 
 extern "C" void *mwhip_view_buffer(mwhip_exec *exec, uint64_t handle, uint32_t column,
@@ -562,7 +520,7 @@ extern "C" void *mwhip_view_buffer(mwhip_exec *exec, uint64_t handle, uint32_t c
 {
     mwhip_view_rec *view = findView(exec, handle);
     if (view == nullptr) {
-        (void)unknownView(handle);
+        (void)unknownObject("view", handle);
         return nullptr;
     }
     if (column >= view->slabs.size()) {
@@ -580,7 +538,7 @@ extern "C" int32_t *mwhip_view_counts(mwhip_exec *exec, uint64_t handle)
 {
     mwhip_view_rec *view = findView(exec, handle);
     if (view == nullptr) {
-        (void)unknownView(handle);
+        (void)unknownObject("view", handle);
         return nullptr;
     }
     return view->countsDev;

@@ -174,6 +174,76 @@ private:
 friend class MWCudaExecutor;
 };
 
+namespace detail {
+
+// What MWHipSnapshot, MWHipDigest and MWHipWorldView share: the move-only handle
+// of an object that belongs to an executor (mwhip_<kind>_create / _destroy,
+// include/mwhip.h).  Kind: { name, destroy(exec, handle) }.
+template <typename Kind>
+class ExecObject {
+public:
+    ExecObject() : exec_(nullptr), handle_(0) {}
+    ExecObject(const ExecObject &) = delete;
+    ExecObject(ExecObject &&o) : exec_(o.exec_), handle_(o.handle_)
+    {
+        o.exec_ = nullptr;
+        o.handle_ = 0;
+    }
+
+    ~ExecObject()
+    {
+        if (exec_ != nullptr) {
+            Kind::destroy(exec_, handle_);
+        }
+    }
+
+    ExecObject &operator=(ExecObject &&o)
+    {
+        if (this != &o) {
+            if (exec_ != nullptr) {
+                Kind::destroy(exec_, handle_);
+            }
+            exec_ = o.exec_;
+            handle_ = o.handle_;
+            o.exec_ = nullptr;
+            o.handle_ = 0;
+        }
+        return *this;
+    }
+
+    uint64_t handle() const { return handle_; }
+
+protected:
+    ExecObject(mwhip_exec *exec, uint64_t handle) : exec_(exec), handle_(handle) {}
+
+    static void req(int rc, const char *what)
+    {
+        if (rc != 0) {
+            fprintf(stderr, "madrona_amd: %s %s failed (%d): %s\n", Kind::name, what, rc,
+                    mwhip_last_error());
+            abort();
+        }
+    }
+
+    mwhip_exec *exec_;
+    uint64_t handle_;
+};
+
+struct SnapshotKind {
+    static constexpr const char *name = "snapshot";
+    static void destroy(mwhip_exec *exec, uint64_t handle) { mwhip_snapshot_destroy(exec, handle); }
+};
+struct DigestKind {
+    static constexpr const char *name = "digest";
+    static void destroy(mwhip_exec *exec, uint64_t handle) { mwhip_digest_destroy(exec, handle); }
+};
+struct WorldViewKind {
+    static constexpr const char *name = "world view";
+    static void destroy(mwhip_exec *exec, uint64_t handle) { mwhip_view_destroy(exec, handle); }
+};
+
+}
+
 // Everything a batch of worlds is -- tables, entity store, per-world data, the
 // persistent region -- saved in device memory and put back, any number of times
 // (mwhip_snapshot_*, include/mwhip.h).  An extension of this backend: the
@@ -181,67 +251,24 @@ friend class MWCudaExecutor;
 // replay count (and the slot position of the input and output rings with it) and the ray
 // caster's output columns, which keep their contents until the next render
 // pass.  Belongs to the executor that made it and must not outlive it.
-class MWHipSnapshot {
+class MWHipSnapshot : public detail::ExecObject<detail::SnapshotKind> {
 public:
-    MWHipSnapshot() : exec_(nullptr), snapshot_(0) {}
-    MWHipSnapshot(const MWHipSnapshot &) = delete;
-    MWHipSnapshot(MWHipSnapshot &&o) : exec_(o.exec_), snapshot_(o.snapshot_)
-    {
-        o.exec_ = nullptr;
-        o.snapshot_ = 0;
-    }
-
-    ~MWHipSnapshot()
-    {
-        if (exec_ != nullptr) {
-            mwhip_snapshot_destroy(exec_, snapshot_);
-        }
-    }
-
-    MWHipSnapshot &operator=(MWHipSnapshot &&o)
-    {
-        if (this != &o) {
-            if (exec_ != nullptr) {
-                mwhip_snapshot_destroy(exec_, snapshot_);
-            }
-            exec_ = o.exec_;
-            snapshot_ = o.snapshot_;
-            o.exec_ = nullptr;
-            o.snapshot_ = 0;
-        }
-        return *this;
-    }
+    MWHipSnapshot() = default;
 
     // wait for the executor's stream; save() makes room for every row mapped
-    void save() { req(mwhip_snapshot_save(exec_, snapshot_), "save"); }
-    void restore() { req(mwhip_snapshot_restore(exec_, snapshot_), "restore"); }
+    void save() { req(mwhip_snapshot_save(exec_, handle_), "save"); }
+    void restore() { req(mwhip_snapshot_restore(exec_, handle_), "restore"); }
     // queued on the executor's stream behind the replays queued so far
-    void saveAsync() { req(mwhip_snapshot_save_async(exec_, snapshot_), "saveAsync"); }
+    void saveAsync() { req(mwhip_snapshot_save_async(exec_, handle_), "saveAsync"); }
     void restoreAsync()
     {
-        req(mwhip_snapshot_restore_async(exec_, snapshot_), "restoreAsync");
+        req(mwhip_snapshot_restore_async(exec_, handle_), "restoreAsync");
     }
     // bytes the last save holds
-    uint64_t numBytes() const { return mwhip_snapshot_bytes(exec_, snapshot_); }
-
-    uint64_t handle() const { return snapshot_; }
+    uint64_t numBytes() const { return mwhip_snapshot_bytes(exec_, handle_); }
 
 private:
-    MWHipSnapshot(mwhip_exec *exec, uint64_t snapshot)
-        : exec_(exec), snapshot_(snapshot)
-    {}
-
-    static void req(int rc, const char *what)
-    {
-        if (rc != 0) {
-            fprintf(stderr, "madrona_amd: snapshot %s failed (%d): %s\n", what, rc,
-                    mwhip_last_error());
-            abort();
-        }
-    }
-
-    mwhip_exec *exec_;
-    uint64_t snapshot_;
+    MWHipSnapshot(mwhip_exec *exec, uint64_t snapshot) : ExecObject(exec, snapshot) {}
 
 friend class MWCudaExecutor;
 };
@@ -260,68 +287,25 @@ static_assert(sizeof(DigestColumn) == sizeof(mwhip_digest_column));
 // definition).  It is a hash of the multiset of each world's rows: blind to the
 // order of a world's rows, to where they sit and to other worlds.  An extension
 // of this backend.  Belongs to the executor that made it and must not outlive it.
-class MWHipDigest {
+class MWHipDigest : public detail::ExecObject<detail::DigestKind> {
 public:
-    MWHipDigest() : exec_(nullptr), digest_(0) {}
-    MWHipDigest(const MWHipDigest &) = delete;
-    MWHipDigest(MWHipDigest &&o) : exec_(o.exec_), digest_(o.digest_)
-    {
-        o.exec_ = nullptr;
-        o.digest_ = 0;
-    }
-
-    ~MWHipDigest()
-    {
-        if (exec_ != nullptr) {
-            mwhip_digest_destroy(exec_, digest_);
-        }
-    }
-
-    MWHipDigest &operator=(MWHipDigest &&o)
-    {
-        if (this != &o) {
-            if (exec_ != nullptr) {
-                mwhip_digest_destroy(exec_, digest_);
-            }
-            exec_ = o.exec_;
-            digest_ = o.digest_;
-            o.exec_ = nullptr;
-            o.digest_ = 0;
-        }
-        return *this;
-    }
+    MWHipDigest() = default;
 
     // waits for the executor's stream
-    void compute() { req(mwhip_digest_compute(exec_, digest_), "compute"); }
+    void compute() { req(mwhip_digest_compute(exec_, handle_), "compute"); }
     // queued on the executor's stream behind the replays queued so far
-    void computeAsync() { req(mwhip_digest_compute_async(exec_, digest_), "computeAsync"); }
+    void computeAsync() { req(mwhip_digest_compute_async(exec_, handle_), "computeAsync"); }
     // uint64 [numGroups()][worlds] on the device, owned by the executor
-    void *devicePtr() const { return mwhip_digest_buffer(exec_, digest_, nullptr, nullptr); }
+    void *devicePtr() const { return mwhip_digest_buffer(exec_, handle_, nullptr, nullptr); }
     uint32_t numGroups() const
     {
         uint32_t groups = 0;
-        (void)mwhip_digest_buffer(exec_, digest_, &groups, nullptr);
+        (void)mwhip_digest_buffer(exec_, handle_, &groups, nullptr);
         return groups;
     }
 
-    uint64_t handle() const { return digest_; }
-
 private:
-    MWHipDigest(mwhip_exec *exec, uint64_t digest)
-        : exec_(exec), digest_(digest)
-    {}
-
-    static void req(int rc, const char *what)
-    {
-        if (rc != 0) {
-            fprintf(stderr, "madrona_amd: digest %s failed (%d): %s\n", what, rc,
-                    mwhip_last_error());
-            abort();
-        }
-    }
-
-    mwhip_exec *exec_;
-    uint64_t digest_;
+    MWHipDigest(mwhip_exec *exec, uint64_t digest) : ExecObject(exec, digest) {}
 
 friend class MWCudaExecutor;
 };
@@ -332,44 +316,14 @@ friend class MWCudaExecutor;
 // kernel where the table is, sorted or not (mwhip_view_*, include/mwhip.h: the
 // exact definition).  An extension of this backend.  Belongs to the executor
 // that made it and must not outlive it.
-class MWHipWorldView {
+class MWHipWorldView : public detail::ExecObject<detail::WorldViewKind> {
 public:
-    MWHipWorldView() : exec_(nullptr), view_(0), max_rows_(0), gpu_id_(0) {}
-    MWHipWorldView(const MWHipWorldView &) = delete;
-    MWHipWorldView(MWHipWorldView &&o)
-        : exec_(o.exec_), view_(o.view_), max_rows_(o.max_rows_), gpu_id_(o.gpu_id_)
-    {
-        o.exec_ = nullptr;
-        o.view_ = 0;
-    }
-
-    ~MWHipWorldView()
-    {
-        if (exec_ != nullptr) {
-            mwhip_view_destroy(exec_, view_);
-        }
-    }
-
-    MWHipWorldView &operator=(MWHipWorldView &&o)
-    {
-        if (this != &o) {
-            if (exec_ != nullptr) {
-                mwhip_view_destroy(exec_, view_);
-            }
-            exec_ = o.exec_;
-            view_ = o.view_;
-            max_rows_ = o.max_rows_;
-            gpu_id_ = o.gpu_id_;
-            o.exec_ = nullptr;
-            o.view_ = 0;
-        }
-        return *this;
-    }
+    MWHipWorldView() : max_rows_(0), gpu_id_(0) {}
 
     // waits for the executor's stream
-    void compute() { req(mwhip_view_compute(exec_, view_), "compute"); }
+    void compute() { req(mwhip_view_compute(exec_, handle_), "compute"); }
     // queued on the executor's stream behind the replays queued so far
-    void computeAsync() { req(mwhip_view_compute_async(exec_, view_), "computeAsync"); }
+    void computeAsync() { req(mwhip_view_compute_async(exec_, handle_), "computeAsync"); }
 
     // uint8 [worlds][maxRows()][cell bytes] of listed column `column`
     // (position in the list given to makeWorldView), owned by the executor
@@ -377,7 +331,7 @@ public:
     {
         uint64_t bytes = 0;
         uint32_t cell = 0;
-        void *ptr = mwhip_view_buffer(exec_, view_, column, &bytes, &cell);
+        void *ptr = mwhip_view_buffer(exec_, handle_, column, &bytes, &cell);
         req(ptr != nullptr ? 0 : -1, "columnTensor");
         const int64_t dims[3] = { (int64_t)mwhip_num_worlds(exec_), (int64_t)max_rows_,
                                   (int64_t)cell };
@@ -388,7 +342,7 @@ public:
     // int32 [worlds]: each world's rows in the table (may exceed maxRows())
     py::Tensor countsTensor() const
     {
-        void *ptr = mwhip_view_counts(exec_, view_);
+        void *ptr = mwhip_view_counts(exec_, handle_);
         req(ptr != nullptr ? 0 : -1, "countsTensor");
         const int64_t dims[1] = { (int64_t)mwhip_num_worlds(exec_) };
         return py::Tensor(ptr, py::TensorElementType::Int32, Span<const int64_t>(dims, 1),
@@ -396,24 +350,12 @@ public:
     }
 
     uint32_t maxRows() const { return max_rows_; }
-    uint64_t handle() const { return view_; }
 
 private:
     MWHipWorldView(mwhip_exec *exec, uint64_t view, uint32_t max_rows, int32_t gpu_id)
-        : exec_(exec), view_(view), max_rows_(max_rows), gpu_id_(gpu_id)
+        : ExecObject(exec, view), max_rows_(max_rows), gpu_id_(gpu_id)
     {}
 
-    static void req(int rc, const char *what)
-    {
-        if (rc != 0) {
-            fprintf(stderr, "madrona_amd: world view %s failed (%d): %s\n", what, rc,
-                    mwhip_last_error());
-            abort();
-        }
-    }
-
-    mwhip_exec *exec_;
-    uint64_t view_;
     uint32_t max_rows_;
     int32_t gpu_id_;
 
@@ -722,7 +664,7 @@ public:
     // nodes and before its pack node and output rings; nullptr: none
     void setStepDigest(const MWHipDigest *digest)
     {
-        req(mwhip_set_step_digest(exec_, digest != nullptr ? digest->digest_ : 0),
+        req(mwhip_set_step_digest(exec_, digest != nullptr ? digest->handle() : 0),
             "setStepDigest");
     }
 
@@ -742,7 +684,7 @@ public:
     // MWHIP_MAX_STEP_VIEWS views, one launch for all); off: no longer
     void setStepView(const MWHipWorldView *view, bool on)
     {
-        req(mwhip_set_step_view(exec_, view != nullptr ? view->view_ : 0, on ? 1 : 0),
+        req(mwhip_set_step_view(exec_, view != nullptr ? view->handle() : 0, on ? 1 : 0),
             "setStepView");
     }
 

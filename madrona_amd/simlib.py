@@ -217,7 +217,60 @@ def runtime_lib() -> C.CDLL:
     return lib
 
 
-class Snapshot:
+class _Checked:
+    """A wrapper of executor calls that is closed like a file: _check() raises
+    with the runtime's message, `with` closes."""
+
+    _rt = None
+
+    def _check(self, rc: int, what: str) -> None:
+        if rc != 0:
+            raise RuntimeError(f"{what} -> {rc}: {self._rt.mwhip_last_error().decode()}")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class _ExecObject(_Checked):
+    """What Snapshot, StateDigest and WorldView are: something a simulator's
+    executor owns, named by `handle` there, kept in one of the simulator's
+    lists (`_list`) while it is open.  close() frees it and takes it off the
+    list (a snapshot too, which used to stay on it until the simulator closed); Simulator.close() frees the executor and orphans
+    what is left: close() then does nothing, anything else raises."""
+
+    _kind = "object"    # in messages
+    _destroy = ""       # the runtime's destroy call
+    _list = ""          # the simulator's list of the open ones
+    _sim = None
+    _exec = 0
+    handle = 0
+
+    def _live(self) -> int:
+        # (the executor pointer dies with the simulator: never passed on then)
+        if self._sim is None:
+            raise RuntimeError(f"this {self._kind} is closed (or its simulator is)")
+        return self.handle
+
+    def _orphan(self) -> None:
+        """Simulator.close(): the executor has freed (or is about to free) it."""
+        self.handle = 0
+        self._exec = 0
+        self._sim = None
+
+    def close(self) -> None:
+        if self._sim is not None:
+            if self.handle:
+                getattr(self._rt, self._destroy)(self._exec, self.handle)
+            open_ones = getattr(self._sim, self._list)
+            if self in open_ones:
+                open_ones.remove(self)
+        self._orphan()
+
+
+class Snapshot(_ExecObject):
     """One saved copy of all world state of a HIP-backend simulator, in device
     memory (mwhip_snapshot_*, include/mwhip.h): save() / restore() wait,
     save_async() / restore_async() are queued on the executor's stream behind
@@ -226,6 +279,8 @@ class Snapshot:
     those snapshots (their close() then does nothing, any other call raises).
     Not rewound: the executor's replay count (the input
     ring's slot position) and the rgb / depth outputs of the render pass."""
+
+    _kind, _destroy, _list = "snapshot", "mwhip_snapshot_destroy", "_snapshots"
 
     def __init__(self, sim: "Simulator"):
         self._rt = runtime_lib()
@@ -236,21 +291,7 @@ class Snapshot:
         self._check(self._rt.mwhip_snapshot_create(self._exec, C.byref(handle)),
                     "mwhip_snapshot_create")
         self.handle = int(handle.value)
-
-    def _check(self, rc: int, what: str) -> None:
-        if rc != 0:
-            raise RuntimeError(f"{what} -> {rc}: {self._rt.mwhip_last_error().decode()}")
-
-    def _live(self) -> int:
-        # (the executor pointer dies with the simulator: never passed on then)
-        if not self.handle:
-            raise RuntimeError("this snapshot is closed (or its simulator is)")
-        return self.handle
-
-    def _orphan(self) -> None:
-        """Simulator.close(): the executor has freed (or is about to free) it."""
-        self.handle = 0
-        self._exec = 0
+        self._sim = sim
 
     def save(self) -> None:
         self._check(self._rt.mwhip_snapshot_save(self._exec, self._live()),
@@ -273,23 +314,12 @@ class Snapshot:
         """Bytes the last save holds (waits for the executor's stream)."""
         return int(self._rt.mwhip_snapshot_bytes(self._exec, self._live()))
 
-    def close(self) -> None:
-        if self.handle:
-            self._rt.mwhip_snapshot_destroy(self._exec, self.handle)
-            self.handle = 0
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
 
 RING_ON_STEP = 0      # MWHIP_RING_ON_STEP
 RING_ON_RENDER = 1    # MWHIP_RING_ON_RENDER
 
 
-class Trajectory:
+class Trajectory(_Checked):
     """Exported tensors of a HIP-backend simulator recorded per step on the
     device (mwhip_set_output_ring, include/mwhip.h): traj[name] is a torch
     tensor [steps, *dims] of the tensor's dtype on the simulator's device, and
@@ -348,10 +378,6 @@ class Trajectory:
             self.close()
             raise
 
-    def _check(self, rc: int, what: str) -> None:
-        if rc != 0:
-            raise RuntimeError(f"{what} -> {rc}: {self._rt.mwhip_last_error().decode()}")
-
     def _orphan(self) -> None:
         """Simulator.close(): the executor (and its rings) is gone."""
         self._exec = 0
@@ -396,14 +422,8 @@ class Trajectory:
                 self._open_in.remove(self)
             self._open_in = None
 
-    def __enter__(self):
-        return self
 
-    def __exit__(self, *exc):
-        self.close()
-
-
-class StateDigest:
+class StateDigest(_ExecObject):
     """A 64-bit hash per world of a list of dump-list columns, one row of
     hashes per table the list names (madrona_amd/digest_ref.py is the exact
     definition; mwhip_digest_*, include/mwhip.h, computes it on the device).
@@ -419,6 +439,8 @@ class StateDigest:
     of a step graph recompute the digest (before its output rings: a ring over
     `buffer_ptr` records the digest of every step).  close() frees it;
     Simulator.close() orphans what is left."""
+
+    _kind, _destroy, _list = "digest", "mwhip_digest_destroy", "_digests"
 
     def __init__(self, sim: "Simulator", columns=None):
         names = [c[0] for c in sim._columns]
@@ -472,30 +494,21 @@ class StateDigest:
                         "mwhip_digest_group")
             self.groups.append(self._tables[tag.value])
 
-    def _check(self, rc: int, what: str) -> None:
-        if rc != 0:
-            raise RuntimeError(f"{what} -> {rc}: {self._rt.mwhip_last_error().decode()}")
-
     def _live(self) -> int:
-        if self._sim is None:
-            raise RuntimeError("this digest is closed (or its simulator is)")
+        handle = super()._live()
         if self._rt is None:
             raise RuntimeError("only compute() works on the reference backend: "
                                "this needs the HIP backend")
-        return self.handle
+        return handle
 
     def _orphan(self) -> None:
-        """Simulator.close(): the executor has freed (or is about to free) it."""
-        self.handle = 0
-        self._exec = 0
-        self._sim = None
+        super()._orphan()
         self._tensor = None
 
     def compute(self) -> np.ndarray:
         """uint64 [groups, worlds]; waits for the executor's stream."""
-        if self._sim is None:
-            raise RuntimeError("this digest is closed (or its simulator is)")
         if self._rt is None:
+            super()._live()
             sim = self._sim
             return digest_ref.digest_of_dump(
                 self._tables, [sim.dump_column(i) for i in self._indices], self.num_worlds)
@@ -539,22 +552,8 @@ class StateDigest:
         self._every_step = bool(on)
         # (the rebuilt graphs are looked up by the same handles)
 
-    def close(self) -> None:
-        if self._sim is not None:
-            if self.handle:
-                self._rt.mwhip_digest_destroy(self._exec, self.handle)
-            if self in self._sim._digests:
-                self._sim._digests.remove(self)
-        self._orphan()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
-class WorldView:
+class WorldView(_ExecObject):
     """A dense, zero-padded, world-major copy of columns of ONE table on the
     device: per column uint8 [worlds, max_rows, cell_bytes], plus int32 [worlds]
     row counts that are NOT clipped to max_rows (counts[w] > max_rows: rows were
@@ -567,6 +566,8 @@ class WorldView:
     recompute the view (before its output rings: a ring over buffer_ptr(name)
     records [K, worlds, max_rows, ...]).  close() frees it; Simulator.close()
     orphans what is left."""
+
+    _kind, _destroy, _list = "world view", "mwhip_view_destroy", "_views"
 
     def __init__(self, sim: "Simulator", table: str, columns, max_rows: int):
         names = [c[0] for c in sim._columns]
@@ -620,20 +621,8 @@ class WorldView:
             self._buffers[name] = (int(ptr), int(cell.value))
         self.counts_ptr = int(self._rt.mwhip_view_counts(self._exec, self.handle) or 0)
 
-    def _check(self, rc: int, what: str) -> None:
-        if rc != 0:
-            raise RuntimeError(f"{what} -> {rc}: {self._rt.mwhip_last_error().decode()}")
-
-    def _live(self) -> int:
-        if self._sim is None:
-            raise RuntimeError("this world view is closed (or its simulator is)")
-        return self.handle
-
     def _orphan(self) -> None:
-        """Simulator.close(): the executor has freed (or is about to free) it."""
-        self.handle = 0
-        self._exec = 0
-        self._sim = None
+        super()._orphan()
         self._tensors = {}
 
     def compute(self) -> "WorldView":
@@ -693,20 +682,6 @@ class WorldView:
                     "mwhip_set_step_view")
         self._every_step = bool(on)
 
-    def close(self) -> None:
-        if self._sim is not None:
-            if self.handle:
-                self._rt.mwhip_view_destroy(self._exec, self.handle)
-            if self in self._sim._views:
-                self._sim._views.remove(self)
-        self._orphan()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
 
 class Simulator:
     """One simulator instance behind the C API (either backend)."""
@@ -751,22 +726,13 @@ class Simulator:
     # -- lifecycle ---------------------------------------------------------
     def close(self) -> None:
         if self.handle:
-            # sim_destroy frees the executor and its snapshots with it
-            for snap in self._snapshots:
-                snap._orphan()
-            self._snapshots.clear()
-            # ... and forgets its output rings (the trajectories keep their tensors)
-            for traj in self._trajectories:
-                traj._orphan()
-            self._trajectories.clear()
-            # ... and frees its digests
-            for dig in self._digests:
-                dig._orphan()
-            self._digests.clear()
-            # ... and its world views
-            for view in self._views:
-                view._orphan()
-            self._views.clear()
+            # sim_destroy frees the executor and with it its snapshots, digests
+            # and world views, and forgets its output rings (the trajectories
+            # keep their tensors)
+            for open_ones in (self._snapshots, self._trajectories, self._digests, self._views):
+                for obj in open_ones:
+                    obj._orphan()
+                open_ones.clear()
             self.lib.sim_destroy(self.handle)
             self.handle = None
 

@@ -13,6 +13,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from madrona_amd import view_ref
 from madrona_amd.simlib import (RING_ON_RENDER, RING_ON_STEP, Simulator, hip_lib_path,
                                 runtime_lib)
 from madrona_amd.tensor import DeviceColumn
@@ -286,6 +287,60 @@ def test_all_rings_of_a_kind_share_one_launch(built):
         for i in range(16):
             assert _set_ring(rt, sim, lidar + 64 * i, 0, 0, 0) == 0
         assert _ring_kernels(sim) == []
+
+
+def test_the_tail_keeps_its_order_with_everything_set(built):
+    """A step digest, two step views and an output ring over one view's buffer
+    on one simulator: the tail of the step replay is digest, views, ring, in
+    that order and right in front of the health kernel; closing a digest and a
+    view while they are set takes exactly their launches out; the ring records
+    the view of the step it belongs to (view_ref over dump_all())."""
+    torch = _torch()
+    rt = runtime_lib()
+    W, M, K = 33, 40, 3
+    tail = ["digest:digest.zero", "digest:digest", "view:view", "ring:ring.out"]
+    with Simulator(hip_lib_path("sort_stress"), W, seed=7) as sim:
+        names = lambda: [k["name"] for k in sim.profile(reps=1)]   # noqa: E731
+        before = names()
+        assert not [n for n in before if n in tail]
+
+        dig = sim.digest()
+        vec = sim.world_view("Item", ["Item.Vec3"], max_rows=M)
+        tag = sim.world_view("Item", ["Item.Tag8"], max_rows=M)
+        ring = torch.zeros((K, W, M, 12), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        src = vec.buffer_ptr("Item.Vec3")
+        # (set in another order than the one they run in)
+        assert _set_ring(rt, sim, src, ring.data_ptr(), W * M * 12, K) == 0
+        tag.every_step()
+        dig.every_step()
+        vec.every_step()
+        during = names()
+        assert during[-5:-1] == tail, during[-6:]
+        assert during[:-5] + during[-1:] == before
+
+        # closed while set: their launches go, the rest keeps its order
+        dig.close()
+        tag.close()
+        after = names()
+        assert after[-3:-1] == ["view:view", "ring:ring.out"], after[-6:]
+        assert after[:-3] + after[-1:] == before
+
+        done = _recorded(rt, sim, src)
+        assert done == 2        # (the two profiled steps recorded like replays)
+        slots = []
+        for k in range(K):
+            sim.step(1)
+            rows, counts = sim.dump_all()["Item.Vec3"]
+            want, _ = view_ref.view_of_dump(rows, counts, W, M)
+            got = ring[(done + k) % K].cpu().numpy()
+            assert got.shape == want.shape and np.array_equal(got, want), ("step", k)
+            slots.append(got)
+        assert not np.array_equal(slots[0], slots[1]) and slots[0].any()
+
+        assert _set_ring(rt, sim, src, 0, 0, 0) == 0
+        vec.close()
+        assert names() == before
 
 
 # ---- 5. render rings ------------------------------------------------------------------

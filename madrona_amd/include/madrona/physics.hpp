@@ -174,20 +174,23 @@ MADRONA_HD inline void findEntitiesWithinAABB(Context &ctx, math::AABB aabb,
 // entity findEntitiesWithinAABB would report for which accept(entity) holds
 // (Entity::none() if there is none), found by the 64 lanes of the calling
 // wavefront together: a lane per BVH leaf answering for all boxes, instead of a
-// tree walk per box with a chain of dependent loads per hit.  Every lane calls
-// with the same boxes; `accept` is evaluated by different lanes for different
-// entities and must not have side effects; the queries see the state as it is
-// when the call is made.  For systems that run a wavefront per world
+// tree walk per box with a chain of dependent loads per hit.  LANES = 32: by
+// the 32 lanes of one half of a wavefront (threadIdx.x / 32 names the group,
+// CustomParallelForNode<..., 32, 1, ...>); the other half may be in the call
+// for another world with other boxes, or not in it at all.  Every lane of a
+// group calls with the same boxes; `accept` is evaluated by different lanes
+// for different entities and must not have side effects; the queries see the
+// state as it is when the call is made.  For systems that run a wavefront per world
 // (CustomParallelForNode<..., 64, 1, ...>), after setupBroadphaseTasks has
 // brought the leaves up to date with the poses (leaves are culled by their own
 // box, which then contains the body with 100 dt^2 to spare).
-template <int MAX_BOXES, typename Fn>
+template <int MAX_BOXES, int LANES = 64, typename Fn>
 MADRONA_DEVICE inline void findFirstEntitiesWithinAABBsWave(Context &ctx,
                                                             const math::AABB *boxes,
                                                             int32_t num_boxes,
                                                             Entity *out,
                                                             Fn &&accept);
-template <typename Fn>
+template <int LANES = 64, typename Fn>
 MADRONA_DEVICE inline Entity findFirstEntityWithinAABBWave(Context &ctx,
                                                            math::AABB aabb,
                                                            Fn &&accept);

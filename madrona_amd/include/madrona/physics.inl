@@ -1582,7 +1582,10 @@ __device__ inline void rebuildTreeStaged(broadphase::BVH &bvh, uint32_t lane,
 // (86 registers: five wavefronts per SIMD.  Capped at 64 for eight -- every world
 // resident at once -- it spills 26 dwords and takes 32.6 us instead of 21.4:
 // profiles/r06_refresh_variants.jsonl.  The node is bound by its scattered
-// bytes, not by wavefronts in flight.)
+// bytes, not by wavefronts in flight.  Two worlds per wavefront, a half each --
+// 4096 wavefronts -- took 3.2 and 1.6 us off the first two launches of a step
+// and added 1.6 to the one that rebuilds: 0.4 % of the step, inside the noise
+// of the headline, not kept)
 template <bool WithRebuild>
 __global__ void __launch_bounds__(64)
 bvhRefreshKernel(EcsState *S, void *, uint32_t, uint32_t)
@@ -1897,15 +1900,22 @@ MADRONA_DEVICE inline uint32_t checkEntityAABBsOverlap(Context &ctx,
     return result;
 }
 
-template <int MAX_BOXES, typename Fn>
+template <int MAX_BOXES, int LANES, typename Fn>
 MADRONA_DEVICE inline void findFirstEntitiesWithinAABBsWave(Context &ctx,
                                                             const math::AABB *boxes,
                                                             int32_t num_boxes,
                                                             Entity *out,
                                                             Fn &&accept)
 {
+    static_assert(LANES == 32 || LANES == 64);
     const broadphase::BVH &bvh = ctx.singleton<broadphase::BVH>();
-    const uint32_t lane = threadIdx.x % 64u;
+    const uint32_t lane = threadIdx.x % (uint32_t)LANES;
+    // (LANES == 32: the first lane of this half of the wavefront; the other
+    // half answers for another world, with other boxes, or is not here at all
+    // -- every ballot below is cut down to this group, every shuffle reads a
+    // lane of this group)
+    const int group_first = LANES == 64 ? 0 :
+        (int)(kernels::wave::laneID() & ~(uint32_t)(LANES - 1));
     for (int32_t b = 0; b < num_boxes; b++) {
         out[b] = Entity::none();
     }
@@ -1924,8 +1934,9 @@ MADRONA_DEVICE inline void findFirstEntitiesWithinAABBsWave(Context &ctx,
                     }
                 });
             }
-            out[b] = Entity { (uint32_t)__shfl((int32_t)found.gen, 0, 64),
-                              __shfl(found.id, 0, 64) };
+            out[b] = Entity {
+                (uint32_t)__shfl((int32_t)found.gen, group_first, 64),
+                __shfl(found.id, group_first, 64) };
         }
         return;
     }
@@ -1938,7 +1949,7 @@ MADRONA_DEVICE inline void findFirstEntitiesWithinAABBsWave(Context &ctx,
     const int32_t n = bvh.numLeaves();
     const int32_t *order = bvh.traversalOrder();
     uint32_t open = num_boxes >= 32 ? 0xFFFFFFFFu : (1u << num_boxes) - 1u;
-    for (int32_t base = 0; base < n && open != 0u; base += 64) {
+    for (int32_t base = 0; base < n && open != 0u; base += LANES) {
         const int32_t i = base + (int32_t)lane;
         Entity e = Entity::none();
         uint32_t hits = 0;
@@ -1969,9 +1980,10 @@ MADRONA_DEVICE inline void findFirstEntitiesWithinAABBsWave(Context &ctx,
             if ((open >> b & 1u) == 0u) {
                 continue;
             }
-            const unsigned long long mask = __ballot((hits >> b & 1u) != 0u);
+            const unsigned long long mask =
+                kernels::wave::groupBallot<LANES>((hits >> b & 1u) != 0u);
             if (mask != 0ull) {
-                const int first = __builtin_ctzll(mask);
+                const int first = group_first + __builtin_ctzll(mask);
                 out[b] = Entity { (uint32_t)__shfl((int32_t)e.gen, first, 64),
                                   __shfl(e.id, first, 64) };
                 open &= ~(1u << b);
@@ -1980,14 +1992,14 @@ MADRONA_DEVICE inline void findFirstEntitiesWithinAABBsWave(Context &ctx,
     }
 }
 
-template <typename Fn>
+template <int LANES, typename Fn>
 MADRONA_DEVICE inline Entity findFirstEntityWithinAABBWave(Context &ctx,
                                                            math::AABB aabb,
                                                            Fn &&accept)
 {
     Entity found;
-    findFirstEntitiesWithinAABBsWave<1>(ctx, &aabb, 1, &found,
-                                        std::forward<Fn>(accept));
+    findFirstEntitiesWithinAABBsWave<1, LANES>(ctx, &aabb, 1, &found,
+                                               std::forward<Fn>(accept));
     return found;
 }
 #endif

@@ -53,3 +53,7 @@ if __name__ == "__main__":
             rec.update(label=v["label"], build=v.get("build", "_build"),
                        env=v.get("env", {}), repeat=rep)
             print(json.dumps(rec), flush=True)
+            if "error" in rec:
+                # (nothing more is started on a GPU that a variant may have
+                # faulted or hung)
+                sys.exit(1)

@@ -455,12 +455,20 @@ ESCPHYS_COLD static void releaseGrab(Engine &ctx, Entity held, GrabState &grab)
 }
 
 #ifdef SIM_WAVE_API
-// The GPU graph splits the grab in two.  This node runs a wavefront per world
-// (CustomParallelForNode<..., 64, 1, ...>): the box queries of all agents that
-// reach for something, a lane per BVH leaf (grabbing moves no body, so the
-// queries see what the CPU's sequential loop sees).  grabSystem then runs one
-// lane per world and only creates / destroys joints: lanes of a wavefront that
-// append to one table share one atomic, waves of their own would queue on it.
+// Lanes per world of the grab queries: 32 = two worlds per wavefront (a world
+// has 28 leaves; half as many wavefronts, all on the chip at once: 43.2 ->
+// 25.4 us at 8192 worlds, profiles/r07_two_worlds_variants.jsonl), 64 = one.
+#ifndef ESCPHYS_GRAB_QUERY_LANES
+#define ESCPHYS_GRAB_QUERY_LANES 32
+#endif
+
+// The GPU graph splits the grab in two.  This node runs half a wavefront per
+// world (CustomParallelForNode<..., ESCPHYS_GRAB_QUERY_LANES, 1, ...>): the box
+// queries of all agents that reach for something, a lane per BVH leaf (grabbing
+// moves no body, so the queries see what the CPU's sequential loop sees).
+// grabSystem then runs one lane per world and only creates / destroys joints:
+// lanes of a wavefront that append to one table share one atomic, waves of
+// their own would queue on it.
 inline void grabQuerySystem(Engine &ctx, LevelState &)
 {
     Sim &sim = ctx.data();
@@ -483,11 +491,12 @@ inline void grabQuerySystem(Engine &ctx, LevelState &)
         owner[num_boxes++] = i;
     }
     Entity first[consts::numAgents];
-    PhysicsSystem::findFirstEntitiesWithinAABBsWave<consts::numAgents>(
+    PhysicsSystem::findFirstEntitiesWithinAABBsWave<consts::numAgents,
+                                                    ESCPHYS_GRAB_QUERY_LANES>(
         ctx, boxes, num_boxes, first, [&](Entity other) {
             return ctx.get<EntityType>(other) == EntityType::Cube;
         });
-    if (threadIdx.x % 64 == 0) {
+    if (threadIdx.x % ESCPHYS_GRAB_QUERY_LANES == 0) {
         for (int32_t i = 0; i < consts::numAgents; i++) {
             sim.grabTargets[i] = Entity::none();
         }
@@ -1306,9 +1315,9 @@ void Sim::setupTasks(TaskGraphManager &taskgraph_mgr, const Config &)
         PhysicsSystem::setupBroadphaseTasks(builder, {move_sys});
 
 #ifdef SIM_WAVE_API
-    // 64 lanes per world: the grab queries test a BVH leaf per lane
+    // the grab queries test a BVH leaf per lane
     auto grab_query_sys = builder.addToGraph<CustomParallelForNode<Engine,
-        grabQuerySystem, 64, 1,
+        grabQuerySystem, ESCPHYS_GRAB_QUERY_LANES, 1,
             LevelState
         >>({broadphase_setup_sys});
 #else

@@ -388,6 +388,13 @@ inline void movementSystem(Engine &,
     external_torque = Vector3 { 0.f, 0.f, t_z };
 }
 
+// (this backend) lanes per world of the lock system's box queries: 32 = two
+// worlds per wavefront (a world has 29 leaves; 94 -> 55.5 us at 8192 worlds,
+// profiles/r07_two_worlds_variants.jsonl), 64 = one
+#ifndef HIDESEEK_LOCK_LANES
+#define HIDESEEK_LOCK_LANES 32
+#endif
+
 // Lock / unlock the movable object in front of each agent: a locked object is
 // a Static body until a member of the locking team releases it.  One
 // invocation per world, agents in order, so the outcome does not depend on how
@@ -397,10 +404,11 @@ inline void lockSystem(Engine &ctx, LevelState &)
     Sim &sim = ctx.data();
 
 #ifdef SIM_WAVE_API
-    // 64 lanes per world (CustomParallelForNode<..., 64, 1, ...>).  First the
+    // HIDESEEK_LOCK_LANES lanes per world (CustomParallelForNode<...,
+    // HIDESEEK_LOCK_LANES, 1, ...>; 32 = two worlds per wavefront).  First the
     // box queries of all agents that press the lock button, a lane per BVH leaf
     // (locking moves nothing, so they see what the sequential loop sees); then
-    // lane 0 toggles the locks agent by agent, in the CPU's order.
+    // the group's lane 0 toggles the locks agent by agent, in the CPU's order.
     Entity found[consts::numAgents];
     {
         AABB boxes[consts::numAgents];
@@ -421,7 +429,8 @@ inline void lockSystem(Engine &ctx, LevelState &)
             owner[num_boxes++] = i;
         }
         Entity first[consts::numAgents];
-        PhysicsSystem::findFirstEntitiesWithinAABBsWave<consts::numAgents>(
+        PhysicsSystem::findFirstEntitiesWithinAABBsWave<consts::numAgents,
+                                                        HIDESEEK_LOCK_LANES>(
             ctx, boxes, num_boxes, first, [&](Entity other) {
                 EntityType type = ctx.get<EntityType>(other);
                 return type == EntityType::Box || type == EntityType::Ramp;
@@ -430,7 +439,7 @@ inline void lockSystem(Engine &ctx, LevelState &)
             found[owner[b]] = first[b];
         }
     }
-    if (threadIdx.x % 64 != 0) {
+    if (threadIdx.x % HIDESEEK_LOCK_LANES != 0) {
         return;
     }
 #endif
@@ -994,9 +1003,9 @@ void Sim::setupTasks(TaskGraphManager &taskgraph_mgr, const Config &)
         PhysicsSystem::setupBroadphaseTasks(builder, {move_sys});
 
 #ifdef SIM_WAVE_API
-    // 64 lanes per world: the lock queries test a BVH leaf per lane
+    // the lock queries test a BVH leaf per lane
     auto lock_sys = builder.addToGraph<CustomParallelForNode<Engine,
-        lockSystem, 64, 1,
+        lockSystem, HIDESEEK_LOCK_LANES, 1,
 #else
     auto lock_sys = builder.addToGraph<ParallelForNode<Engine,
         lockSystem,

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded() and mwhip_digest_*() / mwhip_set_step_digest() (a per-world hash of chosen columns computed on the device) and mwhip_view_*() / mwhip_set_step_view() (padded per-world tensors of a table's columns); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
+#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded() and mwhip_digest_*() / mwhip_set_step_digest() (a per-world hash of chosen columns computed on the device) and mwhip_view_*() / mwhip_set_step_view() (padded per-world tensors of a table's columns) and mwhip_write_*() / mwhip_set_step_write() (padded per-world tensors scattered into a table's columns); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
 
 typedef struct mwhip_exec mwhip_exec; /* opaque; == MWCudaExecutor::Impl */
 
@@ -752,6 +752,84 @@ void *mwhip_view_buffer(mwhip_exec *exec, uint64_t view, uint32_t column,
                         uint64_t *bytes_out, uint32_t *cell_bytes_out);
 int32_t *mwhip_view_counts(mwhip_exec *exec, uint64_t view);
 int mwhip_set_step_view(mwhip_exec *exec, uint64_t view, int on);
+
+/* World writes (added under ABI 9): the inverse of a world view.  Padded
+ * per-world tensors are scattered into the rows of chosen columns of ONE table
+ * by one kernel where the table is (madrona_amd/write_ref.py is
+ * the same definition in numpy).  A write names one archetype a, an ordered
+ * list of n of its components -- NOT Entity (component 0) or WorldID
+ * (component 1) -- and max_rows >= 1, and owns, with W = the executor's number
+ * of worlds,
+ *   in_c   (in)  uint8 [W][max_rows][cell_bytes] per listed column c, 256-byte
+ *                aligned: exactly the layout of a world view made with the same
+ *                columns and max_rows, so what a view produced can be copied in
+ *                tensor for tensor; the caller fills them;
+ *   take   (in)  int32 [W]: how many leading rows of each world to write;
+ *   count  (out) int32 [W]: each world's rows in the table, not clipped.
+ * All of them are zero at creation: an apply before anything is filled writes
+ * nothing.  An apply reads the table's row count and column addresses on the
+ * device at the time the kernel runs and does, for every world w:
+ *   count[w] = the rows r < numRows of the table whose WorldID cell equals w;
+ *   k = min(max(take[w], 0), count[w], max_rows);
+ *   for j < k, the listed cells of the j-th such row in table order (ascending
+ *   r) become in_c[w][j].
+ * Every other byte of the table is unchanged: rows of w from k on, rows
+ * destroyed in place (WorldID < 0), unlisted columns, the Entity and WorldID
+ * columns, the table header (numRows, needsSort, sortedRows, the world ranges).
+ * in_c and take are not modified.  As for views, the result does not depend on
+ * which side of a column's twin buffers is current, on whether worldOffsets /
+ * worldCounts are current, or on whether the table has a sorted prefix, holes
+ * in it, rows appended behind it, or was last sorted by another key: a row is
+ * found by its own WorldID cell.  What a simulator derives from a written
+ * component (a rigid body's broadphase leaf from its pose, say) is the
+ * simulator's business, exactly as if one of its own systems had written the
+ * component: it follows when the system that derives it next runs.  Filling
+ * the buffers (from another stream, say) is ordered against an apply by the
+ * caller, as for exported action tensors.  The asynchronous form is
+ * stream-ordered behind the replays queued before it, and a write made before a
+ * table grew stays valid.
+ *
+ * mwhip_write_buffer: device address of in_c of listed column `column`
+ * (position in the list), owned by the executor and valid until the write is
+ * destroyed; NULL for an unknown handle or a column index out of range.
+ * mwhip_write_take / mwhip_write_counts: take and count, likewise.
+ * mwhip_set_step_write(on != 0): every replay of every STEP graph of the
+ * executor (packed ones included; render graphs are untouched) applies the
+ * write directly behind its input-ring launches and in front of its first
+ * task-graph node -- an input ring whose dst is mwhip_write_buffer() or
+ * mwhip_write_take() so feeds the injection of the same replay, and K queued
+ * steps carry K different injections with nothing but graph launches on the
+ * stream.  Up to MWHIP_MAX_STEP_WRITES step writes, ONE launch for all of them;
+ * mwhip_profile lists it with name and role "write", algo_bytes = rows written
+ * x listed row bytes x 2 (read from the slab, written to the table) + 4 bytes
+ * per WorldID cell counted, worked out after the run from take and count.
+ * on == 0 takes it out again.  The set lives in the executor, not in a graph:
+ * changing it waits for the stream and rebuilds the launch graphs (handles stay
+ * valid; rebuilds on table growth keep it).  Destroying a step write unsets it.
+ * Snapshots do not save a write's buffers.  Handles are unique in the process;
+ * mwhip_destroy frees what is left.
+ * Errors (non-zero, text in mwhip_last_error(), nothing changed or allocated):
+ * an unknown handle or one of another executor ("write N is not one of this
+ * executor's"; looked up first, so also with a null executor), n == 0 or
+ * n > MWHIP_WRITE_MAX_COLUMNS, max_rows == 0, an archetype that is not
+ * registered, a component the archetype does not have, a component listed
+ * twice, the Entity or the WorldID column listed, a ninth step write, buffers
+ * that cannot be allocated.
+ * (No reference counterpart.) */
+#define MWHIP_WRITE_MAX_COLUMNS 32
+#define MWHIP_MAX_STEP_WRITES 8
+int mwhip_write_create(mwhip_exec *exec, uint32_t archetype_id, const uint32_t *component_ids,
+                       uint32_t n, uint32_t max_rows, uint64_t *write_out);
+void mwhip_write_destroy(mwhip_exec *exec, uint64_t write);
+/* waits for the executor's stream */
+int mwhip_write_apply(mwhip_exec *exec, uint64_t write);
+/* queued on the executor's stream behind the replays queued so far */
+int mwhip_write_apply_async(mwhip_exec *exec, uint64_t write);
+void *mwhip_write_buffer(mwhip_exec *exec, uint64_t write, uint32_t column,
+                         uint64_t *bytes_out, uint32_t *cell_bytes_out);
+int32_t *mwhip_write_take(mwhip_exec *exec, uint64_t write);
+int32_t *mwhip_write_counts(mwhip_exec *exec, uint64_t write);
+int mwhip_set_step_write(mwhip_exec *exec, uint64_t write, int on);
 
 #ifdef __cplusplus
 }

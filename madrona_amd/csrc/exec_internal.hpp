@@ -4,7 +4,8 @@
 // runtime_kernels.hip: the runtime's own small kernels; output_ring.hip: the
 // output rings; snapshot.hip: saving and restoring all world state; digest.hip:
 // per-world state digests; world_view.hip: padded per-world views of a table's
-// columns).  Not installed.
+// columns; world_write.hip: the same tensors scattered into a table's columns).
+// Not installed.
 #pragma once
 #include "runtime_internal.hpp"
 #include <madrona/tracing.hpp>
@@ -246,9 +247,10 @@ extern MWHIP_RT __thread std::vector<void *> *t_allocScope;   // (runtime_state.
 struct mwhip_snapshot_rec;      // (snapshot.hip)
 struct mwhip_digest_rec;        // (digest.hip)
 struct mwhip_view_rec;          // (world_view.hip)
+struct mwhip_write_rec;         // (world_write.hip)
 
 // What a replay carries besides its task graphs.  Every launch graph is built
-// from it (the input rings open a step graph, the rest are tail stages:
+// from it (the input rings and the step writes open a step graph, the rest are tail stages:
 // instantiateLaunchGraph), so it changes only through changeReplayExtras.
 struct ReplayExtras {
     // mwhip_set_input_ring
@@ -276,6 +278,9 @@ struct ReplayExtras {
     uint64_t stepDigest = 0;
     // mwhip_set_step_view: those every step replay recomputes, in one launch
     std::vector<uint64_t> stepViews;
+    // mwhip_set_step_write: those every step replay applies, in one launch
+    // behind the input rings
+    std::vector<uint64_t> stepWrites;
 };
 
 struct mwhip_exec {
@@ -370,10 +375,12 @@ struct mwhip_exec {
     PreparedInstance *preparedInstances = nullptr;
 
     // executor objects by handle (exec_objects.hpp): mwhip_snapshot_create,
-    // mwhip_digest_create, mwhip_view_create; what is left goes with the executor
+    // mwhip_digest_create, mwhip_view_create, mwhip_write_create; what is left goes
+    // with the executor
     ExecObjectTable<mwhip_snapshot_rec> snapshots;
     ExecObjectTable<mwhip_digest_rec> digests;
     ExecObjectTable<mwhip_view_rec> views;
+    ExecObjectTable<mwhip_write_rec> writes;
 };
 
 // ---- functions one translation unit defines and another calls ----------------------
@@ -430,6 +437,11 @@ MWHIP_RT int stepDigestStage(mwhip_exec *exec, const LaunchGraph &lg,
 MWHIP_RT int stepViewStage(mwhip_exec *exec, const LaunchGraph &lg,
                            std::vector<KernelLaunch> &out);
       // (world_view.hip)
+// head stage of a step replay: behind its input rings, in front of its first
+// task-graph node (buildLaunchList, runtime_launch.hip)
+MWHIP_RT int stepWriteStage(mwhip_exec *exec, const LaunchGraph &lg,
+                            std::vector<KernelLaunch> &out);
+      // (world_write.hip)
 MWHIP_RT int outputRingStage(mwhip_exec *exec, const LaunchGraph &lg,
                              std::vector<KernelLaunch> &out);
       // (output_ring.hip)

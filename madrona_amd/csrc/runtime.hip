@@ -667,6 +667,7 @@ extern "C" void mwhip_destroy(mwhip_exec *exec)
     exec->snapshots.clear();
     exec->digests.clear();
     exec->views.clear();
+    exec->writes.clear();
     for (void *p : exec->allocations) {
         (void)hipFree(p);
     }

@@ -375,6 +375,10 @@ static int buildLaunchList(mwhip_exec *exec, const std::vector<uint32_t> &tg_ids
             k.kind = MWHIP_NODE_RECYCLE;
             lg.launches.push_back(k);
         }
+        // the step writes, fed by the input rings of the same replay
+        // (mwhip_set_step_write, world_write.hip)
+        int rc = stepWriteStage(exec, lg, lg.launches);
+        if (rc != 0) return rc;
     }
     for (uint32_t tg_id : tg_ids) {
         if (tg_id >= exec->taskGraphs.size()) {

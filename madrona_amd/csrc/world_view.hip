@@ -32,9 +32,11 @@
 // and rank < max_rows by construction.  A team writes nothing but its own
 // world's slabs: no atomics, no spin-waits, no workgroup waits for another, no
 // LDS.  (copyChunk of copy_chunk.hpp moves a chunk with a whole workgroup; a
-// team is a part of a wavefront, so only its vector types are shared.)
+// team is a part of a wavefront, so only its vector types are shared.  What a
+// team does that the world writes need too -- teamCopy, cellCopy, teamRange --
+// is in world_team.hpp.)
 #include "exec_internal.hpp"
-#include "copy_chunk.hpp"
+#include "world_team.hpp"
 
 namespace {
 
@@ -69,35 +71,8 @@ using madrona::mwhip::CopyU4;
 using madrona::mwhip::GlobalU4;
 using madrona::mwhip::GlobalU32;
 using madrona::mwhip::GlobalU8;
-
-// n bytes by the T lanes of a team (t: lane in the team)
-__device__ inline void teamCopy(char *dst, const char *src, uint64_t n, uint32_t t, uint32_t T)
-{
-    const uint64_t d = (uint64_t)dst, s = (uint64_t)src;
-    GlobalU8 *d8 = (GlobalU8 *)d;
-    const GlobalU8 *s8 = (const GlobalU8 *)s;
-    uint64_t done = 0;
-    if (((d ^ s) & 15ull) == 0ull) {
-        uint64_t head = (16ull - (d & 15ull)) & 15ull;
-        head = head < n ? head : n;
-        for (uint64_t i = t; i < head; i += T) d8[i] = s8[i];
-        const uint64_t num_vec = (n - head) >> 4;
-        GlobalU4 *d4 = (GlobalU4 *)(d + head);
-        const GlobalU4 *s4 = (const GlobalU4 *)(s + head);
-        for (uint64_t i = t; i < num_vec; i += T) d4[i] = s4[i];
-        done = head + (num_vec << 4);
-    } else if (((d ^ s) & 3ull) == 0ull) {
-        uint64_t head = (4ull - (d & 3ull)) & 3ull;
-        head = head < n ? head : n;
-        for (uint64_t i = t; i < head; i += T) d8[i] = s8[i];
-        const uint64_t num_words = (n - head) >> 2;
-        GlobalU32 *d1 = (GlobalU32 *)(d + head);
-        const GlobalU32 *s1 = (const GlobalU32 *)(s + head);
-        for (uint64_t i = t; i < num_words; i += T) d1[i] = s1[i];
-        done = head + (num_words << 2);
-    }
-    for (uint64_t i = done + t; i < n; i += T) d8[i] = s8[i];
-}
+using madrona::mwhip::cellCopy;
+using madrona::mwhip::teamCopy;
 
 // n zero bytes by the T lanes of a team
 __device__ inline void teamZero(char *dst, uint64_t n, uint32_t t, uint32_t T)
@@ -112,25 +87,6 @@ __device__ inline void teamZero(char *dst, uint64_t n, uint32_t t, uint32_t T)
     const CopyU4 zero = { 0u, 0u, 0u, 0u };
     for (uint64_t i = t; i < num_vec; i += T) d4[i] = zero;
     for (uint64_t i = head + (num_vec << 4) + t; i < n; i += T) d8[i] = (uint8_t)0;
-}
-
-// one cell by one lane
-__device__ inline void cellCopy(char *dst, const char *src, uint32_t bytes)
-{
-    const uint64_t d = (uint64_t)dst, s = (uint64_t)src;
-    if (((d | s) & 15ull) == 0ull && bytes % 16u == 0u) {
-        GlobalU4 *d4 = (GlobalU4 *)d;
-        const GlobalU4 *s4 = (const GlobalU4 *)s;
-        for (uint32_t i = 0; i < bytes / 16u; i++) d4[i] = s4[i];
-    } else if (((d | s) & 3ull) == 0ull && bytes % 4u == 0u) {
-        GlobalU32 *d1 = (GlobalU32 *)d;
-        const GlobalU32 *s1 = (const GlobalU32 *)s;
-        for (uint32_t i = 0; i < bytes / 4u; i++) d1[i] = s1[i];
-    } else {
-        GlobalU8 *d8 = (GlobalU8 *)d;
-        const GlobalU8 *s8 = (const GlobalU8 *)s;
-        for (uint32_t i = 0; i < bytes; i++) d8[i] = s8[i];
-    }
 }
 
 // Rows [from, to) of the table, T at a time: those whose WorldID cell is w are
@@ -179,30 +135,11 @@ __device__ inline void viewWave(const ViewPlan *plan, uint32_t item, uint32_t la
     const uint32_t w = item * (64u / T) + team;
     const bool valid = w < num_worlds;
 
-    const TableHdr *hdr = plan->hdr;
-    // (appends wait for the rows they take to be mapped: numRows rows are there,
-    // as for digestKernel; the header's capacity word may lag behind a growth)
-    int32_t n = hdr->numRows;
-    n = n > 0 ? n : 0;
-    int32_t prefix = hdr->sortedRows;
-    if (prefix < 0 || prefix > n) {
-        prefix = 0;         // whatever truncated the table: everything is "tail"
-    }
-    const int32_t *world_col = (const int32_t *)hdr->columns[1];
-
     // where world w's rows of the sorted prefix are (a hint: each row is still
     // tested against its own WorldID cell)
-    int32_t lo = 0, hi = 0;
-    if (valid && prefix > 0) {
-        const int32_t off = hdr->worldOffsets[w];
-        const int32_t cnt = hdr->worldCounts[w];
-        lo = off > 0 ? (off < prefix ? off : prefix) : 0;
-        if (cnt > 0) {
-            const int64_t end = (int64_t)off + cnt;
-            hi = end < (int64_t)prefix ? (int32_t)end : prefix;
-        }
-        hi = hi > lo ? hi : lo;
-    }
+    const madrona::mwhip::TeamRange range = madrona::mwhip::teamRange(plan->hdr, w, valid);
+    const int32_t n = range.n, prefix = range.prefix, lo = range.lo, hi = range.hi;
+    const int32_t *world_col = range.worldCol;
 
     // 1. the live rows of the range
     uint32_t live = 0;

@@ -176,7 +176,7 @@ friend class MWCudaExecutor;
 
 namespace detail {
 
-// What MWHipSnapshot, MWHipDigest and MWHipWorldView share: the move-only handle
+// What MWHipSnapshot, MWHipDigest, MWHipWorldView and MWHipWorldWrite share: the move-only handle
 // of an object that belongs to an executor (mwhip_<kind>_create / _destroy,
 // include/mwhip.h).  Kind: { name, destroy(exec, handle) }.
 template <typename Kind>
@@ -240,6 +240,10 @@ struct DigestKind {
 struct WorldViewKind {
     static constexpr const char *name = "world view";
     static void destroy(mwhip_exec *exec, uint64_t handle) { mwhip_view_destroy(exec, handle); }
+};
+struct WorldWriteKind {
+    static constexpr const char *name = "world write";
+    static void destroy(mwhip_exec *exec, uint64_t handle) { mwhip_write_destroy(exec, handle); }
 };
 
 }
@@ -355,6 +359,74 @@ private:
     MWHipWorldView(mwhip_exec *exec, uint64_t view, uint32_t max_rows, int32_t gpu_id)
         : ExecObject(exec, view), max_rows_(max_rows), gpu_id_(gpu_id)
     {}
+
+    uint32_t max_rows_;
+    int32_t gpu_id_;
+
+friend class MWCudaExecutor;
+};
+
+// The inverse of a world view: per listed column uint8 [worlds][maxRows()][cell
+// bytes] on the device (the layout of a view of the same columns and maxRows())
+// and int32 [worlds] `take`, both filled by the caller; apply() makes the
+// listed cells of the first min(max(take[w], 0), rows of w, maxRows()) rows of
+// every world w, in table order, those of the tensors, with one kernel where
+// the table is, sorted or not, and leaves each world's row count (not clipped)
+// in the counts (mwhip_write_*, include/mwhip.h: the exact definition).
+// Nothing else of the table changes; what the simulator derives from the
+// written components follows when its own systems next derive it.  Filling the
+// tensors is ordered against apply by the caller, as for exported action
+// tensors.  An extension of this backend.  Belongs to the executor that made
+// it and must not outlive it.
+class MWHipWorldWrite : public detail::ExecObject<detail::WorldWriteKind> {
+public:
+    MWHipWorldWrite() : max_rows_(0), gpu_id_(0) {}
+
+    // waits for the executor's stream
+    void apply() { req(mwhip_write_apply(exec_, handle_), "apply"); }
+    // queued on the executor's stream behind the replays queued so far
+    void applyAsync() { req(mwhip_write_apply_async(exec_, handle_), "applyAsync"); }
+
+    // uint8 [worlds][maxRows()][cell bytes] of listed column `column`
+    // (position in the list given to makeWorldWrite), owned by the executor
+    py::Tensor columnTensor(uint32_t column) const
+    {
+        uint64_t bytes = 0;
+        uint32_t cell = 0;
+        void *ptr = mwhip_write_buffer(exec_, handle_, column, &bytes, &cell);
+        req(ptr != nullptr ? 0 : -1, "columnTensor");
+        const int64_t dims[3] = { (int64_t)mwhip_num_worlds(exec_), (int64_t)max_rows_,
+                                  (int64_t)cell };
+        return py::Tensor(ptr, py::TensorElementType::UInt8, Span<const int64_t>(dims, 3),
+                          Optional<int>::make((int)gpu_id_));
+    }
+
+    // int32 [worlds], in: the leading rows of each world to write
+    py::Tensor takeTensor() const
+    {
+        return perWorld(mwhip_write_take(exec_, handle_), "takeTensor");
+    }
+
+    // int32 [worlds], out: each world's rows in the table (may exceed maxRows())
+    py::Tensor countsTensor() const
+    {
+        return perWorld(mwhip_write_counts(exec_, handle_), "countsTensor");
+    }
+
+    uint32_t maxRows() const { return max_rows_; }
+
+private:
+    MWHipWorldWrite(mwhip_exec *exec, uint64_t write, uint32_t max_rows, int32_t gpu_id)
+        : ExecObject(exec, write), max_rows_(max_rows), gpu_id_(gpu_id)
+    {}
+
+    py::Tensor perWorld(void *ptr, const char *what) const
+    {
+        req(ptr != nullptr ? 0 : -1, what);
+        const int64_t dims[1] = { (int64_t)mwhip_num_worlds(exec_) };
+        return py::Tensor(ptr, py::TensorElementType::Int32, Span<const int64_t>(dims, 1),
+                          Optional<int>::make((int)gpu_id_));
+    }
 
     uint32_t max_rows_;
     int32_t gpu_id_;
@@ -686,6 +758,26 @@ public:
     {
         req(mwhip_set_step_view(exec_, view != nullptr ? view->handle() : 0, on ? 1 : 0),
             "setStepView");
+    }
+
+    // tensors to scatter into `components` of archetype `archetype`'s table
+    // (neither Entity nor WorldID), max_rows rows per world (see MWHipWorldWrite)
+    MWHipWorldWrite makeWorldWrite(uint32_t archetype, Span<const uint32_t> components,
+                                   uint32_t max_rows)
+    {
+        uint64_t write = 0;
+        req(mwhip_write_create(exec_, archetype, components.data(),
+            (uint32_t)components.size(), max_rows, &write), "makeWorldWrite");
+        return MWHipWorldWrite(exec_, write, max_rows, gpu_id_);
+    }
+
+    // on: every replay of a step graph applies `write` behind its input rings
+    // and in front of its first task-graph node (up to MWHIP_MAX_STEP_WRITES
+    // writes, one launch for all); off: no longer
+    void setStepWrite(const MWHipWorldWrite *write, bool on)
+    {
+        req(mwhip_set_step_write(exec_, write != nullptr ? write->handle() : 0, on ? 1 : 0),
+            "setStepWrite");
     }
 
     // Device-resident rings (extensions of this backend, include/mwhip.h).

@@ -214,6 +214,22 @@ def runtime_lib() -> C.CDLL:
     lib.mwhip_view_counts.argtypes = [C.c_void_p, C.c_uint64]
     lib.mwhip_set_step_view.restype = C.c_int
     lib.mwhip_set_step_view.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
+    lib.mwhip_write_create.restype = C.c_int
+    lib.mwhip_write_create.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32),
+                                       C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+    lib.mwhip_write_destroy.restype = None
+    lib.mwhip_write_destroy.argtypes = [C.c_void_p, C.c_uint64]
+    for fn in (lib.mwhip_write_apply, lib.mwhip_write_apply_async):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_uint64]
+    lib.mwhip_write_buffer.restype = C.c_void_p
+    lib.mwhip_write_buffer.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32,
+                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    for fn in (lib.mwhip_write_take, lib.mwhip_write_counts):
+        fn.restype = C.c_void_p
+        fn.argtypes = [C.c_void_p, C.c_uint64]
+    lib.mwhip_set_step_write.restype = C.c_int
+    lib.mwhip_set_step_write.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
     return lib
 
 
@@ -235,7 +251,7 @@ class _Checked:
 
 
 class _ExecObject(_Checked):
-    """What Snapshot, StateDigest and WorldView are: something a simulator's
+    """What Snapshot, StateDigest, WorldView and WorldWrite are: something a simulator's
     executor owns, named by `handle` there, kept in one of the simulator's
     lists (`_list`) while it is open.  close() frees it and takes it off the
     list (a snapshot too, which used to stay on it until the simulator closed); Simulator.close() frees the executor and orphans
@@ -683,6 +699,159 @@ class WorldView(_ExecObject):
         self._every_step = bool(on)
 
 
+class WorldWrite(_ExecObject):
+    """The inverse of a WorldView: tensors on the device that are scattered
+    into columns of ONE table.  Per column uint8 [worlds, max_rows, cell_bytes]
+    (tensor(name): exactly the layout of a WorldView of the same columns and
+    max_rows, so a view's tensors can be copied in one for one) and int32
+    [worlds] `take`; apply() makes the listed cells of the first
+    min(max(take[w], 0), rows of w, max_rows) rows of every world w, in table
+    order, those of the tensors, and leaves each world's row count, not
+    clipped, in `counts`.  Nothing else of the table changes, Entity and
+    WorldID cannot be listed, and what the simulator derives from a written
+    component follows when its own systems next derive it.
+    madrona_amd/write_ref.py is the exact definition; mwhip_write_*,
+    include/mwhip.h, applies it with one kernel where the table is, sorted or
+    not.  HIP backend only.  All buffers start as zeros (take too: nothing is
+    written until it is set).
+
+    apply() waits for the executor's stream, apply_async() queues behind the
+    replays queued so far.  FILLING THE TENSORS IS THE CALLER'S TO ORDER: torch
+    fills them on its own stream, so synchronize that stream (or make the
+    executor's stream wait for it) before apply_async() or a step that carries
+    the write, exactly as for the exported action tensors.  every_step() makes
+    every replay of a step graph apply the write behind its input rings and in
+    front of its first node: an input ring over buffer_ptr(name) or take_ptr
+    feeds K queued steps K different injections.  close() frees it;
+    Simulator.close() orphans what is left."""
+
+    _kind, _destroy, _list = "world write", "mwhip_write_destroy", "_writes"
+
+    def __init__(self, sim: "Simulator", table: str, columns, max_rows: int):
+        names = [c[0] for c in sim._columns]
+        of_table = [n for n in names if n.split(".", 1)[0] == table]
+        if not of_table:
+            raise KeyError(f"world_write(): no table {table!r} in the dump list")
+        if not hasattr(sim.lib, "sim_hip_column_ids"):
+            raise RuntimeError("this simulator library has no sim_hip_column_ids: rebuild it")
+
+        def ids(name):
+            arch, comp = C.c_uint32(0), C.c_uint32(0)
+            if sim.lib.sim_hip_column_ids(sim.handle, names.index(name), C.byref(arch),
+                                          C.byref(comp)) != 0:
+                raise RuntimeError(f"sim_hip_column_ids({name}) failed")
+            return arch.value, comp.value
+
+        if columns is None:
+            # (component 0 is Entity, 1 is WorldID: include/mwhip.h)
+            columns = [n for n in of_table if ids(n)[1] not in (0, 1)]
+        columns = list(columns)
+        for name in columns:
+            if name not in of_table:
+                raise KeyError(f"world_write(): {name!r} is not a column of table {table!r}")
+        if not columns:
+            raise ValueError("world_write(): no columns")
+        if len(set(columns)) != len(columns):
+            raise ValueError("world_write(): a column is listed twice")
+        self._sim = sim
+        self.table = table
+        self.columns = columns
+        self.max_rows = int(max_rows)
+        self.num_worlds = sim.num_worlds
+        self._rt = runtime_lib()
+        self._exec = sim.hip_exec()
+        self._tensors = {}
+        self._every_step = False
+        self.handle = 0
+        archetypes = set()
+        comps = (C.c_uint32 * len(columns))()
+        for p, name in enumerate(columns):
+            arch, comps[p] = ids(name)
+            archetypes.add(arch)
+        assert len(archetypes) == 1, archetypes
+        self.archetype = archetypes.pop()
+        handle = C.c_uint64(0)
+        self._check(self._rt.mwhip_write_create(
+            self._exec, self.archetype, comps, len(columns),
+            min(max(self.max_rows, 0), 0xFFFFFFFF), C.byref(handle)), "mwhip_write_create")
+        self.handle = int(handle.value)
+        self._buffers = {}
+        for p, name in enumerate(columns):
+            nbytes, cell = C.c_uint64(0), C.c_uint32(0)
+            ptr = self._rt.mwhip_write_buffer(self._exec, self.handle, p, C.byref(nbytes),
+                                              C.byref(cell))
+            assert ptr and nbytes.value == self.num_worlds * self.max_rows * cell.value
+            self._buffers[name] = (int(ptr), int(cell.value))
+        self._take_ptr = int(self._rt.mwhip_write_take(self._exec, self.handle) or 0)
+        self.counts_ptr = int(self._rt.mwhip_write_counts(self._exec, self.handle) or 0)
+
+    def _orphan(self) -> None:
+        super()._orphan()
+        self._tensors = {}
+
+    def apply(self) -> "WorldWrite":
+        """Writes the table; waits for the executor's stream."""
+        self._check(self._rt.mwhip_write_apply(self._exec, self._live()),
+                    "mwhip_write_apply")
+        return self
+
+    def apply_async(self) -> None:
+        self._check(self._rt.mwhip_write_apply_async(self._exec, self._live()),
+                    "mwhip_write_apply_async")
+
+    def buffer_ptr(self, name: str) -> int:
+        """Device address of column `name`'s [worlds, max_rows, cell_bytes] bytes."""
+        self._live()
+        return self._buffers[name][0]
+
+    def cell_bytes(self, name: str) -> int:
+        return self._buffers[name][1]
+
+    @property
+    def take_ptr(self) -> int:
+        """Device address of the int32 [worlds] take buffer."""
+        self._live()
+        return self._take_ptr
+
+    _wrap = WorldView._wrap
+
+    def tensor(self, name: str, dtype=None):
+        """torch uint8 [worlds, max_rows, cell_bytes] over the device buffer of
+        column `name` (no copy), or, with a numpy dtype, [worlds, max_rows,
+        cell_bytes // itemsize] of that type.  The caller fills it."""
+        self._live()
+        ptr, cell = self._buffers[name]
+        dt = np.dtype(np.uint8 if dtype is None else dtype)
+        if cell % dt.itemsize != 0:
+            raise TypeError(f"{name}: cells of {cell} bytes do not hold whole {dt} items")
+        return self._wrap((name, dt.str), ptr, dt.type,
+                          (self.num_worlds, self.max_rows, cell // dt.itemsize))
+
+    @property
+    def take(self):
+        """torch int32 [worlds] over the device buffer (no copy): the leading
+        rows of each world to write.  The caller fills it."""
+        self._live()
+        return self._wrap(("", "take"), self._take_ptr, np.int32, (self.num_worlds,))
+
+    @property
+    def counts(self):
+        """torch int32 [worlds] over the device buffer (no copy): each world's
+        rows in the table as the last apply found them, not clipped."""
+        self._live()
+        return self._wrap(("", "counts"), self.counts_ptr, np.int32, (self.num_worlds,))
+
+    def every_step(self, on: bool = True) -> None:
+        """Every replay of a step graph applies this write first (waits for the
+        stream and rebuilds the launch graphs); on=False turns it off again."""
+        handle = self._live()
+        if not on and not self._every_step:
+            return
+        self._check(self._rt.mwhip_set_step_write(self._exec, handle, 1 if on else 0),
+                    "mwhip_set_step_write")
+        self._every_step = bool(on)
+
+
 class Simulator:
     """One simulator instance behind the C API (either backend)."""
 
@@ -710,6 +879,7 @@ class Simulator:
         self._trajectories: List["Trajectory"] = []
         self._digests: List["StateDigest"] = []
         self._views: List["WorldView"] = []
+        self._writes: List["WorldWrite"] = []
         self._tensor_info: Dict[str, Tuple[int, np.dtype, Tuple[int, ...], bool]] = {}
         for i in range(self.lib.sim_num_tensors(self.handle)):
             info = SimTensorInfo()
@@ -726,10 +896,11 @@ class Simulator:
     # -- lifecycle ---------------------------------------------------------
     def close(self) -> None:
         if self.handle:
-            # sim_destroy frees the executor and with it its snapshots, digests
-            # and world views, and forgets its output rings (the trajectories
-            # keep their tensors)
-            for open_ones in (self._snapshots, self._trajectories, self._digests, self._views):
+            # sim_destroy frees the executor and with it its snapshots, digests,
+            # world views and world writes, and forgets its output rings (the
+            # trajectories keep their tensors)
+            for open_ones in (self._snapshots, self._trajectories, self._digests, self._views,
+                              self._writes):
                 for obj in open_ones:
                     obj._orphan()
                 open_ones.clear()
@@ -885,6 +1056,18 @@ class Simulator:
         view = WorldView(self, table, columns, max_rows)
         self._views.append(view)
         return view
+
+    def world_write(self, table: str, columns=None, max_rows: int = 0) -> "WorldWrite":
+        """A WorldWrite into `columns` (names as in `columns`, e.g. "Item.Vec3";
+        default: every dump-list column of the table except Entity and
+        WorldID, which cannot be written) of table `table`, max_rows rows per
+        world.  HIP backend; raises on the reference backend, which has no
+        executor to ask."""
+        if self.backend != "hip":
+            raise RuntimeError(f"world writes need the HIP backend, this is {self.backend!r}")
+        write = WorldWrite(self, table, columns, max_rows)
+        self._writes.append(write)
+        return write
 
     def record(self, names: List[str], steps: int, on_render: bool = False) -> "Trajectory":
         """Records the exported tensors `names` on the device from the next

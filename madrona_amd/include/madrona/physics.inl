@@ -1410,7 +1410,13 @@ candidateKernel(EcsState *S, void *, uint32_t, uint32_t)
 
 #include <madrona/phys_impl/world_step.inl>
 
-// LDS of one staged tree rebuild (<= 64 leaves)
+// LDS of one staged tree rebuild: <= 64 leaves AND a node array of <= 85
+// nodes.  The node array is sized by the tree's max_leaves
+// (numInternalNodes(max_leaves), BVH::nodeCapacity()), not by the leaves it
+// holds, so staging depends on max_leaves <= 64: the same 64 leaves under
+// max_leaves = 65 (capacity 87) are built in place.  Both sides of that
+// boundary: tests/test_bvh_edges_gpu.py::test_plan_lock_step, max_leaves
+// modes "64" and "65".
 struct BvhRebuildStaging {
     static constexpr int32_t maxLeaves = 64;
     static constexpr int32_t maxNodes = 21 + maxLeaves;    // numInternalNodes(64)
@@ -1483,6 +1489,12 @@ __device__ inline void rebuildTreeStaged(broadphase::BVH &bvh, uint32_t lane,
     int32_t num_nodes = local.rebuildStagedSegmented(lane, &staging.segmented);
     wave::phaseFence();
 #endif
+    // (-1: more range records than maxRebuildRanges = 96.  A record is a node,
+    // and a build that stays inside its node array -- the condition under
+    // which the reference's own build is defined -- numbers at most 85 of them
+    // here, so this branch is unreachable from legal inputs
+    // (tests/test_bvh_edges_cpu.py: 49 at most over the planned cases); it is
+    // what MADRONA_PHYS_STACK_REBUILD builds run.)
     if (num_nodes < 0) {
         for (int32_t i = (int32_t)lane; i < num_leaves; i += 64) {
             staging.sortedLeaves[i] = bvh.rawSortedLeaves()[i];

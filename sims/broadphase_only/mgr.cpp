@@ -128,4 +128,13 @@ void SimTraits::describeColumns(T &cols)
     cols.template add<Sensor, RayFan>("Sensor.RayFan", false);
     cols.template add<CandidateTemporary, CandidateCollision>(
         "Candidates.CandidateCollision", false);
+    // (plan mode's outputs and what its tests rebuild the leaf boxes from;
+    // behind the columns above, whose indices stay)
+    cols.template add<Sensor, RayFanPlain>("Sensor.RayFanPlain", false);
+    cols.template add<Prober, Probe32>("Prober.Probe32", false);
+    cols.template add<Prober, Probe64>("Prober.Probe64", false);
+    cols.template add<Box, madrona::phys::Velocity>("Box.Velocity", true);
+    cols.template add<Box, madrona::base::Scale>("Box.Scale", true);
+    cols.template add<Pillar, madrona::phys::broadphase::LeafID>(
+        "Pillar.LeafID", false);
 }

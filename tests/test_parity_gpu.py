@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from madrona_amd.simlib import Simulator, hip_lib_path, ref_lib_path
+from bvh_edges_utils import candidate_pairs as _candidate_pairs
 from parity_utils import compare_columns, run_pair
 
 pytestmark = pytest.mark.gpu
@@ -296,31 +297,6 @@ def test_ball_pit_crowd(built, monkeypatch, extra, kernel):
     probs, step = run_pair("ball_pit", 24, 70, flags=(extra << 16) | denom,
                            check_every=5, check_init=False)
     assert not probs, (kernel, step, probs[:3])
-
-
-def _candidate_pairs(dump, arch_names):
-    """CandidateCollision rows -> (world, entity id a, entity id b, aPrim, bPrim).
-    A Loc's row is world-local on the CPU backend and global on the GPU; both are
-    resolved through the dumped Entity columns (grouped by world, world order)."""
-    cand, cand_counts = dump["Candidates.CandidateCollision"]
-    cand = cand.view(np.int32).reshape(-1, 6)      # a.arch a.row b.arch b.row aPrim bPrim
-    tables = {}
-    for arch_id, name in arch_names.items():
-        ents, counts = dump[f"{name}.Entity"]
-        ids = ents.view(np.int32).reshape(-1, 2)[:, 1]
-        tables[arch_id] = (ids, np.concatenate([[0], np.cumsum(counts)]))
-    out = []
-    world_of_row = np.repeat(np.arange(len(cand_counts)), cand_counts)
-    for row, w in zip(cand, world_of_row):
-        pair = []
-        for arch, r in ((row[0], row[1]), (row[2], row[3])):
-            ids, starts = tables[int(arch)]
-            local_guess = starts[w] + r           # CPU: world-local row
-            global_guess = r                      # GPU: global row
-            pair.append((int(ids[local_guess]) if local_guess < len(ids) else -1,
-                         int(ids[global_guess]) if global_guess < len(ids) else -1))
-        out.append((int(w), pair, int(row[4]), int(row[5])))
-    return out, cand_counts
 
 
 @pytest.mark.parametrize("worlds", [1, 7, 200])

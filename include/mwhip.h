@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded() and mwhip_digest_*() / mwhip_set_step_digest() (a per-world hash of chosen columns computed on the device) and mwhip_view_*() / mwhip_set_step_view() (padded per-world tensors of a table's columns) and mwhip_write_*() / mwhip_set_step_write() (padded per-world tensors scattered into a table's columns); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
+#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded() and mwhip_digest_*() / mwhip_set_step_digest() (a per-world hash of chosen columns computed on the device) and mwhip_view_*() / mwhip_set_step_view() (padded per-world tensors of a table's columns) and mwhip_write_*() / mwhip_set_step_write() (padded per-world tensors scattered into a table's columns) and mwhip_reduce_term / mwhip_reduce_*() / mwhip_set_step_reduce() (per-world sums, extrema, counts and alarms of a table's columns); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
 
 typedef struct mwhip_exec mwhip_exec; /* opaque; == MWCudaExecutor::Impl */
 
@@ -830,6 +830,115 @@ void *mwhip_write_buffer(mwhip_exec *exec, uint64_t write, uint32_t column,
 int32_t *mwhip_write_take(mwhip_exec *exec, uint64_t write);
 int32_t *mwhip_write_counts(mwhip_exec *exec, uint64_t write);
 int mwhip_set_step_write(mwhip_exec *exec, uint64_t write, int on);
+
+/* World reductions (added under ABI 9): one number per world, element and term
+ * about ONE table, computed by one kernel where the table is (DESIGN.md §28;
+ * madrona_amd/reduce_ref.py is the same definition in numpy).  A reduce names
+ * one archetype a and an ordered list of n TERMS
+ *   { component_id, byte_offset, num_elems, dtype, op, flags, limit }.
+ * The same component may appear in several terms; Entity (component 0) and
+ * WorldID (component 1) may be listed.
+ * Rows and elements.  The rows of world w are the rows r < numRows of the
+ * table whose WorldID cell equals w, taken in ascending r: exactly the world
+ * view's rule.  Rows destroyed in place (WorldID < 0) belong to no world.
+ * Nothing depends on which side of a column's twin buffers is current, on
+ * worldOffsets / worldCounts being current, or on the sorted prefix.  Element
+ * e < num_elems of row j is the `dtype` value at byte_offset + e *
+ * sizeof(dtype) of that row's cell of the component (F32, I32, U32: 4 bytes,
+ * U8: 1 byte).
+ * Outputs, with W = the executor's number of worlds:
+ *   count[w]   int32 [W]: the number of rows of w, as for views;
+ *   R_t[w][e]  one 4-byte result [W][num_elems] per term t;
+ *   alarm[w]   int32 [W], 0 or 1.
+ * Operations, x_j being element e of the j-th row of w (row order):
+ *   SUM             f32 / i32 / u32 (U8 widened to u32).  F32: acc = +0.0f,
+ *                   then acc = acc + x_j in row order, fp32 round-to-nearest,
+ *                   no reassociation, no flushing of denormals.  Integers:
+ *                   modulo 2^32.
+ *   MIN             as above.  acc = +inf (F32) or the largest value of the
+ *                   result type; if (x < acc) acc = x in row order.  A NaN
+ *                   never replaces; of -0 and +0 the first one met stays.
+ *   MAX             mirrored: acc = -inf, INT32_MIN or 0; if (x > acc) acc = x.
+ *   ABSMAX          F32 only, f32: acc = +0; a = x with the sign bit cleared;
+ *                   if (a > acc) acc = a.  NaNs are ignored, Inf counts.
+ *   COUNT_NONZERO   int32: the rows with x != 0.  NaN counts, -0 does not.
+ *   COUNT_NONFINITE F32 only, int32: the rows whose exponent bits are all ones.
+ * A world without rows gets the identities.
+ * Alarms.  A term with MWHIP_REDUCE_ALARM in flags TRIPS for w when any of its
+ * elements meets the condition: COUNT_*: the result is > 0; F32 ABSMAX and
+ * MAX: the result is > limit; F32 MIN: the result is < limit.  alarm[w] = 1 if
+ * any alarm term trips for w, else 0.  `limit` is ignored without the flag.
+ * Every compute writes all outputs in full; they start as zeros; each is
+ * 256-byte aligned and all sit in one allocation per reduce.  A compute reads
+ * the table's row count, sorted prefix and column addresses on the device when
+ * the kernel runs: the asynchronous form is stream-ordered behind the replays
+ * queued before it, and a reduce made before a table grew stays valid.
+ *
+ * mwhip_reduce_buffer: device address of R_t of term `term` (position in the
+ * list), valid until the reduce is destroyed; *bytes_out = W * num_elems * 4,
+ * *elems_out = num_elems; NULL for an unknown handle or a term out of range.
+ * mwhip_reduce_counts / mwhip_reduce_alarm: count and alarm, likewise.
+ * mwhip_set_step_reduce(on != 0): every replay of every STEP graph of the
+ * executor (packed ones included; render graphs are untouched) recomputes the
+ * reduce behind its last task-graph node, its step digest and its step views
+ * and in front of its pack node and its output-ring copies: an output ring
+ * whose src is one of the buffers records one result per step, and an input
+ * ring whose ring is mwhip_reduce_alarm() (one slot) feeds the alarm of replay
+ * k to the head of replay k + 1 with nothing but graph launches on the stream.
+ * Up to MWHIP_MAX_STEP_REDUCES step reduces, ONE launch for all of them;
+ * mwhip_profile lists it with name and role "reduce", algo_bytes = the bytes
+ * written + per row counted its WorldID cell and its listed elements, worked
+ * out after the run from count.  on == 0 takes it out again.  The set lives in
+ * the executor, not in a graph: changing it waits for the stream and rebuilds
+ * the launch graphs (handles stay valid; rebuilds on table growth keep it).
+ * Destroying a step reduce unsets it.  Snapshots do not save a reduce's
+ * buffers.  Handles are unique in the process; mwhip_destroy frees what is left.
+ * Errors (non-zero, text in mwhip_last_error(), nothing changed or allocated):
+ * an unknown handle or one of another executor ("reduce N is not one of this
+ * executor's"; looked up first, so also with a null executor), n == 0 or
+ * n > MWHIP_REDUCE_MAX_TERMS, num_elems == 0, more than MWHIP_REDUCE_MAX_ELEMS
+ * elements in all, an unknown dtype, op or flag, ABSMAX or COUNT_NONFINITE on a
+ * dtype other than F32, the alarm flag on an (op, dtype) pair without a rule
+ * above, an archetype that is not registered, a component the archetype does
+ * not have, a byte_offset that is not a multiple of the element size, a cell
+ * whose size is not, an element range that leaves the cell, a ninth step
+ * reduce, buffers that cannot be allocated.
+ * (No reference counterpart.) */
+#define MWHIP_REDUCE_MAX_TERMS 32
+#define MWHIP_REDUCE_MAX_ELEMS 256
+#define MWHIP_MAX_STEP_REDUCES 8
+#define MWHIP_REDUCE_F32 0u
+#define MWHIP_REDUCE_I32 1u
+#define MWHIP_REDUCE_U32 2u
+#define MWHIP_REDUCE_U8 3u
+#define MWHIP_REDUCE_SUM 0u
+#define MWHIP_REDUCE_MIN 1u
+#define MWHIP_REDUCE_MAX 2u
+#define MWHIP_REDUCE_ABSMAX 3u
+#define MWHIP_REDUCE_COUNT_NONZERO 4u
+#define MWHIP_REDUCE_COUNT_NONFINITE 5u
+#define MWHIP_REDUCE_ALARM 1u
+typedef struct mwhip_reduce_term {
+    uint32_t component_id;
+    uint32_t byte_offset;   /* of element 0 in the component's cell */
+    uint32_t num_elems;
+    uint32_t dtype;         /* MWHIP_REDUCE_F32 .. _U8 */
+    uint32_t op;            /* MWHIP_REDUCE_SUM .. _COUNT_NONFINITE */
+    uint32_t flags;         /* MWHIP_REDUCE_ALARM or 0 */
+    float limit;            /* of an F32 ABSMAX / MAX / MIN alarm */
+} mwhip_reduce_term;
+int mwhip_reduce_create(mwhip_exec *exec, uint32_t archetype_id, const mwhip_reduce_term *terms,
+                        uint32_t n, uint64_t *reduce_out);
+void mwhip_reduce_destroy(mwhip_exec *exec, uint64_t reduce);
+/* waits for the executor's stream */
+int mwhip_reduce_compute(mwhip_exec *exec, uint64_t reduce);
+/* queued on the executor's stream behind the replays queued so far */
+int mwhip_reduce_compute_async(mwhip_exec *exec, uint64_t reduce);
+void *mwhip_reduce_buffer(mwhip_exec *exec, uint64_t reduce, uint32_t term,
+                          uint64_t *bytes_out, uint32_t *elems_out);
+int32_t *mwhip_reduce_counts(mwhip_exec *exec, uint64_t reduce);
+int32_t *mwhip_reduce_alarm(mwhip_exec *exec, uint64_t reduce);
+int mwhip_set_step_reduce(mwhip_exec *exec, uint64_t reduce, int on);
 
 #ifdef __cplusplus
 }

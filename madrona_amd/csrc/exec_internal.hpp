@@ -4,7 +4,8 @@
 // runtime_kernels.hip: the runtime's own small kernels; output_ring.hip: the
 // output rings; snapshot.hip: saving and restoring all world state; digest.hip:
 // per-world state digests; world_view.hip: padded per-world views of a table's
-// columns; world_write.hip: the same tensors scattered into a table's columns).
+// columns; world_write.hip: the same tensors scattered into a table's columns;
+// world_reduce.hip: per-world reductions of a table's columns).
 // Not installed.
 #pragma once
 #include "runtime_internal.hpp"
@@ -248,6 +249,7 @@ struct mwhip_snapshot_rec;      // (snapshot.hip)
 struct mwhip_digest_rec;        // (digest.hip)
 struct mwhip_view_rec;          // (world_view.hip)
 struct mwhip_write_rec;         // (world_write.hip)
+struct mwhip_reduce_rec;        // (world_reduce.hip)
 
 // What a replay carries besides its task graphs.  Every launch graph is built
 // from it (the input rings and the step writes open a step graph, the rest are tail stages:
@@ -281,6 +283,9 @@ struct ReplayExtras {
     // mwhip_set_step_write: those every step replay applies, in one launch
     // behind the input rings
     std::vector<uint64_t> stepWrites;
+    // mwhip_set_step_reduce: those every step replay recomputes, in one launch
+    // behind the step views
+    std::vector<uint64_t> stepReduces;
 };
 
 struct mwhip_exec {
@@ -381,6 +386,7 @@ struct mwhip_exec {
     ExecObjectTable<mwhip_digest_rec> digests;
     ExecObjectTable<mwhip_view_rec> views;
     ExecObjectTable<mwhip_write_rec> writes;
+    ExecObjectTable<mwhip_reduce_rec> reduces;     // mwhip_reduce_create
 };
 
 // ---- functions one translation unit defines and another calls ----------------------
@@ -437,6 +443,9 @@ MWHIP_RT int stepDigestStage(mwhip_exec *exec, const LaunchGraph &lg,
 MWHIP_RT int stepViewStage(mwhip_exec *exec, const LaunchGraph &lg,
                            std::vector<KernelLaunch> &out);
       // (world_view.hip)
+MWHIP_RT int stepReduceStage(mwhip_exec *exec, const LaunchGraph &lg,
+                             std::vector<KernelLaunch> &out);
+      // (world_reduce.hip)
 // head stage of a step replay: behind its input rings, in front of its first
 // task-graph node (buildLaunchList, runtime_launch.hip)
 MWHIP_RT int stepWriteStage(mwhip_exec *exec, const LaunchGraph &lg,

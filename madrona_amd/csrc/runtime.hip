@@ -668,6 +668,7 @@ extern "C" void mwhip_destroy(mwhip_exec *exec)
     exec->digests.clear();
     exec->views.clear();
     exec->writes.clear();
+    exec->reduces.clear();
     for (void *p : exec->allocations) {
         (void)hipFree(p);
     }

@@ -176,7 +176,8 @@ friend class MWCudaExecutor;
 
 namespace detail {
 
-// What MWHipSnapshot, MWHipDigest, MWHipWorldView and MWHipWorldWrite share: the move-only handle
+// What MWHipSnapshot, MWHipDigest, MWHipWorldView, MWHipWorldWrite and
+// MWHipWorldReduce share: the move-only handle
 // of an object that belongs to an executor (mwhip_<kind>_create / _destroy,
 // include/mwhip.h).  Kind: { name, destroy(exec, handle) }.
 template <typename Kind>
@@ -244,6 +245,10 @@ struct WorldViewKind {
 struct WorldWriteKind {
     static constexpr const char *name = "world write";
     static void destroy(mwhip_exec *exec, uint64_t handle) { mwhip_write_destroy(exec, handle); }
+};
+struct WorldReduceKind {
+    static constexpr const char *name = "world reduce";
+    static void destroy(mwhip_exec *exec, uint64_t handle) { mwhip_reduce_destroy(exec, handle); }
 };
 
 }
@@ -430,6 +435,80 @@ private:
 
     uint32_t max_rows_;
     int32_t gpu_id_;
+
+friend class MWCudaExecutor;
+};
+
+// One number per world, element and term about one table, on the device:
+// sums, minima, maxima, largest magnitudes, counts of non-zero and of
+// non-finite values of chosen elements of chosen components over each world's
+// rows in table order, each world's row count, and an alarm word per world
+// that is 1 when a term flagged MWHIP_REDUCE_ALARM trips (mwhip_reduce_*,
+// include/mwhip.h: the exact definition, the float sum's order included).
+// compute() runs one kernel where the table is, sorted or not, and rewrites
+// every tensor in full.  An extension of this backend.  Belongs to the
+// executor that made it and must not outlive it.
+class MWHipWorldReduce : public detail::ExecObject<detail::WorldReduceKind> {
+public:
+    MWHipWorldReduce() : num_terms_(0), gpu_id_(0), is_float_ {} {}
+
+    // waits for the executor's stream
+    void compute() { req(mwhip_reduce_compute(exec_, handle_), "compute"); }
+    // queued on the executor's stream behind the replays queued so far
+    void computeAsync() { req(mwhip_reduce_compute_async(exec_, handle_), "computeAsync"); }
+
+    // [worlds][num_elems] of term `term` (position in the list given to
+    // makeWorldReduce) in the result type: Float32 for SUM / MIN / MAX of F32
+    // and for ABSMAX, Int32 otherwise (py::Tensor has no unsigned 32-bit type:
+    // the u32 results of U32 and U8 terms are those bits)
+    py::Tensor termTensor(uint32_t term) const
+    {
+        uint64_t bytes = 0;
+        uint32_t elems = 0;
+        void *ptr = mwhip_reduce_buffer(exec_, handle_, term, &bytes, &elems);
+        req(ptr != nullptr ? 0 : -1, "termTensor");
+        const int64_t dims[2] = { (int64_t)mwhip_num_worlds(exec_), (int64_t)elems };
+        return py::Tensor(ptr, is_float_[term] ? py::TensorElementType::Float32 :
+                          py::TensorElementType::Int32, Span<const int64_t>(dims, 2),
+                          Optional<int>::make((int)gpu_id_));
+    }
+
+    // int32 [worlds]: each world's rows in the table
+    py::Tensor countsTensor() const
+    {
+        return perWorld(mwhip_reduce_counts(exec_, handle_), "countsTensor");
+    }
+
+    // int32 [worlds]: 1 where an alarm term tripped, else 0
+    py::Tensor alarmTensor() const
+    {
+        return perWorld(mwhip_reduce_alarm(exec_, handle_), "alarmTensor");
+    }
+
+    uint32_t numTerms() const { return num_terms_; }
+
+private:
+    MWHipWorldReduce(mwhip_exec *exec, uint64_t reduce, const mwhip_reduce_term *terms,
+                     uint32_t n, int32_t gpu_id)
+        : ExecObject(exec, reduce), num_terms_(n), gpu_id_(gpu_id), is_float_ {}
+    {
+        for (uint32_t i = 0; i < n && i < MWHIP_REDUCE_MAX_TERMS; i++) {
+            is_float_[i] = terms[i].dtype == MWHIP_REDUCE_F32 &&
+                terms[i].op <= MWHIP_REDUCE_ABSMAX;
+        }
+    }
+
+    py::Tensor perWorld(void *ptr, const char *what) const
+    {
+        req(ptr != nullptr ? 0 : -1, what);
+        const int64_t dims[1] = { (int64_t)mwhip_num_worlds(exec_) };
+        return py::Tensor(ptr, py::TensorElementType::Int32, Span<const int64_t>(dims, 1),
+                          Optional<int>::make((int)gpu_id_));
+    }
+
+    uint32_t num_terms_;
+    int32_t gpu_id_;
+    bool is_float_[MWHIP_REDUCE_MAX_TERMS];
 
 friend class MWCudaExecutor;
 };
@@ -778,6 +857,25 @@ public:
     {
         req(mwhip_set_step_write(exec_, write != nullptr ? write->handle() : 0, on ? 1 : 0),
             "setStepWrite");
+    }
+
+    // per-world reductions of archetype `archetype`'s table, one per term (see
+    // MWHipWorldReduce and mwhip_reduce_term)
+    MWHipWorldReduce makeWorldReduce(uint32_t archetype, const mwhip_reduce_term *terms,
+                                     uint32_t n)
+    {
+        uint64_t reduce = 0;
+        req(mwhip_reduce_create(exec_, archetype, terms, n, &reduce), "makeWorldReduce");
+        return MWHipWorldReduce(exec_, reduce, terms, n, gpu_id_);
+    }
+
+    // on: every replay of a step graph recomputes `reduce` behind its step
+    // views and in front of its pack node and output rings (up to
+    // MWHIP_MAX_STEP_REDUCES reduces, one launch for all); off: no longer
+    void setStepReduce(const MWHipWorldReduce *reduce, bool on)
+    {
+        req(mwhip_set_step_reduce(exec_, reduce != nullptr ? reduce->handle() : 0, on ? 1 : 0),
+            "setStepReduce");
     }
 
     // Device-resident rings (extensions of this backend, include/mwhip.h).

@@ -123,6 +123,13 @@ class DigestColumn(C.Structure):
     _fields_ = [("archetype_id", C.c_uint32), ("component_id", C.c_uint32)]
 
 
+class ReduceTerm(C.Structure):
+    """mwhip_reduce_term (include/mwhip.h)"""
+    _fields_ = [("component_id", C.c_uint32), ("byte_offset", C.c_uint32),
+                ("num_elems", C.c_uint32), ("dtype", C.c_uint32), ("op", C.c_uint32),
+                ("flags", C.c_uint32), ("limit", C.c_float)]
+
+
 class SortStats(C.Structure):
     """mwhip_sort_counters (include/mwhip.h)"""
     _fields_ = [(name, C.c_uint64) for name in
@@ -230,6 +237,22 @@ def runtime_lib() -> C.CDLL:
         fn.argtypes = [C.c_void_p, C.c_uint64]
     lib.mwhip_set_step_write.restype = C.c_int
     lib.mwhip_set_step_write.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
+    lib.mwhip_reduce_create.restype = C.c_int
+    lib.mwhip_reduce_create.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(ReduceTerm),
+                                        C.c_uint32, C.POINTER(C.c_uint64)]
+    lib.mwhip_reduce_destroy.restype = None
+    lib.mwhip_reduce_destroy.argtypes = [C.c_void_p, C.c_uint64]
+    for fn in (lib.mwhip_reduce_compute, lib.mwhip_reduce_compute_async):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_uint64]
+    lib.mwhip_reduce_buffer.restype = C.c_void_p
+    lib.mwhip_reduce_buffer.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32,
+                                        C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    for fn in (lib.mwhip_reduce_counts, lib.mwhip_reduce_alarm):
+        fn.restype = C.c_void_p
+        fn.argtypes = [C.c_void_p, C.c_uint64]
+    lib.mwhip_set_step_reduce.restype = C.c_int
+    lib.mwhip_set_step_reduce.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
     return lib
 
 
@@ -852,6 +875,168 @@ class WorldWrite(_ExecObject):
         self._every_step = bool(on)
 
 
+class WorldReduce(_ExecObject):
+    """One number per world, element and term about ONE table, on the device:
+    per term a [worlds, elems] tensor of sums, minima, maxima, largest
+    magnitudes, counts of non-zero or of non-finite values over each world's
+    rows in table order, plus int32 [worlds] `counts` (each world's rows) and
+    int32 [worlds] `alarm` (1 where a term made with alarm=True trips).
+    madrona_amd/reduce_ref.py is the exact definition, the order of the float
+    sum included; mwhip_reduce_*, include/mwhip.h, computes it with one kernel
+    where the table is, sorted or not.  HIP backend only.
+
+    A term is (column, op) or (column, op, options): op one of "sum", "min",
+    "max", "absmax", "count_nonzero", "count_nonfinite"; options a dict of
+    dtype ("f32", "i32", "u32", "u8"; default f32 for a float column, else u32
+    for cells of whole dwords, else u8), offset (bytes into the cell, default
+    0), elems (default: the rest of the cell), limit and alarm.  `terms` holds
+    them as (column, reduce_ref.Term).
+
+    compute() waits for the executor's stream, compute_async() queues behind
+    the replays queued so far; every compute rewrites every buffer in full.
+    every_step() makes every replay of a step graph recompute the reduce
+    (behind its step views, before its output rings: a ring over buffer_ptr(i)
+    records [K, worlds, elems]; an input ring of one slot over alarm_ptr feeds
+    this step's alarms to the next queued step).  close() frees it;
+    Simulator.close() orphans what is left."""
+
+    _kind, _destroy, _list = "world reduce", "mwhip_reduce_destroy", "_reduces"
+
+    def __init__(self, sim: "Simulator", table: str, terms):
+        from . import reduce_ref
+
+        info = {c[0]: c for c in sim._columns}
+        names = list(info)
+        of_table = [n for n in names if n.split(".", 1)[0] == table]
+        if not of_table:
+            raise KeyError(f"world_reduce(): no table {table!r} in the dump list")
+        if not hasattr(sim.lib, "sim_hip_column_ids"):
+            raise RuntimeError("this simulator library has no sim_hip_column_ids: rebuild it")
+        terms = list(terms)
+        if not terms:
+            raise ValueError("world_reduce(): no terms")
+        self.terms = []
+        for given in terms:
+            column, op = given[0], given[1]
+            options = dict(given[2]) if len(given) > 2 else {}
+            if column not in of_table:
+                raise KeyError(f"world_reduce(): {column!r} is not a column of table {table!r}")
+            if op not in reduce_ref.OPS:
+                raise ValueError(f"world_reduce(): unknown op {op!r}")
+            _, cell, is_float = info[column]
+            dtype = options.pop("dtype", None)
+            if dtype is None:
+                dtype = "f32" if is_float else ("u32" if cell % 4 == 0 else "u8")
+            if dtype not in reduce_ref.DTYPES:
+                raise ValueError(f"world_reduce(): unknown dtype {dtype!r}")
+            item = 1 if dtype == "u8" else 4
+            offset = int(options.pop("offset", 0))
+            elems = options.pop("elems", None)
+            if elems is None:
+                elems = max(cell - offset, 0) // item
+            term = reduce_ref.Term(op, dtype, offset, int(elems),
+                                   float(options.pop("limit", 0.0)),
+                                   bool(options.pop("alarm", False)))
+            if options:
+                raise TypeError(f"world_reduce(): unknown options {sorted(options)}")
+            self.terms.append((column, term))
+        self._sim = sim
+        self.table = table
+        self.num_worlds = sim.num_worlds
+        self._rt = runtime_lib()
+        self._exec = sim.hip_exec()
+        self._tensors = {}
+        self._every_step = False
+        self.handle = 0
+        archetypes = set()
+        arr = (ReduceTerm * len(self.terms))()
+        for p, (column, term) in enumerate(self.terms):
+            arch, comp = C.c_uint32(0), C.c_uint32(0)
+            if sim.lib.sim_hip_column_ids(sim.handle, names.index(column), C.byref(arch),
+                                          C.byref(comp)) != 0:
+                raise RuntimeError(f"sim_hip_column_ids({column}) failed")
+            archetypes.add(arch.value)
+            arr[p] = ReduceTerm(comp.value, min(max(term.offset, 0), 0xFFFFFFFF),
+                                min(max(term.elems, 0), 0xFFFFFFFF),
+                                reduce_ref.DTYPES[term.dtype], reduce_ref.OPS[term.op],
+                                reduce_ref.ALARM if term.alarm else 0, term.limit)
+        assert len(archetypes) == 1, archetypes
+        self.archetype = archetypes.pop()
+        handle = C.c_uint64(0)
+        self._check(self._rt.mwhip_reduce_create(self._exec, self.archetype, arr, len(self.terms),
+                                                 C.byref(handle)), "mwhip_reduce_create")
+        self.handle = int(handle.value)
+        self._buffers = []
+        for p, (_, term) in enumerate(self.terms):
+            nbytes, elems = C.c_uint64(0), C.c_uint32(0)
+            ptr = self._rt.mwhip_reduce_buffer(self._exec, self.handle, p, C.byref(nbytes),
+                                               C.byref(elems))
+            assert ptr and elems.value == term.elems and \
+                nbytes.value == self.num_worlds * term.elems * 4
+            self._buffers.append((int(ptr), reduce_ref.result_dtype(term)))
+        self.counts_ptr = int(self._rt.mwhip_reduce_counts(self._exec, self.handle) or 0)
+        self._alarm_ptr = int(self._rt.mwhip_reduce_alarm(self._exec, self.handle) or 0)
+
+    def _orphan(self) -> None:
+        super()._orphan()
+        self._tensors = {}
+
+    def compute(self) -> "WorldReduce":
+        """Rewrites every buffer; waits for the executor's stream."""
+        self._check(self._rt.mwhip_reduce_compute(self._exec, self._live()),
+                    "mwhip_reduce_compute")
+        return self
+
+    def compute_async(self) -> None:
+        self._check(self._rt.mwhip_reduce_compute_async(self._exec, self._live()),
+                    "mwhip_reduce_compute_async")
+
+    def buffer_ptr(self, i: int) -> int:
+        """Device address of term i's [worlds, elems] results (4 bytes each)."""
+        self._live()
+        return self._buffers[i][0]
+
+    @property
+    def alarm_ptr(self) -> int:
+        """Device address of the int32 [worlds] alarm buffer."""
+        self._live()
+        return self._alarm_ptr
+
+    _wrap = WorldView._wrap
+
+    def tensor(self, i: int):
+        """torch [worlds, elems] over the device buffer of term i (no copy) in
+        the result type: float32, int32 or uint32."""
+        self._live()
+        ptr, dtype = self._buffers[i]
+        return self._wrap((i, dtype.str), ptr, dtype.type,
+                          (self.num_worlds, self.terms[i][1].elems))
+
+    @property
+    def counts(self):
+        """torch int32 [worlds] over the device buffer (no copy): each world's
+        rows in the table as the last compute found them."""
+        self._live()
+        return self._wrap(("", "counts"), self.counts_ptr, np.int32, (self.num_worlds,))
+
+    @property
+    def alarm(self):
+        """torch int32 [worlds] over the device buffer (no copy): 1 where an
+        alarm term tripped in the last compute, else 0."""
+        self._live()
+        return self._wrap(("", "alarm"), self._alarm_ptr, np.int32, (self.num_worlds,))
+
+    def every_step(self, on: bool = True) -> None:
+        """Every replay of a step graph recomputes this reduce (waits for the
+        stream and rebuilds the launch graphs); on=False turns it off again."""
+        handle = self._live()
+        if not on and not self._every_step:
+            return
+        self._check(self._rt.mwhip_set_step_reduce(self._exec, handle, 1 if on else 0),
+                    "mwhip_set_step_reduce")
+        self._every_step = bool(on)
+
+
 class Simulator:
     """One simulator instance behind the C API (either backend)."""
 
@@ -880,6 +1065,7 @@ class Simulator:
         self._digests: List["StateDigest"] = []
         self._views: List["WorldView"] = []
         self._writes: List["WorldWrite"] = []
+        self._reduces: List["WorldReduce"] = []
         self._tensor_info: Dict[str, Tuple[int, np.dtype, Tuple[int, ...], bool]] = {}
         for i in range(self.lib.sim_num_tensors(self.handle)):
             info = SimTensorInfo()
@@ -897,10 +1083,10 @@ class Simulator:
     def close(self) -> None:
         if self.handle:
             # sim_destroy frees the executor and with it its snapshots, digests,
-            # world views and world writes, and forgets its output rings (the
-            # trajectories keep their tensors)
+            # world views, world writes and world reduces, and forgets its output
+            # rings (the trajectories keep their tensors)
             for open_ones in (self._snapshots, self._trajectories, self._digests, self._views,
-                              self._writes):
+                              self._writes, self._reduces):
                 for obj in open_ones:
                     obj._orphan()
                 open_ones.clear()
@@ -1068,6 +1254,17 @@ class Simulator:
         write = WorldWrite(self, table, columns, max_rows)
         self._writes.append(write)
         return write
+
+    def world_reduce(self, table: str, terms) -> "WorldReduce":
+        """A WorldReduce of table `table`: one result per world and element for
+        every term -- (column, op) or (column, op, options), see WorldReduce --
+        plus each world's row count and an alarm word per world.  HIP backend;
+        raises on the reference backend, which has no executor to ask."""
+        if self.backend != "hip":
+            raise RuntimeError(f"world reduces need the HIP backend, this is {self.backend!r}")
+        reduce = WorldReduce(self, table, terms)
+        self._reduces.append(reduce)
+        return reduce
 
     def record(self, names: List[str], steps: int, on_render: bool = False) -> "Trajectory":
         """Records the exported tensors `names` on the device from the next

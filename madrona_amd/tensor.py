@@ -13,7 +13,7 @@ import numpy as np
 _TYPESTR = {
     np.dtype(np.uint8): "|u1", np.dtype(np.int8): "|i1", np.dtype(np.int16): "<i2",
     np.dtype(np.int32): "<i4", np.dtype(np.int64): "<i8", np.dtype(np.float16): "<f2",
-    np.dtype(np.float32): "<f4",
+    np.dtype(np.float32): "<f4", np.dtype(np.uint32): "<u4",
 }
 
 

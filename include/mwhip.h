@@ -221,6 +221,17 @@ typedef struct mwhip_sort_counters {
  * -2: the device could not be read */
 int mwhip_sort_stats(mwhip_exec *exec, uint32_t archetype_id,
                      mwhip_sort_counters *out);
+/* Row reuse (Context::destroyEntityOrdered / makeEntityOrdered with
+ * OrderedRows::Reuse; MADRONA_MWHIP_ROW_REUSE=0 turns it off): rows created in
+ * the slot a destroy of the same invocation freed, and world sorts of the table
+ * that found every hole refilled that way and did nothing (they are not counted
+ * in mwhip_sort_counters::runs).  Same return values as mwhip_sort_stats. */
+typedef struct mwhip_sort_reuse_counters {
+    uint64_t skipped_runs;
+    uint64_t rows_reused;
+} mwhip_sort_reuse_counters;
+int mwhip_sort_reuse_stats(mwhip_exec *exec, uint32_t archetype_id,
+                           mwhip_sort_reuse_counters *out);
 /* the persistent region's current bump offset in bytes (device rawAlloc /
  * HostAllocator: mwhip::persistAlloc, 16-B granules): right after creation,
  * what the last constructor pass took; device code that allocates there while

@@ -1238,6 +1238,28 @@ extern "C" int mwhip_sort_stats(mwhip_exec *exec, uint32_t archetype_id,
     return 0;
 }
 
+extern "C" int mwhip_sort_reuse_stats(mwhip_exec *exec, uint32_t archetype_id,
+                                      mwhip_sort_reuse_counters *out)
+{
+    *out = mwhip_sort_reuse_counters {};
+    if (archetype_id >= exec->archetypes.size()) {
+        return -1;
+    }
+    const ArchetypeRec &arch = exec->archetypes[archetype_id];
+    if (!arch.registered || arch.sortState == nullptr) {
+        return 1;
+    }
+    SortState state;
+    if (hipStreamSynchronize(exec->stream) != hipSuccess ||
+        hipMemcpy(&state, arch.sortState, sizeof(state),
+                  hipMemcpyDeviceToHost) != hipSuccess) {
+        return -2;
+    }
+    out->skipped_runs = state.statSkipRuns;
+    out->rows_reused = state.statRowsReused;
+    return 0;
+}
+
 extern "C" uint64_t mwhip_persist_bytes_used(mwhip_exec *exec)
 {
     // the region's bump offset: every constructor pass starts it over, and

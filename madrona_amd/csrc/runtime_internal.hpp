@@ -83,6 +83,12 @@ struct SortState {
     uint32_t stayMoved;             // this run: surviving prefix rows that change position
     unsigned long long statStayRuns;    // cumulative: compaction runs that stayed in place
     unsigned long long statRowsCopied;  // cumulative: rows the gather copied per column
+    // row reuse (TableHdr::orderedFreed): the chain's first kernel found every
+    // hole refilled in place and the run did nothing
+    unsigned long long statSkipRuns;    // cumulative: runs skipped that way
+    unsigned long long statRowsReused;  // cumulative: rows created in a freed slot
+    uint32_t reuseSeen;                 // TableHdr::orderedRefilled already counted
+    uint32_t pad_;
 };
 
 struct SortSite {

@@ -313,6 +313,9 @@ MWHIP_RT int buildDeviceState(mwhip_exec *exec)
     hs.initMode = 0;
     hs.errorFlags = 0;
     hs.hostExec = nullptr;
+    // MADRONA_MWHIP_ROW_REUSE=0: OrderedRows::Reuse creates append like any
+    // other (madrona/state.inl), and no world sort finds its table refilled
+    hs.rowReuse = envU32("MADRONA_MWHIP_ROW_REUSE", 1) != 0 ? 1u : 0u;
 
     // ---- singletons: one row per world, ids in (singleton, world) order -------
     // (reference CPU state.inl:163-179: k-th created singleton entity gets id k)

@@ -335,6 +335,10 @@ int layoutSnapshot(mwhip_exec *exec, std::vector<SnapSegment> &out, uint64_t *da
             static_assert(offsetof(TableHdr, tailRows) ==
                           offsetof(TableHdr, sortedRows) + sizeof(int32_t));
             add_fixed(&hdr->sortedRows, 2 * sizeof(int32_t));
+            // (whether the holes of the saved step have all been refilled)
+            static_assert(offsetof(TableHdr, plainDestroys) ==
+                          offsetof(TableHdr, orderedFreed) + 2 * sizeof(uint32_t));
+            add_fixed(&hdr->orderedFreed, 3 * sizeof(uint32_t));
             add_fixed(arch.worldOffsets, (uint64_t)W * sizeof(int32_t));
             add_fixed(arch.worldCounts, (uint64_t)W * sizeof(int32_t));
         }

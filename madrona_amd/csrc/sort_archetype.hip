@@ -157,6 +157,42 @@ __device__ inline uint32_t blockExclusiveScan256(uint32_t v, uint32_t *scratch,
     return wave_base + incl - v;
 }
 
+// A world-sorted table whose only changes since its last sort are rows freed
+// at the end of their world's range and created again in the same slots
+// (OrderedRows::Reuse, madrona/state.inl; TableHdr::orderedFreed): every row is
+// where this sort would put it.  Appends, ClearTmp, setNeedsSort and key sorts
+// all break numRows == sortedRows > 0.  Every workgroup of a chain's first
+// kernel evaluates this on the same header words; workgroup 0 then clears
+// needsSort (noteRefilled), and a workgroup that reads the cleared flag is
+// inactive by the old rule.  `needs_sort` is the caller's one read of the flag.
+__device__ inline bool tableRefilled(const TableHdr &tbl, uint32_t needs_sort)
+{
+    const int32_t sorted = tbl.sortedRows;
+    return needs_sort != 0u && sorted > 0 && tbl.numRows == sorted &&
+        tbl.plainDestroys == 0u && tbl.orderedFreed == tbl.orderedRefilled;
+}
+
+// Rows created in a freed slot since they were last counted (one thread of a
+// site's workgroup 0).  A restored snapshot brings its own header counters: a
+// count that ran backwards starts over.
+__device__ inline void countReusedRows(SortState *state, const TableHdr &tbl,
+                                       bool publishing)
+{
+    const uint32_t refilled = tbl.orderedRefilled;
+    const uint32_t seen = state->reuseSeen;
+    state->statRowsReused += refilled >= seen ? refilled - seen : refilled;
+    state->reuseSeen = publishing ? 0u : refilled;
+}
+
+// one thread of a site's workgroup 0, for a run that tableRefilled() skips
+// (the two counters stay as they are, equal: other workgroups still read them)
+__device__ inline void noteRefilled(SortState *state, TableHdr &tbl)
+{
+    state->statSkipRuns += 1ull;
+    countReusedRows(state, tbl, false);
+    tbl.needsSort = 0u;
+}
+
 // ---------------------------------------------------------------------------
 // kernel 1: histogram of every pass's digit + survivors + clear offsets
 // ---------------------------------------------------------------------------
@@ -173,8 +209,13 @@ sortHistogram(EcsState *S, const SortSite *sites)
 
     // nothing below this kernel looks at the table header again to decide
     // whether (or what) to sort
-    const bool active = site.worldSort == 0u || tbl.needsSort != 0u;
+    const uint32_t needs_sort = tbl.needsSort;
+    const bool refilled = site.worldSort != 0u && tableRefilled(tbl, needs_sort);
+    const bool active = site.worldSort == 0u || (needs_sort != 0u && !refilled);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (refilled) {
+            noteRefilled(state, tbl);
+        }
         state->active = active ? 1u : 0u;
         state->rowsIn = n;
         state->keyColumn = keys;
@@ -281,6 +322,11 @@ __device__ inline void publishSite(EcsState *S, const SortSite &site,
         // are stale until then (reference sort_archetype.cpp:1001-1007).
         tbl.needsSort = site.worldSort ? 0u : 1u;
         tbl.sortedRows = site.worldSort ? n_out : 0;
+        // (no hole is left that a reused row could be waiting for)
+        countReusedRows(state, tbl, true);
+        tbl.orderedFreed = 0u;
+        tbl.orderedRefilled = 0u;
+        tbl.plainDestroys = 0u;
     }
 }
 
@@ -1323,7 +1369,14 @@ sortSmall(EcsState *S, const SortSite *sites, const GatherColumn *columns,
     }
     const SortSite &site = sites[blockIdx.x];
     TableHdr &tbl = S->tables[site.archetype];
-    if (site.worldSort && tbl.needsSort == 0u) {
+    const uint32_t needs_sort = tbl.needsSort;
+    if (site.worldSort && needs_sort == 0u) {
+        return;
+    }
+    if (site.worldSort && tableRefilled(tbl, needs_sort)) {
+        if (threadIdx.x == 0) {
+            noteRefilled(site.state, tbl);
+        }
         return;
     }
 
@@ -1502,7 +1555,9 @@ sortCompactPrepare(EcsState *S, const SortSite *sites)
     SortState *state = site.state;
 
     // (the header does not change before the scatter kernel publishes)
-    const bool active = tbl.needsSort != 0u;
+    const uint32_t needs_sort = tbl.needsSort;
+    const bool refilled = tableRefilled(tbl, needs_sort);
+    const bool active = needs_sort != 0u && !refilled;
     const int32_t n = tbl.numRows;
     int32_t prefix = tbl.sortedRows;
     if (prefix < 0 || prefix > n) {
@@ -1517,6 +1572,9 @@ sortCompactPrepare(EcsState *S, const SortSite *sites)
     const uint32_t blocked = state->landsBlocked;
     const bool by_lands = compactTailByLands(prefix, tail, blocked);
     if (blockIdx.x == 0 && tid == 0) {
+        if (refilled) {
+            noteRefilled(state, tbl);
+        }
         state->active = active ? 1u : 0u;
         state->rowsIn = n;
         state->keyColumn = keys;

@@ -70,18 +70,27 @@ public:
     // lanes call together; the effect -- entity ids, generations, row order --
     // is that of the lanes with `want` calling makeEntity / destroyEntity one
     // after the other in lane order (state.hpp) ----
+    // OrderedRows::Reuse (both calls): rows the destroy frees at the end of
+    // the world's range of a table are handed to the creates that follow in
+    // the same invocation, so a world that destroys its level and builds it
+    // again leaves the table in world order.  The caller promises that the
+    // running node does not iterate the tables it replaces rows in
+    // (INTEGRATION.md, section 3).  Ids and generations are the same either way.
     template <typename ArchetypeT>
-    MADRONA_HD inline Entity makeEntityOrdered(bool want)
+    MADRONA_HD inline Entity makeEntityOrdered(
+        bool want, OrderedRows rows = OrderedRows::Append)
     {
-        return makeEntityOrdered(TypeTracker::typeID<ArchetypeT>(), want);
+        return makeEntityOrdered(TypeTracker::typeID<ArchetypeT>(), want, rows);
     }
 
     // (lanes may ask for different archetypes: ids still go out in lane order)
-    MADRONA_HD inline Entity makeEntityOrdered(uint32_t archetype_id, bool want)
+    MADRONA_HD inline Entity makeEntityOrdered(
+        uint32_t archetype_id, bool want, OrderedRows rows = OrderedRows::Append)
     {
         Loc loc { 0, 0 };
         Entity e = state_mgr_->makeEntityOrdered(world_id_, archetype_id, want,
-                                                 exclusive_world_, &loc);
+            exclusive_world_, &loc,
+            rows == OrderedRows::Reuse ? &row_reuse_ : nullptr);
         if (want) {
             cached_id_ = e.id;
             cached_gen_ = e.gen;
@@ -90,12 +99,14 @@ public:
         return e;
     }
 
-    MADRONA_HD inline void destroyEntityOrdered(Entity e, bool want)
+    MADRONA_HD inline void destroyEntityOrdered(
+        Entity e, bool want, OrderedRows rows = OrderedRows::Append)
     {
         if (want && e.id == cached_id_) {
             cached_id_ = -1;
         }
-        state_mgr_->destroyEntityOrdered(world_id_, e, want, exclusive_world_);
+        state_mgr_->destroyEntityOrdered(world_id_, e, want, exclusive_world_,
+            rows == OrderedRows::Reuse ? &row_reuse_ : nullptr);
     }
 
     MADRONA_HD inline Loc loc(Entity e) const
@@ -198,6 +209,9 @@ private:
     int32_t cached_id_;
     uint32_t cached_gen_;
     Loc cached_loc_;
+    // rows freed by an OrderedRows::Reuse destroy of this invocation, waiting
+    // for its creates; dropped with the Context (the rows are ordinary holes)
+    RowReuseRecords row_reuse_;
 };
 
 }

@@ -122,6 +122,18 @@ struct TableHdr {
     // rows behind the sorted prefix at the largest world sort of the running
     // step (health kernel: read and reset)
     int32_t tailRows;
+    // Row reuse (Context::destroyEntityOrdered / makeEntityOrdered with
+    // OrderedRows::Reuse, state.inl).  Since the last world sort that really
+    // ran: rows freed as the suffix of their world's range by a wavefront that
+    // remembered them, rows created straight into such slots, and whether
+    // anything else destroyed a row.  When the first two are equal, the third
+    // is 0 and nothing was appended (numRows == sortedRows), every hole has
+    // been filled with the row the sort would have moved there: the table is in
+    // world order and the first kernel of the sort chain says so.  Zeroed where
+    // a world sort publishes the table.
+    uint32_t orderedFreed;
+    uint32_t orderedRefilled;
+    uint32_t plainDestroys;
 };
 
 // == IDMap::Node with V = Loc (reference impl/id_map.hpp:41-53): a live slot
@@ -228,8 +240,10 @@ struct EcsState {
 
     void *hostExec;                 // host mirror only: owning mwhip_exec*
     int32_t runtimeIdBase;          // first id of the post-init block partition
-    int32_t pad_;
-    void *moduleData[4];            // module-private device pointers (physics scratch, ...)
+    // 0: OrderedRows::Reuse behaves as OrderedRows::Append
+    // (MADRONA_MWHIP_ROW_REUSE=0, read when the executor is created)
+    uint32_t rowReuse;
+    void *moduleData[4];           // module-private device pointers (physics scratch, ...)
     HostPrintRing *hostPrintRing;   // pinned host memory, or nullptr
     // replays completed so far (bumped by the last kernel of every replay):
     // with a node's position in the graph, a unique tag per launch

@@ -52,6 +52,26 @@ inline void check(int rc, const char *what)
 
 }
 
+// Where Context::makeEntityOrdered / destroyEntityOrdered take and leave rows.
+//   Append  rows are appended, destroyed rows stay behind as holes until the
+//           next world sort
+//   Reuse   a create takes the rows an earlier destroy of the same invocation
+//           freed at the end of its world's range (StateManager below)
+enum class OrderedRows : uint32_t { Append = 0, Reuse = 1 };
+
+// What a wavefront remembers between an OrderedRows::Reuse destroy and the
+// creates that follow it: per archetype, the next freed row and how many are
+// left.  Every value is the same in all lanes (scalar registers).
+struct RowReuseRecords {
+    static constexpr int32_t maxRecords = 4;
+    static constexpr uint32_t noArchetype = 0xFFFFFFFFu;
+
+    uint32_t archetype[maxRecords] { noArchetype, noArchetype, noArchetype,
+                                     noArchetype };
+    int32_t nextRow[maxRecords] { 0, 0, 0, 0 };
+    int32_t remaining[maxRecords] { 0, 0, 0, 0 };
+};
+
 class StateManager : public mwhip::EcsState {
 public:
     // ---- host: registration (reference device state.inl:7-158) -------------
@@ -134,10 +154,18 @@ public:
     // lane order -- at the latency of one such call: rows come from one atomic,
     // a single lane walks the id free list, everything else is per lane.
     // destroy: the wanted entities must be distinct.
+    // reuse != nullptr (OrderedRows::Reuse): a destroy that frees exactly the
+    // last k rows of its world's range in a world-sorted table remembers them,
+    // and a later create of the same invocation puts its rows of that
+    // archetype there, in lane order, before it appends any.  That is where
+    // the next world sort would have moved them: a table whose every hole is
+    // refilled this way is still in world order (TableHdr::orderedFreed).
     MADRONA_HD Entity makeEntityOrdered(WorldID world_id, uint32_t archetype_id,
-                                        bool want, bool exclusive, Loc *loc_out);
+                                        bool want, bool exclusive, Loc *loc_out,
+                                        RowReuseRecords *reuse = nullptr);
     MADRONA_HD void destroyEntityOrdered(WorldID caller_world, Entity e, bool want,
-                                         bool exclusive);
+                                         bool exclusive,
+                                         RowReuseRecords *reuse = nullptr);
     MADRONA_HD void clearTemporaries(uint32_t archetype_id);
 
     template <typename ArchetypeT, typename ComponentT>

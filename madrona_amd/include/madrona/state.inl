@@ -424,6 +424,7 @@ MADRONA_HD inline void StateManager::destroyEntityNow(WorldID caller_world, Enti
     ((Entity *)mwhip::columnOf(tbl, 0))[loc.row] = Entity::none();
     ((WorldID *)mwhip::columnOf(tbl, 1))[loc.row] = WorldID { -1 };
     tbl.needsSort = 1u;
+    tbl.plainDestroys = 1u;
 
     if (exclusive) {
         mwhip::releaseIdLocked(this,
@@ -442,7 +443,7 @@ MADRONA_HD inline void StateManager::destroyEntityNow(WorldID caller_world, Enti
 
 MADRONA_HD inline Entity StateManager::makeEntityOrdered(
     WorldID world_id, uint32_t archetype_id, bool want, bool exclusive,
-    Loc *loc_out)
+    Loc *loc_out, RowReuseRecords *reuse)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ int32_t ordered_ids[64];
@@ -452,6 +453,7 @@ MADRONA_HD inline Entity StateManager::makeEntityOrdered(
     if (mask == 0) {
         return Entity::none();
     }
+    const bool reuse_on = reuse != nullptr && mwhip::loadInvariant(&rowReuse) != 0u;
     const uint32_t lane =
         __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     const uint32_t count = (uint32_t)__builtin_popcountll(mask);
@@ -486,21 +488,48 @@ MADRONA_HD inline Entity StateManager::makeEntityOrdered(
     int32_t my_row = 0;
     for (uint64_t remaining = mask; remaining != 0; ) {
         const uint32_t first_lane = (uint32_t)__builtin_ctzll(remaining);
-        const uint32_t arch = (uint32_t)__shfl((int)archetype_id, (int)first_lane, 64);
+        uint32_t arch = (uint32_t)__shfl((int)archetype_id, (int)first_lane, 64);
+        if (reuse_on) {
+            arch = __builtin_amdgcn_readfirstlane(arch);
+        }
         const uint64_t same =
             __builtin_amdgcn_ballot_w64(want && archetype_id == arch);
+        const int32_t num_same = (int32_t)__builtin_popcountll(same);
+        // rows an OrderedRows::Reuse destroy of this invocation left for this
+        // archetype: the first reuse_n lanes take them, the others append
+        int32_t reuse_n = 0, reuse_row = 0;
+        if (reuse_on) {
+#pragma unroll
+            for (int32_t i = 0; i < RowReuseRecords::maxRecords; i++) {
+                if (reuse->archetype[i] == arch && reuse->remaining[i] > 0) {
+                    reuse_n = reuse->remaining[i] < num_same ?
+                        reuse->remaining[i] : num_same;
+                    reuse_row = reuse->nextRow[i];
+                    reuse->nextRow[i] += reuse_n;
+                    reuse->remaining[i] -= reuse_n;
+                }
+            }
+        }
         int32_t first_row = 0;
         if (lane == first_lane) {
             mwhip::TableHdr &shared_tbl = mwhip::tablesOf(this)[arch];
-            mwhip::markRowAppender();
-            shared_tbl.needsSort = 1u;
-            first_row = mwhip::atomicAddI32(&shared_tbl.numRows,
-                                            (int32_t)__builtin_popcountll(same));
+            if (reuse_n != 0) {
+                (void)__hip_atomic_fetch_add(&shared_tbl.orderedRefilled,
+                    (uint32_t)reuse_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            if (num_same > reuse_n) {
+                mwhip::markRowAppender();
+                shared_tbl.needsSort = 1u;
+                first_row = mwhip::atomicAddI32(&shared_tbl.numRows,
+                                                num_same - reuse_n);
+            }
         }
         first_row = __shfl(first_row, (int)first_lane, 64);
         if (want && archetype_id == arch) {
-            my_row = first_row +
+            const int32_t among =
                 (int32_t)__builtin_popcountll(same & ((1ull << lane) - 1ull));
+            my_row = among < reuse_n ? reuse_row + among :
+                                       first_row + (among - reuse_n);
         }
         remaining &= ~same;
     }
@@ -533,32 +562,41 @@ MADRONA_HD inline Entity StateManager::makeEntityOrdered(
     return e;
 #else
     (void)world_id; (void)archetype_id; (void)want; (void)exclusive; (void)loc_out;
+    (void)reuse;
     mwhip::hostOnlyAbort("makeEntityOrdered"); return Entity::none();
 #endif
 }
 
 MADRONA_HD inline void StateManager::destroyEntityOrdered(
-    WorldID caller_world, Entity e, bool want, bool exclusive)
+    WorldID caller_world, Entity e, bool want, bool exclusive,
+    RowReuseRecords *reuse)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ int32_t ordered_ids[64];
     __shared__ uint32_t ordered_gens[64];
+
+    const bool reuse_on = reuse != nullptr && mwhip::loadInvariant(&rowReuse) != 0u;
 
     // every lane looks at its own entity (stale handles are ignored, as in
     // destroyEntityNow) and tags its row -- before any id goes back: a free
     // slot's links overwrite the location
     bool valid = false;
     uint32_t slot_gen = 0;
+    Loc freed { 0, 0 };
     if (want && e.id >= 0) {
         const mwhip::EntitySlot &slot = mwhip::entitiesOf(this)[e.id];
         slot_gen = slot.gen;
         const Loc loc { slot.loc.archetype, slot.loc.row };
         if (slot_gen == e.gen) {
             valid = true;
+            freed = loc;
             mwhip::TableHdr &tbl = mwhip::tablesOf(this)[loc.archetype];
             ((Entity *)mwhip::columnOf(tbl, 0))[loc.row] = Entity::none();
             ((WorldID *)mwhip::columnOf(tbl, 1))[loc.row] = WorldID { -1 };
             tbl.needsSort = 1u;
+            if (!reuse_on) {
+                tbl.plainDestroys = 1u;
+            }
         }
     }
 
@@ -568,6 +606,74 @@ MADRONA_HD inline void StateManager::destroyEntityOrdered(
     }
     const uint32_t lane =
         __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+
+    if (reuse_on) {
+        // Per archetype among the valid lanes: are the freed rows exactly the
+        // last k of this world's range [a, a + c) of the sorted prefix?  They
+        // are distinct, so "all of them in [a + c - k, a + c)" says so.  Then
+        // the creates of this invocation may take them (makeEntityOrdered);
+        // otherwise they are holes like any other.
+        const int32_t w = __builtin_amdgcn_readfirstlane(caller_world.idx);
+        const bool one_world =
+            __builtin_amdgcn_ballot_w64(valid && caller_world.idx != w) == 0;
+        for (uint64_t todo = mask; todo != 0; ) {
+            const uint32_t first_lane = (uint32_t)__builtin_ctzll(todo);
+            const uint32_t arch = __builtin_amdgcn_readfirstlane(
+                (uint32_t)__shfl((int)freed.archetype, (int)first_lane, 64));
+            const bool mine = valid && freed.archetype == arch;
+            const uint64_t same = __builtin_amdgcn_ballot_w64(mine);
+            const int32_t k = (int32_t)__builtin_popcountll(same);
+
+            mwhip::TableHdr &tbl = mwhip::tablesOf(this)[arch];
+            // (the same in every lane, and said so: what is derived from them
+            // stays in scalar registers until the creates)
+            const int32_t sorted = __builtin_amdgcn_readfirstlane(tbl.sortedRows);
+            int32_t a = 0, c = 0;
+            if (one_world && sorted > 0) {
+                a = __builtin_amdgcn_readfirstlane(
+                    mwhip::loadInvariant(&tbl.worldOffsets)[w]);
+                c = __builtin_amdgcn_readfirstlane(
+                    mwhip::loadInvariant(&tbl.worldCounts)[w]);
+            }
+            const int32_t end = a + c;
+            const uint64_t outside = __builtin_amdgcn_ballot_w64(
+                mine && (freed.row < end - k || freed.row >= end));
+            bool ok = one_world && sorted > 0 && a >= 0 && k <= c &&
+                end <= sorted && outside == 0;
+            // one record per archetype, RowReuseRecords::maxRecords in all
+            int32_t at = -1;
+#pragma unroll
+            for (int32_t i = RowReuseRecords::maxRecords - 1; i >= 0; i--) {
+                if (reuse->archetype[i] == RowReuseRecords::noArchetype) {
+                    at = i;
+                }
+            }
+#pragma unroll
+            for (int32_t i = 0; i < RowReuseRecords::maxRecords; i++) {
+                if (reuse->archetype[i] == arch) {
+                    ok = false;
+                }
+            }
+            ok = ok && at >= 0;
+#pragma unroll
+            for (int32_t i = 0; i < RowReuseRecords::maxRecords; i++) {
+                if (ok && i == at) {
+                    reuse->archetype[i] = arch;
+                    reuse->nextRow[i] = end - k;
+                    reuse->remaining[i] = k;
+                }
+            }
+            if (lane == first_lane) {
+                if (ok) {
+                    (void)__hip_atomic_fetch_add(&tbl.orderedFreed, (uint32_t)k,
+                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                } else {
+                    tbl.plainDestroys = 1u;
+                }
+            }
+            todo &= ~same;
+        }
+    }
     const uint32_t count = (uint32_t)__builtin_popcountll(mask);
     const uint32_t rank =
         (uint32_t)__builtin_popcountll(mask & ((1ull << lane) - 1ull));
@@ -599,7 +705,7 @@ MADRONA_HD inline void StateManager::destroyEntityOrdered(
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 #else
-    (void)caller_world; (void)e; (void)want; (void)exclusive;
+    (void)caller_world; (void)e; (void)want; (void)exclusive; (void)reuse;
     mwhip::hostOnlyAbort("destroyEntityOrdered");
 #endif
 }

@@ -136,6 +136,11 @@ class SortStats(C.Structure):
                 ("runs", "stay_runs", "rows_copied", "rows_in", "rows_out", "tail_rows")]
 
 
+class SortReuseStats(C.Structure):
+    """mwhip_sort_reuse_counters (include/mwhip.h)"""
+    _fields_ = [("skipped_runs", C.c_uint64), ("rows_reused", C.c_uint64)]
+
+
 def _torch_runtime_first() -> None:
     """PyTorch-ROCm bundles its own HIP / HSA runtime; a process that loads the
     system runtime first (through our libraries) and torch afterwards ends up
@@ -1198,10 +1203,15 @@ class Simulator:
         a sort node, by archetype id (mwhip_sort_stats; HIP backend): runs,
         stay_runs (compaction runs that patched the new rows in place),
         rows_copied (rows the gather copied per column), rows_in, rows_out,
-        tail_rows.  Waits for the executor's stream."""
+        tail_rows, and of row reuse (mwhip_sort_reuse_stats) skipped_runs (world
+        sorts that found every hole refilled in place and did nothing) and
+        rows_reused.  Waits for the executor's stream."""
         rt = runtime_lib()
         rt.mwhip_sort_stats.restype = C.c_int32
         rt.mwhip_sort_stats.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(SortStats)]
+        rt.mwhip_sort_reuse_stats.restype = C.c_int32
+        rt.mwhip_sort_reuse_stats.argtypes = [C.c_void_p, C.c_uint32,
+                                              C.POINTER(SortReuseStats)]
         out = {}
         archetype = 0
         while True:
@@ -1213,6 +1223,12 @@ class Simulator:
                 raise RuntimeError(f"mwhip_sort_stats({archetype}) -> {rc}")
             if rc == 0:
                 out[archetype] = {name: int(getattr(st, name)) for name, _ in st._fields_}
+                reuse = SortReuseStats()
+                rc = rt.mwhip_sort_reuse_stats(self.hip_exec(), archetype, C.byref(reuse))
+                if rc != 0:
+                    raise RuntimeError(f"mwhip_sort_reuse_stats({archetype}) -> {rc}")
+                out[archetype].update(skipped_runs=int(reuse.skipped_runs),
+                                      rows_reused=int(reuse.rows_reused))
             archetype += 1
 
     def snapshot(self) -> "Snapshot":

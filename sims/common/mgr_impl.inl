@@ -127,6 +127,15 @@ static void describeFlagTensors(List &out, const SimCreateArgs &args)
         T::describeFlagTensors(out, args);
     }
 }
+
+// optional: dumped columns of tables that depend on the creation flags
+template <typename T, typename List>
+static void describeFlagColumns(List &cols, const SimCreateArgs &args)
+{
+    if constexpr (requires { T::describeFlagColumns(cols, args); }) {
+        T::describeFlagColumns(cols, args);
+    }
+}
 }
 
 #ifndef SIM_BACKEND_REF_CPU
@@ -231,6 +240,7 @@ SimHandle *sim_create(const SimCreateArgs *args)
     Traits::describeTensors(h->tensors, args->num_worlds);
     simmgr::describeFlagTensors<Traits>(h->tensors, *args);
     Traits::describeColumns(h->columns);
+    simmgr::describeFlagColumns<Traits>(h->columns, *args);
 
     return h;
 }

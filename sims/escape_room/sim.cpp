@@ -540,7 +540,8 @@ static inline void resetWorldWave(Engine &ctx)
                 (k == consts::numCubesPerRoom ? room.door :
                  room.buttons[k - consts::numCubesPerRoom - 1]);
         }
-        ctx.destroyEntityOrdered(e, in_level);
+        // (generateLevel() below creates as many of each: they take these rows)
+        ctx.destroyEntityOrdered(e, in_level, OrderedRows::Reuse);
     }
 
     // ---- initWorld() ----
@@ -595,7 +596,7 @@ static inline void resetWorldWave(Engine &ctx)
     const uint32_t archetype = is_button ? TypeTracker::typeID<ButtonEntity>() :
         (is_door ? TypeTracker::typeID<DoorEntity>() :
                    TypeTracker::typeID<PhysicsEntity>());
-    const Entity e = ctx.makeEntityOrdered(archetype, in_level);
+    const Entity e = ctx.makeEntityOrdered(archetype, in_level, OrderedRows::Reuse);
 
     // (the door wants its room's buttons)
     Entity room_buttons[consts::numButtonsPerRoom];

@@ -804,7 +804,10 @@ static inline void resetWorldWave(Engine &ctx)
             }
 #endif
         }
-        ctx.destroyEntityOrdered(e, want);
+        // (the level's rows end this world's range in every table, and
+        // generateLevel() below creates as many: they take these rows again;
+        // nothing in this node iterates those tables)
+        ctx.destroyEntityOrdered(e, want, OrderedRows::Reuse);
     }
 
     // ---- initWorld() ----
@@ -882,7 +885,7 @@ static inline void resetWorldWave(Engine &ctx)
         archetype = TypeTracker::typeID<render::RenderableArchetype>();
     }
 #endif
-    const Entity e = ctx.makeEntityOrdered(archetype, on_level);
+    const Entity e = ctx.makeEntityOrdered(archetype, on_level, OrderedRows::Reuse);
 
     // (the door wants its room's buttons, a body its render entity)
     Entity room_buttons[consts::numButtonsPerRoom];

@@ -641,7 +641,8 @@ static inline void resetWorldWave(Engine &ctx)
                 (is_ramp ? level.ramps[lane - consts::numBoxes] :
                  level.walls[lane - consts::numBoxes - consts::numRamps]);
         }
-        ctx.destroyEntityOrdered(e, on_level);
+        // (generateLevel() below creates as many of each: they take these rows)
+        ctx.destroyEntityOrdered(e, on_level, OrderedRows::Reuse);
     }
 
     // ---- initWorld() ----
@@ -713,7 +714,7 @@ static inline void resetWorldWave(Engine &ctx)
     // generateLevel(): boxes, ramps (MovableObject), walls (StaticObject)
     const uint32_t archetype = is_box || is_ramp ?
         TypeTracker::typeID<MovableObject>() : TypeTracker::typeID<StaticObject>();
-    const Entity e = ctx.makeEntityOrdered(archetype, on_level);
+    const Entity e = ctx.makeEntityOrdered(archetype, on_level, OrderedRows::Reuse);
 
     if (on_level) {
         // setupRigidBody() with the leaf this body has in the sequence

@@ -25,7 +25,8 @@ struct SimTraits {
                              (args.flags >> 3) & 1u,
                              (args.flags >> 4) & 1u,
                              (args.flags >> 5) & 1u,
-                             (args.flags >> 6) & 1u };
+                             (args.flags >> 6) & 1u,
+                             (args.flags >> 7) & 1u };
     }
 
     static void makeInits(const SimCreateArgs &, Sim::WorldInit *) {}
@@ -36,6 +37,8 @@ struct SimTraits {
     static void describeFlagTensors(T &out, const SimCreateArgs &args);
     template <typename T>
     static void describeColumns(T &cols);
+    template <typename T>
+    static void describeFlagColumns(T &cols, const SimCreateArgs &args);
 };
 
 #include "common/mgr_impl.inl"
@@ -95,4 +98,31 @@ void SimTraits::describeColumns(T &cols)
 #endif
     cols.template add<Scratch, Key>("Scratch.Key", false);
     cols.template add<Scratch, Vec3>("Scratch.Vec3", true);
+}
+
+// columns of the tables that only exist with flags 128 (Config::reusePlan)
+template <typename T>
+void SimTraits::describeFlagColumns(T &cols, const SimCreateArgs &args)
+{
+    using namespace sortstress;
+    using madrona::Entity;
+
+    if ((args.flags & 128u) == 0u) {
+        return;
+    }
+    cols.template add<Reuse0, Entity>("Reuse0.Entity", false);
+    cols.template add<Reuse0, Key>("Reuse0.Key", false);
+    cols.template add<Reuse0, Pair>("Reuse0.Pair", false);
+    cols.template add<Reuse1, Entity>("Reuse1.Entity", false);
+    cols.template add<Reuse1, Key>("Reuse1.Key", false);
+    cols.template add<Reuse1, Pair>("Reuse1.Pair", false);
+    cols.template add<Reuse2, Entity>("Reuse2.Entity", false);
+    cols.template add<Reuse2, Key>("Reuse2.Key", false);
+    cols.template add<Reuse2, Pair>("Reuse2.Pair", false);
+    cols.template add<Reuse3, Entity>("Reuse3.Entity", false);
+    cols.template add<Reuse3, Key>("Reuse3.Key", false);
+    cols.template add<Reuse3, Pair>("Reuse3.Pair", false);
+    cols.template add<Reuse4, Entity>("Reuse4.Entity", false);
+    cols.template add<Reuse4, Key>("Reuse4.Key", false);
+    cols.template add<Reuse4, Pair>("Reuse4.Pair", false);
 }

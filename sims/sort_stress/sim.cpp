@@ -26,6 +26,14 @@ void Sim::registerTypes(ECSRegistry &registry, const Config &cfg)
 
     registry.exportSingleton<Churn>((uint32_t)ExportID::Churn);
 
+    if (cfg.reusePlan != 0) {
+        registry.registerArchetype<Reuse0>();
+        registry.registerArchetype<Reuse1>();
+        registry.registerArchetype<Reuse2>();
+        registry.registerArchetype<Reuse3>();
+        registry.registerArchetype<Reuse4>();
+    }
+
 #ifdef MADRONA_GPU_MODE
     if (cfg.plan != 0) {
         registry.registerSingleton<Plan>();
@@ -301,11 +309,222 @@ inline void probeSystem(Engine &ctx, ProbeOut &out)
 }
 #endif
 
+// ---- Config::reusePlan ------------------------------------------------------
+struct ReusePlan {
+    uint32_t destroy[consts::numReuseTables];   // bit i: the world's i-th row
+    int32_t create[consts::numReuseTables];
+};
+
+static inline uint32_t reuseMix(uint32_t x)
+{
+    x ^= x >> 16;
+    x *= 0x7FEB352Du;
+    x ^= x >> 15;
+    x *= 0x846CA68Bu;
+    x ^= x >> 16;
+    return x;
+}
+
+// the last k of n rows
+static inline uint32_t reuseSuffix(int32_t n, int32_t k)
+{
+    return ((1u << n) - 1u) & ~((1u << (n - k)) - 1u);
+}
+
+static inline int32_t reuseBits(uint32_t x)
+{
+    int32_t n = 0;
+    for (; x != 0u; x &= x - 1u) n++;
+    return n;
+}
+
+// What the world does to its Reuse tables at this step.  Rows are named by
+// their position in the world's list, which is their order in the table:
+// survivors keep their order, new rows follow in creation order.
+static inline ReusePlan reusePlanFor(const Sim &sim, uint32_t step)
+{
+    ReusePlan p {};
+    const int32_t n0 = sim.numReuse[0];
+    const int32_t half = (n0 + 1) / 2;
+    switch ((sim.globalWorld + step) % 8u) {
+    case 0:     // the whole range, as many again
+        p.destroy[0] = reuseSuffix(n0, n0);
+        p.create[0] = n0;
+        break;
+    case 1:     // a proper suffix, as many again
+        p.destroy[0] = reuseSuffix(n0, half);
+        p.create[0] = half;
+        break;
+    case 2:     // a suffix, fewer creates
+        p.destroy[0] = reuseSuffix(n0, half);
+        p.create[0] = half > 0 ? half - 1 : 0;
+        break;
+    case 3:     // a suffix, more creates: reuse and append in one call
+        p.destroy[0] = reuseSuffix(n0, half);
+        p.create[0] = half + 2;
+        break;
+    case 4:     // no suffix: the first row of several
+        p.destroy[0] = n0 >= 2 ? 1u : 0u;
+        p.create[0] = 1;
+        break;
+    case 5:     // two archetypes in one call
+        p.destroy[0] = reuseSuffix(n0, half);
+        p.create[0] = half;
+        p.destroy[1] = reuseSuffix(sim.numReuse[1], sim.numReuse[1]);
+        p.create[1] = sim.numReuse[1];
+        break;
+    case 6:     // five archetypes in one call: the last row of each
+        for (int32_t a = 0; a < consts::numReuseTables; a++) {
+            p.destroy[a] = reuseSuffix(sim.numReuse[a], sim.numReuse[a] > 0 ? 1 : 0);
+            p.create[a] = 1;
+        }
+        break;
+    default:    // leaves the world without rows in the first table
+        p.destroy[0] = reuseSuffix(n0, n0);
+        p.create[0] = 0;
+        break;
+    }
+    for (int32_t a = 0; a < consts::numReuseTables; a++) {
+        const int32_t room =
+            consts::maxReuse - (sim.numReuse[a] - reuseBits(p.destroy[a]));
+        if (p.create[a] > room) {
+            p.create[a] = room;
+        }
+    }
+    return p;
+}
+
+static inline uint32_t reuseKey(const Sim &sim, uint32_t step, int32_t a, int32_t j)
+{
+    return reuseMix(sim.globalWorld * 977u + step * 31u + (uint32_t)(a * 8 + j));
+}
+
+#ifdef MADRONA_GPU_MODE
+static inline uint32_t reuseArchetype(int32_t a)
+{
+    switch (a) {
+    case 0: return TypeTracker::typeID<Reuse0>();
+    case 1: return TypeTracker::typeID<Reuse1>();
+    case 2: return TypeTracker::typeID<Reuse2>();
+    case 3: return TypeTracker::typeID<Reuse3>();
+    default: return TypeTracker::typeID<Reuse4>();
+    }
+}
+
+// 64 lanes per world (CustomParallelForNode<..., 64, 1>): lane 8 a + i stands
+// for row i of table a.  The same ids, rows and values as the loops below.
+inline void reusePlanSystem(Engine &ctx, Churn &churn)
+{
+    Sim &sim = ctx.data();
+    const ReusePlan plan = reusePlanFor(sim, churn.step);
+
+    const int32_t lane = (int32_t)(threadIdx.x % 64);
+    const bool on_table = lane < consts::numReuseTables * consts::maxReuse;
+    const int32_t a = on_table ? lane / consts::maxReuse : 0;
+    const int32_t i = lane % consts::maxReuse;
+    const int32_t n = sim.numReuse[a];
+    const bool held = on_table && i < n;
+    const Entity mine = held ? sim.reuse[a][i] : Entity::none();
+    const bool gone = held && ((plan.destroy[a] >> i) & 1u) != 0u;
+    const int32_t kept = n - reuseBits(plan.destroy[a]);
+    const int32_t kept_before =
+        reuseBits(~plan.destroy[a] & ((1u << i) - 1u) & ((1u << n) - 1u));
+
+    ctx.destroyEntityOrdered(mine, gone, OrderedRows::Reuse);
+
+    const bool make = on_table && i < plan.create[a];
+    const Entity e = ctx.makeEntityOrdered(reuseArchetype(a), make, OrderedRows::Reuse);
+    if (make) {
+        const uint32_t key = reuseKey(sim, churn.step, a, i);
+        ctx.get<Key>(e).v = key;
+        ctx.get<Pair>(e).v = ((uint64_t)key << 32) | (uint64_t)(uint32_t)i;
+    }
+
+    // (every lane read its own slot above; the slots written are distinct)
+    if (held && !gone) {
+        sim.reuse[a][kept_before] = mine;
+    }
+    if (make) {
+        sim.reuse[a][kept + i] = e;
+    }
+    if (on_table && i == 0) {
+        sim.numReuse[a] = kept + plan.create[a];
+    }
+}
+#else
+template <typename ArchetypeT>
+static inline void reusePlanTable(Engine &ctx, Sim &sim, const ReusePlan &plan,
+                                  uint32_t step, int32_t a, bool destroy)
+{
+    if (destroy) {
+        int32_t kept = 0;
+        for (int32_t i = 0; i < sim.numReuse[a]; i++) {
+            if (((plan.destroy[a] >> i) & 1u) != 0u) {
+                ctx.destroyEntity(sim.reuse[a][i]);
+            } else {
+                sim.reuse[a][kept++] = sim.reuse[a][i];
+            }
+        }
+        sim.numReuse[a] = kept;
+        return;
+    }
+    for (int32_t j = 0; j < plan.create[a]; j++) {
+        Entity e = ctx.makeEntity<ArchetypeT>();
+        const uint32_t key = reuseKey(sim, step, a, j);
+        ctx.get<Key>(e).v = key;
+        ctx.get<Pair>(e).v = ((uint64_t)key << 32) | (uint64_t)(uint32_t)j;
+        sim.reuse[a][sim.numReuse[a]++] = e;
+    }
+}
+
+inline void reusePlanSystem(Engine &ctx, Churn &churn)
+{
+    Sim &sim = ctx.data();
+    const ReusePlan plan = reusePlanFor(sim, churn.step);
+    for (int32_t pass = 0; pass < 2; pass++) {
+        const bool destroy = pass == 0;
+        reusePlanTable<Reuse0>(ctx, sim, plan, churn.step, 0, destroy);
+        reusePlanTable<Reuse1>(ctx, sim, plan, churn.step, 1, destroy);
+        reusePlanTable<Reuse2>(ctx, sim, plan, churn.step, 2, destroy);
+        reusePlanTable<Reuse3>(ctx, sim, plan, churn.step, 3, destroy);
+        reusePlanTable<Reuse4>(ctx, sim, plan, churn.step, 4, destroy);
+    }
+}
+#endif
+
+template <typename ArchetypeT>
+static inline void reuseInitTable(Engine &ctx, Sim &sim, int32_t a)
+{
+    const int32_t initial = (int32_t)((sim.globalWorld * 3u + (uint32_t)a * 2u) % 6u);
+    sim.numReuse[a] = 0;
+    for (int32_t j = 0; j < initial; j++) {
+        Entity e = ctx.makeEntity<ArchetypeT>();
+        const uint32_t key = reuseKey(sim, 0xFFFFu, a, j);
+        ctx.get<Key>(e).v = key;
+        ctx.get<Pair>(e).v = ((uint64_t)key << 32) | (uint64_t)(uint32_t)j;
+        sim.reuse[a][sim.numReuse[a]++] = e;
+    }
+}
+
 void Sim::setupTasks(TaskGraphManager &taskgraph_mgr, const Config &cfg)
 {
     TaskGraphBuilder &builder = taskgraph_mgr.init(TaskGraphID::Step);
 
     auto clear_tmp = builder.addToGraph<ClearTmpNode<Scratch>>({});
+    if (cfg.reusePlan != 0) {
+#ifdef MADRONA_GPU_MODE
+        auto plan_sys = builder.addToGraph<CustomParallelForNode<Engine,
+            reusePlanSystem, 64, 1, Churn>>({clear_tmp});
+#else
+        auto plan_sys = builder.addToGraph<ParallelForNode<Engine,
+            reusePlanSystem, Churn>>({clear_tmp});
+#endif
+        auto c0 = builder.addToGraph<CompactArchetypeNode<Reuse0>>({plan_sys});
+        auto c1 = builder.addToGraph<CompactArchetypeNode<Reuse1>>({c0});
+        auto c2 = builder.addToGraph<CompactArchetypeNode<Reuse2>>({c1});
+        auto c3 = builder.addToGraph<CompactArchetypeNode<Reuse3>>({c2});
+        clear_tmp = builder.addToGraph<CompactArchetypeNode<Reuse4>>({c3});
+    }
 
     auto churn_sys = builder.addToGraph<ParallelForNode<Engine,
         churnSystem, Churn>>({clear_tmp});
@@ -393,6 +612,15 @@ void Sim::setupTasks(TaskGraphManager &taskgraph_mgr, const Config &cfg)
         }
     }
     {
+        TaskGraphBuilder &b = taskgraph_mgr.init(TaskGraphID::ReusePlanOnly);
+        if (cfg.reusePlan != 0) {
+            b.addToGraph<CustomParallelForNode<Engine,
+                reusePlanSystem, 64, 1, Churn>>({});
+        } else {
+            b.addToGraph<ResetTmpAllocNode>({});
+        }
+    }
+    {
         TaskGraphBuilder &b = taskgraph_mgr.init(TaskGraphID::PlanResize);
         if (cfg.plan != 0) {
             b.addToGraph<ParallelForNode<Engine, planResizeSystem, Plan>>({});
@@ -442,6 +670,16 @@ Sim::Sim(Engine &ctx, const Config &cfg, const WorldInit &)
         Entity e = ctx.makeEntity<Item>();
         fillItem(ctx, e, rng);
         items[numItems++] = e;
+    }
+    for (int32_t a = 0; a < consts::numReuseTables; a++) {
+        numReuse[a] = 0;
+    }
+    if (cfg.reusePlan != 0) {
+        reuseInitTable<Reuse0>(ctx, *this, 0);
+        reuseInitTable<Reuse1>(ctx, *this, 1);
+        reuseInitTable<Reuse2>(ctx, *this, 2);
+        reuseInitTable<Reuse3>(ctx, *this, 3);
+        reuseInitTable<Reuse4>(ctx, *this, 4);
     }
 }
 

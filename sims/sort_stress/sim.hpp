@@ -19,6 +19,9 @@ namespace consts {
 inline constexpr int32_t maxItems = 40;
 inline constexpr int32_t maxChurn = 6;
 inline constexpr int32_t maxScratch = 12;
+// Config::reusePlan: five small archetypes, at most maxReuse rows per world each
+inline constexpr int32_t numReuseTables = 5;
+inline constexpr int32_t maxReuse = 8;
 }
 
 enum class ExportID : uint32_t {
@@ -105,6 +108,9 @@ enum class TaskGraphID : uint32_t {
     WorldSort,
     Probe,
     PlanResize,
+    // Config::reusePlan: reusePlanSystem alone, no compaction behind it (rows
+    // appended to a table that has not been world-sorted stay that way)
+    ReusePlanOnly,
 #endif
     NumTaskGraphs,
 };
@@ -116,6 +122,13 @@ struct Item : public madrona::Archetype<
 struct Scratch : public madrona::Archetype<
     Key, Vec3
 > {};
+
+// Config::reusePlan: rows a world destroys and creates again in one system
+struct Reuse0 : public madrona::Archetype<Key, Pair> {};
+struct Reuse1 : public madrona::Archetype<Key, Pair> {};
+struct Reuse2 : public madrona::Archetype<Key, Pair> {};
+struct Reuse3 : public madrona::Archetype<Key, Pair> {};
+struct Reuse4 : public madrona::Archetype<Key, Pair> {};
 
 class Engine;
 
@@ -151,6 +164,16 @@ struct Sim : public madrona::WorldBase {
         // 1 (HIP backend only): Item's Vec3 column is exported ("item_vec3"),
         // a pinned column the sort node must keep in place
         uint32_t exportVec3;
+        // 1: five more archetypes (Reuse0 .. Reuse4).  In front of the usual
+        // step every world destroys a planned subset of their rows and creates
+        // a planned number in ONE system (reusePlanSystem), the plan cycling
+        // with the global world index and the step: the whole range or a
+        // suffix of it with as many, fewer or more creates, a subset that is
+        // no suffix, two and five archetypes in one call, a world left with no
+        // rows.  On this backend the system is wave-cooperative and asks for
+        // OrderedRows::Reuse; the reference build of the same plan uses plain
+        // makeEntity / destroyEntity.
+        uint32_t reusePlan;
     };
 
     struct WorldInit {};
@@ -170,6 +193,9 @@ struct Sim : public madrona::WorldBase {
     uint32_t globalWorld;
     int32_t numItems;
     Entity items[consts::maxItems];
+    // Config::reusePlan: the world's rows of Reuse0 .. Reuse4, in table order
+    int32_t numReuse[consts::numReuseTables];
+    Entity reuse[consts::numReuseTables][consts::maxReuse];
 };
 
 class Engine : public madrona::CustomContext<Engine, Sim> {

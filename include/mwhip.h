@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded() and mwhip_digest_*() / mwhip_set_step_digest() (a per-world hash of chosen columns computed on the device) and mwhip_view_*() / mwhip_set_step_view() (padded per-world tensors of a table's columns) and mwhip_write_*() / mwhip_set_step_write() (padded per-world tensors scattered into a table's columns) and mwhip_reduce_term / mwhip_reduce_*() / mwhip_set_step_reduce() (per-world sums, extrema, counts and alarms of a table's columns); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
+#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded() and mwhip_digest_*() / mwhip_set_step_digest() (a per-world hash of chosen columns computed on the device) and mwhip_view_*() / mwhip_set_step_view() (padded per-world tensors of a table's columns) and mwhip_write_*() / mwhip_set_step_write() (padded per-world tensors scattered into a table's columns) and mwhip_reduce_term / mwhip_reduce_*() / mwhip_set_step_reduce() (per-world sums, extrema, counts and alarms of a table's columns) and MWHIP_NODE_CARRIED / mwhip_broadphase_carry_stats() (launches a steady replay leaves out, a bit of mwhip_node_desc::kind that earlier libraries never set); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
 
 typedef struct mwhip_exec mwhip_exec; /* opaque; == MWCudaExecutor::Impl */
 
@@ -284,6 +284,18 @@ enum mwhip_node_kind {
      * replaces arrival-order atomics. */
     MWHIP_NODE_EXCLUSIVE_SCAN = 5
 };
+/* OR-ed into mwhip_node_desc::kind (added under ABI 9: libraries built before it
+ * never set the bit): the node's launches recompute what is already in memory
+ * when nothing but replays of the same launch graph happened since the previous
+ * replay -- the simulator's promise, e.g.
+ * PhysicsSystem::setupBroadphaseTasks(..., BroadphaseInputs::CarriedOver).  A
+ * launch graph that holds such launches is instantiated with and without them,
+ * and a replay that directly follows a replay of the same graph runs the one
+ * without (DESIGN.md section 30 has the whole rule; MADRONA_MWHIP_CARRY_BROADPHASE
+ * = 0: never).  Building a launch graph fails when a task graph of it has a
+ * flagged node that no unflagged node of the same name follows in the task
+ * graph's order: there would be nothing to carry over. */
+#define MWHIP_NODE_CARRIED 0x80000000u
 
 #define MWHIP_SCAN_MAX_SEGMENTS 8
 typedef struct mwhip_scan_params {
@@ -446,6 +458,32 @@ void *mwhip_stream(mwhip_exec *exec);
  * replay like mwhip_run does (new: the reference leaves this to the caller's
  * cudaStreamSynchronize). */
 int mwhip_synchronize(mwhip_exec *exec);
+/* What the MWHIP_NODE_CARRIED nodes of this executor read: component ids, any
+ * archetype (the sets of several calls add up).  While a column of one of them
+ * is exported (mwhip_export_column) every replay runs the carried launches: a
+ * caller may write an exported column without the runtime seeing it.  Called
+ * by whoever adds the flagged nodes (PhysicsSystem::setupBroadphaseTasks). */
+int mwhip_carried_reads(mwhip_exec *exec, const uint32_t *component_ids,
+                        uint32_t num_components);
+/* MADRONA_MWHIP_CARRY_BROADPHASE=2: every replay that would have left out a
+ * MWHIP_NODE_CARRIED launch of `kernel` runs `check_kernel` (same signature,
+ * same grid) in its place: it compares what `kernel` would store with what is
+ * stored, raises a device error flag on a difference and stores nothing -- how
+ * a simulator author finds a broken promise.  A carried kernel without one is
+ * simply run. */
+int mwhip_carried_check(mwhip_exec *exec, const void *kernel,
+                        const void *check_kernel);
+/* Replays of launch graph `graph` that ran without its MWHIP_NODE_CARRIED
+ * launches, and replays that ran all of them (every replay of a graph that has
+ * no such launch is a full one).  Counted when a replay is queued; a rebuild of
+ * the graph (growth, rings, step digests ...) keeps the counts.  Pure getter.
+ * Non-zero for an unknown handle. */
+typedef struct mwhip_carry_counters {
+    uint64_t carried_replays;
+    uint64_t full_replays;
+} mwhip_carry_counters;
+int mwhip_broadphase_carry_stats(mwhip_exec *exec, uint64_t graph,
+                                 mwhip_carry_counters *out);
 /* MWCudaExecutor::getExported (cuda_exec.cpp:2802-2805) */
 void *mwhip_get_exported(const mwhip_exec *exec, uint32_t slot);
 

@@ -352,6 +352,7 @@ MWHIP_RT int stepDigestStage(mwhip_exec *exec, const LaunchGraph &lg,
 extern "C" int mwhip_digest_create(mwhip_exec *exec, const mwhip_digest_column *cols,
                                    uint32_t n, uint64_t *digest_out)
 {
+    carryStale(exec);
     // (every refusal comes before anything is allocated)
     if (exec == nullptr || !exec->stateBuilt || digest_out == nullptr) {
         return fail(-2, "digest_create: no executor state");
@@ -427,6 +428,7 @@ extern "C" int mwhip_digest_create(mwhip_exec *exec, const mwhip_digest_column *
 
 extern "C" int mwhip_set_step_digest(mwhip_exec *exec, uint64_t digest)
 {
+    carryStale(exec);
     if (digest != 0 && findDigest(exec, digest) == nullptr) {
         return unknownObject("digest", digest);
     }
@@ -440,6 +442,7 @@ extern "C" int mwhip_set_step_digest(mwhip_exec *exec, uint64_t digest)
 
 extern "C" void mwhip_digest_destroy(mwhip_exec *exec, uint64_t digest)
 {
+    carryStale(exec);
     if (findDigest(exec, digest) == nullptr) return;
     (void)hipSetDevice(exec->cfg.gpu_id);
     // (the step graphs must stop naming its buffers before they go; if they
@@ -451,11 +454,13 @@ extern "C" void mwhip_digest_destroy(mwhip_exec *exec, uint64_t digest)
 
 extern "C" int mwhip_digest_compute(mwhip_exec *exec, uint64_t digest)
 {
+    carryStale(exec);
     return computeDigest(exec, digest, true);
 }
 
 extern "C" int mwhip_digest_compute_async(mwhip_exec *exec, uint64_t digest)
 {
+    carryStale(exec);
     return computeDigest(exec, digest, false);
 }
 

@@ -190,6 +190,7 @@ struct NodeRec {
     mwhip_node_desc desc;
     std::string name;
     std::vector<int32_t> deps;
+    bool carried = false;       // MWHIP_NODE_CARRIED was set in desc.kind
 };
 
 struct TaskGraphRec {
@@ -210,6 +211,20 @@ struct LaunchGraph {
     std::vector<std::unique_ptr<SortBatch>> sortBatches;
     hipGraph_t graph = nullptr;
     hipGraphExec_t graphExec = nullptr;
+    // Launches flagged MWHIP_NODE_CARRIED (KernelLaunch::carried) recompute what
+    // the previous replay of this graph left in memory.  A graph that holds some
+    // is instantiated a second time without them (the edges are a chain: the
+    // neighbours join), and replayGraph picks per replay (carriedReplay,
+    // runtime.hip).  MADRONA_MWHIP_CARRY_BROADPHASE=2: with
+    // the kernels that check the promise in their place (steadyFn).  Null:
+    // nothing to leave out, or this graph may never leave it out (carryAllowed).
+    hipGraph_t steadyGraph = nullptr;
+    hipGraphExec_t steadyExec = nullptr;
+    bool hasCarried = false;
+    // decided when the graph is built: no step write in the executor's
+    // ReplayExtras, and no exported column of a component the carried launches
+    // read (a caller may write an exported column behind the runtime's back)
+    bool carryAllowed = false;
     std::string statName;
     std::vector<std::string> statNames;     // backing store for mwhip_kernel_stat::name
     std::vector<uint32_t> taskGraphIds;     // to rebuild after a table grew
@@ -230,6 +245,8 @@ struct LaunchGraph {
     {
         if (graphExec) (void)hipGraphExecDestroy(graphExec);
         if (graph) (void)hipGraphDestroy(graph);
+        if (steadyExec) (void)hipGraphExecDestroy(steadyExec);
+        if (steadyGraph) (void)hipGraphDestroy(steadyGraph);
         for (void *p : ownedAllocations) {
             (void)hipFree(p);
         }
@@ -359,6 +376,25 @@ struct mwhip_exec {
     // its one-workgroup tail sort is just slow when the whole table is "tail")
     uint32_t sortCompaction = 1;
     bool eagerReplay = false;       // MADRONA_MWHIP_EAGER (measurement, replayGraph)
+    // ---- carried launches (MWHIP_NODE_CARRIED) ----
+    // MADRONA_MWHIP_CARRY_BROADPHASE, read at creation: 0 every replay is full,
+    // 1 (default) a replay that directly follows a replay of the same launch
+    // graph leaves the carried launches out, 2 every replay is full and the
+    // simulator's carried nodes check instead of store (physics.inl)
+    uint32_t carryMode = 1;
+    // Handle of the launch graph whose replay was the LAST thing this executor
+    // was asked to do, 0 if anything else happened since (carryStale): every
+    // entry point of mwhip.h except the replay calls, mwhip_synchronize and the
+    // pure getters, every rebuild of a launch graph, every failed call.
+    uint64_t carryFrom = 0;
+    uint64_t carryEpoch = 0;        // g_carryEpoch when carryFrom was set
+    std::unordered_map<uint64_t, mwhip_carry_counters> carryCounts;  // by handle
+    // component ids the carried nodes read (mwhip_carried_reads) and those of
+    // every exported column (mwhip_export_column)
+    std::vector<uint32_t> carriedReads;
+    // kernel -> the kernel that checks instead of storing (mwhip_carried_check)
+    std::unordered_map<const void *, const void *> carriedChecks;
+    std::vector<uint32_t> exportedComponents;
     const void *pforGroupKernel = nullptr;  // mwhip_set_pfor_group_kernel
     void *pforBodyScratch = nullptr;        // 8 bytes: where report mode writes
     // MADRONA_MWHIP_EXEC_CONFIG_FILE (the reference's
@@ -388,6 +424,27 @@ struct mwhip_exec {
     ExecObjectTable<mwhip_write_rec> writes;
     ExecObjectTable<mwhip_reduce_rec> reduces;     // mwhip_reduce_create
 };
+
+// Bumped by what changes device memory or fails without naming an executor
+// (mwhip_memcpy_h2d, mwhip_raw_copy_h2d, fail()): every executor of the process
+// is stale after it.  (runtime.hip)
+extern MWHIP_RT std::atomic<uint64_t> g_carryEpoch;
+
+// The next replay of this executor runs every launch.
+inline void carryStale(mwhip_exec *exec)
+{
+    if (exec != nullptr) exec->carryFrom = 0;
+}
+
+// What a steady replay (replayGraph's rule holds) launches for `k`: the launch
+// itself, nothing (nullptr: a carried launch, mode 1), or the kernel that checks
+// the simulator's promise in its place (mode 2).
+inline const void *steadyFn(const mwhip_exec *exec, const KernelLaunch &k)
+{
+    if (!k.carried) return k.fn;
+    if (exec->carryMode == 2u) return k.checkFn != nullptr ? k.checkFn : k.fn;
+    return nullptr;
+}
 
 // ---- functions one translation unit defines and another calls ----------------------
 MWHIP_RT int devAlloc(mwhip_exec *exec, void **out, size_t bytes, bool zero = true);

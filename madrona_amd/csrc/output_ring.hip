@@ -119,6 +119,7 @@ extern "C" int mwhip_set_output_ring(mwhip_exec *exec, const void *src, void *ri
                                      uint64_t slot_bytes, uint32_t num_slots,
                                      uint32_t when)
 {
+    carryStale(exec);
     // (every refusal comes before anything changes)
     if (src == nullptr) {
         return fail(-2, "set_output_ring: no source");

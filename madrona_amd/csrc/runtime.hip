@@ -15,6 +15,8 @@
 
 static thread_local std::string g_lastError;
 
+MWHIP_RT std::atomic<uint64_t> g_carryEpoch { 0 };
+
 // ---------------------------------------------------------------------------
 // errors
 // ---------------------------------------------------------------------------
@@ -26,6 +28,8 @@ MWHIP_RT int fail(int code, const char *fmt, ...)
     vsnprintf(buf, sizeof(buf), fmt, ap);
     va_end(ap);
     g_lastError = buf;
+    // (a failed call: the next replay of every executor is a full one)
+    g_carryEpoch.fetch_add(1, std::memory_order_relaxed);
     if (getenv("MADRONA_MWHIP_VERBOSE") != nullptr) {
         fprintf(stderr, "[mwhip] error %d: %s\n", code, buf);
     }
@@ -50,6 +54,7 @@ extern "C" const char *mwhip_last_error(void)
 extern "C" int mwhip_register_component(mwhip_exec *exec, uint32_t id,
                                         uint32_t alignment, uint32_t num_bytes)
 {
+    carryStale(exec);
     if (!exec->registrationOpen) {
         return fail(-1, "registerComponent outside registerTypes");
     }
@@ -91,6 +96,7 @@ extern "C" int mwhip_register_bundle(mwhip_exec *exec, uint32_t bundle_id,
                                      const uint32_t *component_ids,
                                      uint32_t num_components)
 {
+    carryStale(exec);
     if (!exec->registrationOpen) {
         return fail(-1, "registerBundle outside registerTypes");
     }
@@ -113,6 +119,7 @@ extern "C" int mwhip_register_archetype(mwhip_exec *exec, uint32_t id,
                                         uint32_t archetype_flags,
                                         uint32_t max_per_world)
 {
+    carryStale(exec);
     (void)component_flags;
     if (!exec->registrationOpen) {
         return fail(-1, "registerArchetype outside registerTypes");
@@ -221,6 +228,7 @@ extern "C" int mwhip_register_archetype(mwhip_exec *exec, uint32_t id,
 extern "C" int mwhip_register_singleton(mwhip_exec *exec, uint32_t archetype_id,
                                         uint32_t component_id)
 {
+    carryStale(exec);
     (void)component_id;
     if (archetype_id >= exec->archetypes.size() ||
             !exec->archetypes[archetype_id].registered) {
@@ -286,6 +294,7 @@ MWHIP_RT int finishQueued(mwhip_exec *exec, int rc, bool wait)
 extern "C" void *mwhip_export_column(mwhip_exec *exec, uint32_t archetype_id,
                                      uint32_t component_id, int32_t slot)
 {
+    carryStale(exec);
     if (archetype_id >= exec->archetypes.size() ||
             !exec->archetypes[archetype_id].registered) {
         fail(-3, "exportColumn: archetype %u not registered", archetype_id);
@@ -307,6 +316,7 @@ extern "C" void *mwhip_export_column(mwhip_exec *exec, uint32_t archetype_id,
     // exported columns keep their address across sorts
     arch.colFlags[col] |= kColumnPinned;
     exec->exported[slot] = arch.primary[col];
+    exec->exportedComponents.push_back(component_id);
     return arch.primary[col];
 }
 
@@ -314,6 +324,7 @@ extern "C" int mwhip_make_query(mwhip_exec *exec, const uint32_t *component_ids,
                                 uint32_t num_components, uint32_t *offset_out,
                                 uint32_t *num_matching_out, uint32_t *flags_out)
 {
+    carryStale(exec);
     std::vector<uint32_t> comps(component_ids, component_ids + num_components);
     for (const QueryRec &q : exec->queries) {
         if (q.comps == comps) {
@@ -397,6 +408,7 @@ extern "C" int mwhip_raw_copy_h2d(int gpu_id, void *dst_device,
                                   const void *src_host, uint64_t num_bytes)
 {
     HIPCHK(hipSetDevice(gpu_id));
+    g_carryEpoch.fetch_add(1, std::memory_order_relaxed);
     if (num_bytes != 0) {
         HIPCHK(hipMemcpy(dst_device, src_host, num_bytes,
                          hipMemcpyHostToDevice));
@@ -417,6 +429,7 @@ extern "C" int mwhip_raw_copy_d2h(int gpu_id, void *dst_host,
 
 extern "C" void *mwhip_alloc_device(mwhip_exec *exec, uint64_t num_bytes, int zero)
 {
+    carryStale(exec);
     void *ptr = nullptr;
     if (devAlloc(exec, &ptr, num_bytes, zero != 0) != 0) {
         return nullptr;
@@ -427,6 +440,7 @@ extern "C" void *mwhip_alloc_device(mwhip_exec *exec, uint64_t num_bytes, int ze
 extern "C" int mwhip_set_module_data(mwhip_exec *exec, uint32_t slot,
                                      void *device_ptr)
 {
+    carryStale(exec);
     if (slot >= 4) {
         return fail(-3, "module data slot %u out of range", slot);
     }
@@ -567,6 +581,7 @@ extern "C" int mwhip_create(const mwhip_state_config *cfg,
     exec->sortCarriesMisc = envU32("MADRONA_MWHIP_SORT_CARRIES_MISC", 1) != 0;
     exec->sortCompaction = envU32("MADRONA_MWHIP_SORT_COMPACT", 1);
     exec->eagerReplay = envU32("MADRONA_MWHIP_EAGER", 0) != 0;
+    exec->carryMode = std::min(envU32("MADRONA_MWHIP_CARRY_BROADPHASE", 1), 2u);
     {
         hipDeviceProp_t prop {};
         HIPCHK(hipGetDeviceProperties(&prop, cfg->gpu_id));
@@ -687,6 +702,7 @@ extern "C" void mwhip_destroy(mwhip_exec *exec)
 extern "C" int32_t mwhip_tg_add_node_data(mwhip_exec *exec, uint32_t tg_id,
                                           const void *data, uint32_t num_bytes)
 {
+    carryStale(exec);
     if (tg_id >= exec->taskGraphs.size()) {
         return fail(-3, "task graph %u out of range (numTaskGraphs=%zu)", tg_id,
                     exec->taskGraphs.size());
@@ -717,6 +733,7 @@ extern "C" void *mwhip_tg_node_data(mwhip_exec *exec, uint32_t tg_id,
 
 extern "C" const void *mwhip_pfor_body(mwhip_exec *exec, const void *kernel)
 {
+    carryStale(exec);
     if (kernel == nullptr) return nullptr;
     if (exec->pforBodyScratch == nullptr) {
         if (devAlloc(exec, &exec->pforBodyScratch, 16) != 0) return nullptr;
@@ -746,6 +763,7 @@ extern "C" const void *mwhip_pfor_body(mwhip_exec *exec, const void *kernel)
 
 extern "C" int mwhip_set_pfor_group_kernel(mwhip_exec *exec, const void *kernel)
 {
+    carryStale(exec);
     exec->pforGroupKernel = kernel;
     return 0;
 }
@@ -760,8 +778,11 @@ extern "C" int32_t mwhip_tg_add_node(mwhip_exec *exec, uint32_t tg_id,
     }
     TaskGraphRec &tg = exec->taskGraphs[tg_id];
 
+    carryStale(exec);
     NodeRec node;
     node.desc = *desc;
+    node.carried = (desc->kind & MWHIP_NODE_CARRIED) != 0u;
+    node.desc.kind = desc->kind & ~MWHIP_NODE_CARRIED;
     node.name = desc->name != nullptr ? desc->name : "node";
     node.desc.name = nullptr;
     for (uint32_t i = 0; i < num_deps; i++) {
@@ -771,7 +792,7 @@ extern "C" int32_t mwhip_tg_add_node(mwhip_exec *exec, uint32_t tg_id,
         }
         node.deps.push_back(deps[i]);
     }
-    if (desc->kind == MWHIP_NODE_KERNEL && desc->kernel == nullptr) {
+    if (node.desc.kind == MWHIP_NODE_KERNEL && desc->kernel == nullptr) {
         return fail(-3, "node '%s' has no kernel", node.name.c_str());
     }
 
@@ -828,6 +849,7 @@ extern "C" int mwhip_build_launch_graph(mwhip_exec *exec,
                                         const char *stat_name,
                                         uint64_t *graph_out)
 {
+    carryStale(exec);
     HIPCHK(hipSetDevice(exec->cfg.gpu_id));
 
     std::vector<uint32_t> ids(taskgraph_ids, taskgraph_ids + num_taskgraphs);
@@ -838,6 +860,25 @@ extern "C" int mwhip_build_launch_graph(mwhip_exec *exec,
         if (!exec->taskGraphs[id].built) {
             int rc = topoSort(exec->taskGraphs[id]);
             if (rc != 0) return rc;
+        }
+        // a carried node recomputes what an unflagged node of the same name
+        // left behind in the previous replay: one has to follow it
+        const TaskGraphRec &tg = exec->taskGraphs[id];
+        for (size_t i = 0; i < tg.sorted.size(); i++) {
+            const NodeRec &node = tg.nodes[(size_t)tg.sorted[i]];
+            if (!node.carried) continue;
+            bool followed = false;
+            for (size_t j = i + 1; j < tg.sorted.size(); j++) {
+                const NodeRec &later = tg.nodes[(size_t)tg.sorted[j]];
+                followed = followed || (!later.carried && later.name == node.name);
+            }
+            if (!followed) {
+                return fail(-3, "task graph %u: node '%s' is flagged as carried "
+                            "over (MWHIP_NODE_CARRIED), but no unflagged '%s' "
+                            "follows it in the task graph: there would be nothing "
+                            "to carry over", id, node.name.c_str(),
+                            node.name.c_str());
+            }
         }
     }
 
@@ -861,6 +902,7 @@ extern "C" int mwhip_build_launch_graph(mwhip_exec *exec,
 extern "C" int mwhip_set_render_layout(mwhip_exec *exec,
                                        const mwhip_render_layout *layout)
 {
+    carryStale(exec);
     if (layout == nullptr) {
         return fail(-2, "set_render_layout: null layout");
     }
@@ -871,6 +913,7 @@ extern "C" int mwhip_set_render_layout(mwhip_exec *exec,
 
 extern "C" int mwhip_build_render_graph(mwhip_exec *exec, uint64_t *graph_out)
 {
+    carryStale(exec);
     HIPCHK(hipSetDevice(exec->cfg.gpu_id));
     if (exec->cfg.raycast_output_resolution == 0) {
         return fail(-3, "buildRenderGraph: the executor was created without a "
@@ -902,6 +945,7 @@ extern "C" int mwhip_build_render_graph(mwhip_exec *exec, uint64_t *graph_out)
 
 extern "C" void mwhip_free_launch_graph(mwhip_exec *exec, uint64_t graph)
 {
+    carryStale(exec);
     auto it = exec->launchGraphs.find(graph);
     if (it == exec->launchGraphs.end()) return;
     (void)hipStreamSynchronize(exec->stream);
@@ -930,7 +974,8 @@ static int checkHealth(mwhip_exec *exec)
     return 0;
 }
 
-static int replayGraph(mwhip_exec *exec, LaunchGraph &lg, hipStream_t stream);
+static int replayGraph(mwhip_exec *exec, uint64_t handle, LaunchGraph &lg,
+                       hipStream_t stream);
 
 extern "C" int mwhip_run(mwhip_exec *exec, uint64_t graph)
 {
@@ -939,7 +984,7 @@ extern "C" int mwhip_run(mwhip_exec *exec, uint64_t graph)
         return fail(-3, "unknown launch graph");
     }
     {
-        int launch_rc = replayGraph(exec, *it->second, exec->stream);
+        int launch_rc = replayGraph(exec, graph, *it->second, exec->stream);
         if (launch_rc != 0) return launch_rc;
     }
     exec->replaysLaunched++;
@@ -959,16 +1004,79 @@ extern "C" int mwhip_run(mwhip_exec *exec, uint64_t graph)
 // kernel node costs ~4 us on this runtime whatever the kernel does; a
 // dependent launch on a stream 1.5 us of device time and 3-4 us of host time,
 // which a step of a millisecond hides).
-static int replayGraph(mwhip_exec *exec, LaunchGraph &lg, hipStream_t stream)
+// THE RULE for the launches a simulator flagged as carried over
+// (MWHIP_NODE_CARRIED) lives here: this replay leaves
+// them out only if the graph was built to allow it (no step write, no exported
+// column of what they read: instantiateLaunchGraph), the mode is not 0, and the
+// last thing this executor was asked to do was to replay the same launch
+// graph.  (Mode 2: such a replay runs the checking kernels in their place,
+// steadyFn, and counts as a full one.)  carryFrom is that graph's handle; carryStale() -- every other entry
+// point that is not a pure getter, every rebuild --, a failed call or a copy
+// into device memory (g_carryEpoch) clear it.  The first replay after creation
+// is therefore a full one.
+static bool carriedReplay(const mwhip_exec *exec, uint64_t handle,
+                          const LaunchGraph &lg)
 {
+    return lg.hasCarried && lg.carryAllowed && exec->carryMode != 0u &&
+        exec->carryFrom == handle &&
+        exec->carryEpoch == g_carryEpoch.load(std::memory_order_relaxed);
+}
+
+static int replayGraph(mwhip_exec *exec, uint64_t handle, LaunchGraph &lg,
+                       hipStream_t stream)
+{
+    const bool steady = carriedReplay(exec, handle, lg);
+    // (whatever goes wrong below leaves the executor stale)
+    exec->carryFrom = 0;
     if (!exec->eagerReplay) {
-        HIPCHK(hipGraphLaunch(lg.graphExec, stream));
-        return 0;
+        HIPCHK(hipGraphLaunch(steady ? lg.steadyExec : lg.graphExec, stream));
+    } else {
+        for (KernelLaunch &k : lg.launches) {
+            const void *fn = steady ? steadyFn(exec, k) : k.fn;
+            if (fn == nullptr) continue;
+            KernelLaunch as_run = k;
+            as_run.fn = fn;
+            int rc = launchOne(exec, as_run, stream);
+            if (rc != 0) return rc;
+        }
     }
-    for (KernelLaunch &k : lg.launches) {
-        int rc = launchOne(exec, k, stream);
-        if (rc != 0) return rc;
+    mwhip_carry_counters &counts = exec->carryCounts[handle];
+    (steady && exec->carryMode == 1u ? counts.carried_replays :
+                                       counts.full_replays) += 1;
+    exec->carryEpoch = g_carryEpoch.load(std::memory_order_relaxed);
+    exec->carryFrom = handle;
+    return 0;
+}
+
+extern "C" int mwhip_broadphase_carry_stats(mwhip_exec *exec, uint64_t graph,
+                                            mwhip_carry_counters *out)
+{
+    if (exec == nullptr || out == nullptr ||
+            exec->launchGraphs.find(graph) == exec->launchGraphs.end()) {
+        return -3;      // (a getter: no fail(), which would make replays full)
     }
+    auto it = exec->carryCounts.find(graph);
+    *out = it != exec->carryCounts.end() ? it->second : mwhip_carry_counters {};
+    return 0;
+}
+
+extern "C" int mwhip_carried_check(mwhip_exec *exec, const void *kernel,
+                                   const void *check_kernel)
+{
+    carryStale(exec);
+    if (kernel == nullptr || check_kernel == nullptr) {
+        return fail(-2, "carried_check: null kernel");
+    }
+    exec->carriedChecks[kernel] = check_kernel;
+    return 0;
+}
+
+extern "C" int mwhip_carried_reads(mwhip_exec *exec, const uint32_t *component_ids,
+                                   uint32_t num_components)
+{
+    carryStale(exec);
+    exec->carriedReads.insert(exec->carriedReads.end(), component_ids,
+                              component_ids + num_components);
     return 0;
 }
 
@@ -1042,7 +1150,7 @@ extern "C" int mwhip_run_async(mwhip_exec *exec, uint64_t graph, void *hip_strea
     }
     // (growing rebuilds the graphs: look the handle up again)
     it = exec->launchGraphs.find(graph);
-    rc = replayGraph(exec, *it->second, (hipStream_t)hip_stream);
+    rc = replayGraph(exec, graph, *it->second, (hipStream_t)hip_stream);
     if (rc != 0) return rc;
     exec->replaysLaunched++;
     return 0;
@@ -1074,6 +1182,7 @@ extern "C" int mwhip_build_launch_graph_with_pack(
     const void *const *src_columns, const uint32_t *words_per_row,
     uint32_t num_rows, void *dst, uint64_t *graph_out)
 {
+    carryStale(exec);
     auto it = exec->launchGraphs.find(base_graph);
     if (it == exec->launchGraphs.end()) {
         return fail(-3, "unknown launch graph");
@@ -1122,6 +1231,7 @@ extern "C" uint32_t mwhip_device_cus(const mwhip_exec *exec)
 extern "C" int mwhip_set_input_ring(mwhip_exec *exec, void *dst, const void *ring,
                                     uint64_t slot_bytes, uint32_t num_slots)
 {
+    carryStale(exec);
     // (every refusal comes before anything changes or is waited for)
     if (dst == nullptr) {
         return fail(-2, "set_input_ring: no destination");
@@ -1162,6 +1272,7 @@ extern "C" int mwhip_set_input_ring(mwhip_exec *exec, void *dst, const void *rin
 // does not order a later hipStreamWaitEvent (measured: the wait returns early).
 extern "C" int mwhip_stream_wait_replays(mwhip_exec *exec, void *hip_stream)
 {
+    carryStale(exec);
     if (exec->replaySignal == nullptr) {
         return fail(-3, "no replay signal");
     }
@@ -1176,6 +1287,7 @@ extern "C" int mwhip_pack_rows(mwhip_exec *exec, uint32_t num_columns,
                                const uint32_t *words_per_row, uint32_t num_rows,
                                void *dst)
 {
+    carryStale(exec);
     PackArgs args {};
     int rc = makePackArgs(num_columns, src_columns, words_per_row, num_rows,
                           &args);
@@ -1198,6 +1310,7 @@ extern "C" int mwhip_pack_rows(mwhip_exec *exec, uint32_t num_columns,
 
 extern "C" int mwhip_mark_window(mwhip_exec *exec, uint32_t id)
 {
+    carryStale(exec);
     HIPCHK(hipSetDevice(exec->cfg.gpu_id));
     uint32_t *no_signal = nullptr;
     void *mark_args[] = { &no_signal, &id };
@@ -1438,6 +1551,8 @@ extern "C" int mwhip_memcpy_any(void *dst_host, const void *src,
 extern "C" int mwhip_memcpy_h2d(void *dst_dev, const void *src_host,
                                 uint64_t num_bytes)
 {
+    // (names no executor: whichever one owns dst_dev, its next replay is full)
+    g_carryEpoch.fetch_add(1, std::memory_order_relaxed);
     HIPCHK(hipMemcpy(dst_dev, src_host, num_bytes, hipMemcpyHostToDevice));
     return 0;
 }
@@ -1458,6 +1573,7 @@ static int readRowCounts(mwhip_exec *exec, std::vector<int32_t> &rows)
 extern "C" int32_t mwhip_profile(mwhip_exec *exec, uint64_t graph, uint32_t reps,
                                  mwhip_kernel_stat *out, uint32_t max_out)
 {
+    carryStale(exec);
     auto it = exec->launchGraphs.find(graph);
     if (it == exec->launchGraphs.end()) {
         return fail(-3, "unknown launch graph");
@@ -1497,6 +1613,13 @@ extern "C" int32_t mwhip_profile(mwhip_exec *exec, uint64_t graph, uint32_t reps
         std::vector<int32_t> rows;
         int rc = readRowCounts(exec, rows);
         if (rc != 0) return rc;
+        // Each rep is a replay under replayGraph's rule: the first one is full
+        // (this call is not a replay: carryStale above), the others leave the
+        // carried launches out where a steady replay would.  avg_us stays "per
+        // step of this run": a carried launch that ran in one rep of twenty
+        // shows a twentieth of its time, and the column adds up to the mean step.
+        const bool steady = carriedReplay(exec, graph, lg);
+        exec->carryFrom = 0;
 
         // queue everything behind the gate, then open it
         volatile int32_t *gate_host = exec->statsHost + kStatsGate;
@@ -1512,9 +1635,11 @@ extern "C" int32_t mwhip_profile(mwhip_exec *exec, uint64_t graph, uint32_t reps
         }
         for (size_t i = 0; i < n; i++) {
             KernelLaunch &k = lg.launches[i];
+            const void *fn = steady ? steadyFn(exec, k) : k.fn;
+            if (fn == nullptr) continue;
             void *kargs[8];
             k.argPointers(kargs);
-            hipError_t lres = hipExtLaunchKernel(k.fn, k.grid, k.block, kargs,
+            hipError_t lres = hipExtLaunchKernel(fn, k.grid, k.block, kargs,
                 k.dynamicLds, exec->stream, ev_start[i], ev_stop[i], 0);
             if (lres != hipSuccess) {
                 *gate_host = 1;
@@ -1531,8 +1656,16 @@ extern "C" int32_t mwhip_profile(mwhip_exec *exec, uint64_t graph, uint32_t reps
                          sizeof(uint32_t), hipMemcpyDeviceToHost));
         rc = checkHealth(exec);
         if (rc != 0) return rc;
+        {
+            mwhip_carry_counters &counts = exec->carryCounts[graph];
+            (steady && exec->carryMode == 1u ? counts.carried_replays :
+                                               counts.full_replays) += 1;
+            exec->carryEpoch = g_carryEpoch.load(std::memory_order_relaxed);
+            exec->carryFrom = graph;
+        }
 
         for (size_t i = 0; i < n; i++) {
+            if (steady && steadyFn(exec, lg.launches[i]) == nullptr) continue;
             float ms = 0.f;
             HIPCHK(hipEventElapsedTime(&ms, ev_start[i], ev_stop[i]));
             total_us[i] += (double)ms * 1000.0;
@@ -1650,6 +1783,7 @@ extern "C" int32_t mwhip_profile(mwhip_exec *exec, uint64_t graph, uint32_t reps
         (void)hipEventDestroy(ev_start[i]);
         (void)hipEventDestroy(ev_stop[i]);
     }
+    carryStale(exec);
 
     lg.statNames.resize(n);
     uint32_t count = (uint32_t)std::min<size_t>(n, max_out);

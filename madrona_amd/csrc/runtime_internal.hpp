@@ -238,6 +238,12 @@ struct KernelLaunch {
     const SortBatch *sortBatch = nullptr;
     SortRole sortRole = SortRole::None;
     bool carriesMisc = false;       // trailing (ops, count) arguments were pushed
+    // the node was flagged MWHIP_NODE_CARRIED: left out of the graph's steady
+    // instantiation (LaunchGraph::steadyExec), never part of a grouped launch
+    bool carried = false;
+    // ... and what MADRONA_MWHIP_CARRY_BROADPHASE=2 launches in its place there
+    // (mwhip_carried_check; nullptr: the launch itself)
+    const void *checkFn = nullptr;
 
     // ---- the launch's place in the step's DAG (buildLaunchDeps) ----
     // A kernel node of a task graph (ParallelFor / custom kernel) waits for the

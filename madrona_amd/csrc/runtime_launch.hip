@@ -504,6 +504,12 @@ static int buildLaunchList(mwhip_exec *exec, const std::vector<uint32_t> &tg_ids
                 k.dagKernel = true;
                 k.tgId = tg_id;
                 k.tgNode = order[oi];
+                k.carried = node.carried;
+                if (k.carried) {
+                    auto check = exec->carriedChecks.find(d.kernel);
+                    k.checkFn = check != exec->carriedChecks.end() ?
+                        check->second : nullptr;
+                }
                 lg.launches.push_back(k);
             } break;
             case MWHIP_NODE_SORT_ARCHETYPE: {
@@ -867,8 +873,12 @@ MWHIP_RT void releaseLaunchGraph(LaunchGraph &lg)
 {
     if (lg.graphExec) (void)hipGraphExecDestroy(lg.graphExec);
     if (lg.graph) (void)hipGraphDestroy(lg.graph);
+    if (lg.steadyExec) (void)hipGraphExecDestroy(lg.steadyExec);
+    if (lg.steadyGraph) (void)hipGraphDestroy(lg.steadyGraph);
     lg.graphExec = nullptr;
     lg.graph = nullptr;
+    lg.steadyExec = nullptr;
+    lg.steadyGraph = nullptr;
     for (void *p : lg.ownedAllocations) {
         (void)hipFree(p);
     }
@@ -894,8 +904,10 @@ static int groupLaunches(mwhip_exec *exec, LaunchGraph &lg)
     // collectObservations: step + 38 us, profiles/r05_group_variants.jsonl), so
     // a node whose own kernel needs more than this many VGPRs keeps its launch.
     const uint32_t max_vgprs = envU32("MADRONA_MWHIP_GROUP_MAX_VGPRS", 96);
+    // (a carried launch keeps its own launch: the steady instantiation leaves
+    // it out, and the groups are the same in both)
     auto groupable = [&](const KernelLaunch &k) {
-        return k.dagKernel && k.pforBody != nullptr &&
+        return k.dagKernel && !k.carried && k.pforBody != nullptr &&
             k.pforGroupKernel != nullptr && !k.rowSnapshot &&
             k.pforVgprs <= max_vgprs &&
             k.countMode == MWHIP_COUNT_QUERY_ROWS && k.tgNode >= 0 &&
@@ -1084,6 +1096,8 @@ MWHIP_RT int instantiateLaunchGraph(mwhip_exec *exec,
                                   std::unique_ptr<LaunchGraph> &out,
                                   const LaunchGraph *pack_from)
 {
+    // (a rebuild: whatever graph the last replay ran no longer exists)
+    carryStale(exec);
     std::unique_ptr<LaunchGraph> lg(new LaunchGraph {});
     lg->statName = stat_name;
     lg->taskGraphIds = ids;
@@ -1140,27 +1154,56 @@ MWHIP_RT int instantiateLaunchGraph(mwhip_exec *exec,
     // The step as an explicit hipGraph: one kernel node per launch, edges from
     // buildLaunchDeps.  (Rounds 1-4 captured the launches from the stream: a
     // chain, whatever the task graph said.)
-    HIPCHK(hipGraphCreate(&lg->graph, 0));
-    std::vector<hipGraphNode_t> nodes(lg->launches.size(), nullptr);
-    for (size_t i = 0; i < lg->launches.size(); i++) {
-        KernelLaunch &k = lg->launches[i];
-        void *args[8];
-        k.argPointers(args);
-        hipKernelNodeParams params {};
-        params.func = const_cast<void *>(k.fn);
-        params.gridDim = k.grid;
-        params.blockDim = k.block;
-        params.sharedMemBytes = k.dynamicLds;
-        params.kernelParams = args;
-        params.extra = nullptr;
-        std::vector<hipGraphNode_t> deps;
-        for (int32_t d : k.deps) {
-            deps.push_back(nodes[(size_t)d]);
+    // `steady`: without the carried launches (or with their checks in their
+    // place, steadyFn).  The edges are a chain, so a launch whose predecessor
+    // is left out waits for the one before that.
+    auto makeGraph = [&](bool steady, hipGraph_t *graph, hipGraphExec_t *graph_exec) {
+        HIPCHK(hipGraphCreate(graph, 0));
+        std::vector<hipGraphNode_t> nodes(lg->launches.size(), nullptr);
+        for (size_t i = 0; i < lg->launches.size(); i++) {
+            KernelLaunch &k = lg->launches[i];
+            const void *fn = steady ? steadyFn(exec, k) : k.fn;
+            if (fn == nullptr) continue;
+            void *args[8];
+            k.argPointers(args);
+            hipKernelNodeParams params {};
+            params.func = const_cast<void *>(fn);
+            params.gridDim = k.grid;
+            params.blockDim = k.block;
+            params.sharedMemBytes = k.dynamicLds;
+            params.kernelParams = args;
+            params.extra = nullptr;
+            std::vector<hipGraphNode_t> deps;
+            for (int32_t d : k.deps) {
+                while (d >= 0 && nodes[(size_t)d] == nullptr) d--;
+                if (d >= 0) deps.push_back(nodes[(size_t)d]);
+            }
+            HIPCHK(hipGraphAddKernelNode(&nodes[i], *graph, deps.data(),
+                                         deps.size(), &params));
         }
-        HIPCHK(hipGraphAddKernelNode(&nodes[i], lg->graph, deps.data(),
-                                     deps.size(), &params));
+        HIPCHK(hipGraphInstantiate(graph_exec, *graph, nullptr, nullptr, 0));
+        return 0;
+    };
+    rc = makeGraph(false, &lg->graph, &lg->graphExec);
+    if (rc != 0) return rc;
+
+    // Carried launches (MWHIP_NODE_CARRIED): whether this
+    // graph may ever leave them out is decided here -- a step write can write
+    // what they read in every replay, and so can the owner of an exported
+    // column -- and which replay does is replayGraph's business (runtime.hip).
+    for (const KernelLaunch &k : lg->launches) {
+        lg->hasCarried = lg->hasCarried || k.carried;
     }
-    HIPCHK(hipGraphInstantiate(&lg->graphExec, lg->graph, nullptr, nullptr, 0));
+    lg->carryAllowed = lg->hasCarried && exec->extras.stepWrites.empty();
+    for (uint32_t component : exec->carriedReads) {
+        lg->carryAllowed = lg->carryAllowed &&
+            std::find(exec->exportedComponents.begin(), exec->exportedComponents.end(),
+                      component) == exec->exportedComponents.end();
+    }
+    if (lg->carryAllowed && exec->carryMode != 0u) {
+        rc = makeGraph(true, &lg->steadyGraph, &lg->steadyExec);
+        if (rc != 0) return rc;
+    }
     out = std::move(lg);
     return 0;
 }

@@ -483,6 +483,7 @@ int restoreSnapshot(mwhip_exec *exec, uint64_t snapshot, bool wait)
 
 extern "C" int mwhip_snapshot_create(mwhip_exec *exec, uint64_t *snapshot_out)
 {
+    carryStale(exec);
     if (exec == nullptr || !exec->stateBuilt || snapshot_out == nullptr) {
         return fail(-2, "snapshot_create: no executor state");
     }
@@ -503,6 +504,7 @@ extern "C" int mwhip_snapshot_create(mwhip_exec *exec, uint64_t *snapshot_out)
 
 extern "C" void mwhip_snapshot_destroy(mwhip_exec *exec, uint64_t snapshot)
 {
+    carryStale(exec);
     if (findSnapshot(exec, snapshot) == nullptr) return;
     (void)hipSetDevice(exec->cfg.gpu_id);
     (void)hipStreamSynchronize(exec->stream);
@@ -511,6 +513,7 @@ extern "C" void mwhip_snapshot_destroy(mwhip_exec *exec, uint64_t snapshot)
 
 extern "C" int mwhip_snapshot_save(mwhip_exec *exec, uint64_t snapshot)
 {
+    carryStale(exec);
     mwhip_snapshot_rec *snap = findSnapshot(exec, snapshot);
     if (snap == nullptr) return unknownObject("snapshot", snapshot);
     HIPCHK(hipSetDevice(exec->cfg.gpu_id));
@@ -530,6 +533,7 @@ extern "C" int mwhip_snapshot_save(mwhip_exec *exec, uint64_t snapshot)
 // (into the room the snapshot has)
 extern "C" int mwhip_snapshot_save_async(mwhip_exec *exec, uint64_t snapshot)
 {
+    carryStale(exec);
     mwhip_snapshot_rec *snap = findSnapshot(exec, snapshot);
     if (snap == nullptr) return unknownObject("snapshot", snapshot);
     HIPCHK(hipSetDevice(exec->cfg.gpu_id));
@@ -538,11 +542,13 @@ extern "C" int mwhip_snapshot_save_async(mwhip_exec *exec, uint64_t snapshot)
 
 extern "C" int mwhip_snapshot_restore(mwhip_exec *exec, uint64_t snapshot)
 {
+    carryStale(exec);
     return restoreSnapshot(exec, snapshot, true);
 }
 
 extern "C" int mwhip_snapshot_restore_async(mwhip_exec *exec, uint64_t snapshot)
 {
+    carryStale(exec);
     return restoreSnapshot(exec, snapshot, false);
 }
 

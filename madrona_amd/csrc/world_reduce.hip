@@ -499,6 +499,7 @@ extern "C" int mwhip_reduce_create(mwhip_exec *exec, uint32_t archetype_id,
                                    const mwhip_reduce_term *terms, uint32_t n,
                                    uint64_t *reduce_out)
 {
+    carryStale(exec);
     // (every refusal comes before anything is allocated)
     if (exec == nullptr || !exec->stateBuilt || reduce_out == nullptr) {
         return fail(-2, "reduce_create: no executor state");
@@ -649,6 +650,7 @@ extern "C" int mwhip_reduce_create(mwhip_exec *exec, uint32_t archetype_id,
 
 extern "C" int mwhip_set_step_reduce(mwhip_exec *exec, uint64_t reduce, int on)
 {
+    carryStale(exec);
     if (findReduce(exec, reduce) == nullptr) return unknownObject("reduce", reduce);
     const std::vector<uint64_t> &step_reduces = exec->extras.stepReduces;
     const bool is_on =
@@ -671,6 +673,7 @@ extern "C" int mwhip_set_step_reduce(mwhip_exec *exec, uint64_t reduce, int on)
 
 extern "C" void mwhip_reduce_destroy(mwhip_exec *exec, uint64_t handle)
 {
+    carryStale(exec);
     if (findReduce(exec, handle) == nullptr) return;
     (void)hipSetDevice(exec->cfg.gpu_id);
     // (the step graphs must stop naming its buffers before they go; if they
@@ -682,11 +685,13 @@ extern "C" void mwhip_reduce_destroy(mwhip_exec *exec, uint64_t handle)
 
 extern "C" int mwhip_reduce_compute(mwhip_exec *exec, uint64_t handle)
 {
+    carryStale(exec);
     return computeReduce(exec, handle, true);
 }
 
 extern "C" int mwhip_reduce_compute_async(mwhip_exec *exec, uint64_t handle)
 {
+    carryStale(exec);
     return computeReduce(exec, handle, false);
 }
 

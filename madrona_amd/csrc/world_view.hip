@@ -338,6 +338,7 @@ extern "C" int mwhip_view_create(mwhip_exec *exec, uint32_t archetype_id,
                                  const uint32_t *component_ids, uint32_t n,
                                  uint32_t max_rows, uint64_t *view_out)
 {
+    carryStale(exec);
     // (every refusal comes before anything is allocated)
     if (exec == nullptr || !exec->stateBuilt || view_out == nullptr) {
         return fail(-2, "view_create: no executor state");
@@ -412,6 +413,7 @@ extern "C" int mwhip_view_create(mwhip_exec *exec, uint32_t archetype_id,
 
 extern "C" int mwhip_set_step_view(mwhip_exec *exec, uint64_t view, int on)
 {
+    carryStale(exec);
     if (findView(exec, view) == nullptr) return unknownObject("view", view);
     const std::vector<uint64_t> &step_views = exec->extras.stepViews;
     const bool is_on = std::find(step_views.begin(), step_views.end(), view) != step_views.end();
@@ -433,6 +435,7 @@ extern "C" int mwhip_set_step_view(mwhip_exec *exec, uint64_t view, int on)
 
 extern "C" void mwhip_view_destroy(mwhip_exec *exec, uint64_t handle)
 {
+    carryStale(exec);
     if (findView(exec, handle) == nullptr) return;
     (void)hipSetDevice(exec->cfg.gpu_id);
     // (the step graphs must stop naming its buffers before they go; if they
@@ -444,11 +447,13 @@ extern "C" void mwhip_view_destroy(mwhip_exec *exec, uint64_t handle)
 
 extern "C" int mwhip_view_compute(mwhip_exec *exec, uint64_t handle)
 {
+    carryStale(exec);
     return computeView(exec, handle, true);
 }
 
 extern "C" int mwhip_view_compute_async(mwhip_exec *exec, uint64_t handle)
 {
+    carryStale(exec);
     return computeView(exec, handle, false);
 }
 

@@ -333,6 +333,7 @@ extern "C" int mwhip_write_create(mwhip_exec *exec, uint32_t archetype_id,
                                   const uint32_t *component_ids, uint32_t n,
                                   uint32_t max_rows, uint64_t *write_out)
 {
+    carryStale(exec);
     // (every refusal comes before anything is allocated)
     if (exec == nullptr || !exec->stateBuilt || write_out == nullptr) {
         return fail(-2, "write_create: no executor state");
@@ -422,6 +423,7 @@ extern "C" int mwhip_write_create(mwhip_exec *exec, uint32_t archetype_id,
 
 extern "C" int mwhip_set_step_write(mwhip_exec *exec, uint64_t write, int on)
 {
+    carryStale(exec);
     if (findWrite(exec, write) == nullptr) return unknownObject("write", write);
     const std::vector<uint64_t> &step_writes = exec->extras.stepWrites;
     const bool is_on =
@@ -444,6 +446,7 @@ extern "C" int mwhip_set_step_write(mwhip_exec *exec, uint64_t write, int on)
 
 extern "C" void mwhip_write_destroy(mwhip_exec *exec, uint64_t handle)
 {
+    carryStale(exec);
     if (findWrite(exec, handle) == nullptr) return;
     (void)hipSetDevice(exec->cfg.gpu_id);
     // (the step graphs must stop naming its buffers before they go; if they
@@ -455,11 +458,13 @@ extern "C" void mwhip_write_destroy(mwhip_exec *exec, uint64_t handle)
 
 extern "C" int mwhip_write_apply(mwhip_exec *exec, uint64_t handle)
 {
+    carryStale(exec);
     return applyWrite(exec, handle, true);
 }
 
 extern "C" int mwhip_write_apply_async(mwhip_exec *exec, uint64_t handle)
 {
+    carryStale(exec);
     return applyWrite(exec, handle, false);
 }
 

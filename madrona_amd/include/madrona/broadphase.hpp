@@ -274,6 +274,18 @@ public:
         const math::Diag3x3 &scale, const math::Vector3 &linear_vel,
         const math::AABB &obj_aabb);
 
+    // Would applyLeafUpdate with these arguments change nothing?  True when the
+    // leaf's box and transform are stored bit for bit and the leaf's slot
+    // already contains the box (then no ancestor grows either); false when a
+    // rebuild is pending.  Stores nothing.  (sortedLeaves[leaf], which
+    // applyLeafUpdate resets for the next rebuild, is not compared: a rebuild
+    // always runs behind a leaf update that has just reset it.)
+    MADRONA_HD static inline bool leafUpdateIsStored(
+        const RefitView &view, int32_t leaf, math::AABB slot,
+        const math::Vector3 &pos, const math::Quat &rot,
+        const math::Diag3x3 &scale, const math::Vector3 &linear_vel,
+        const math::AABB &obj_aabb);
+
     // == leafSlotBounds(leaf) with parent = view.leafParents[leaf]
     MADRONA_HD static inline math::AABB loadSlotBounds(const void *nodes,
                                                        uint32_t parent)

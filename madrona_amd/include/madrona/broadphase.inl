@@ -346,6 +346,47 @@ void BVH::applyLeafUpdate(const RefitView &view, int32_t leaf,
     growAncestors(nodes, node_idx, leaf_aabb);
 }
 
+bool BVH::leafUpdateIsStored(const RefitView &view, int32_t leaf,
+                             math::AABB slot,
+                             const math::Vector3 &pos, const math::Quat &rot,
+                             const math::Diag3x3 &scale,
+                             const math::Vector3 &linear_vel,
+                             const math::AABB &obj_aabb)
+{
+    using mwhip::loadGlobal;
+
+    if (!view.refit) {
+        return false;
+    }
+    const math::AABB world_aabb = obj_aabb.applyTRS(pos, rot, scale);
+    const math::AABB leaf_aabb = detail::expandAABBWithMotion(
+        world_aabb, linear_vel, view.velocityExpansion, view.accelExpansion);
+    const LeafTransform would { pos, rot, scale };
+
+    const math::AABB stored_aabb = loadGlobal(view.leafAABBs + leaf);
+    const LeafTransform stored =
+        loadGlobal((const LeafTransform *)view.leafTransforms + leaf);
+    // (bit for bit: a NaN that is stored again is no difference)
+    auto sameWords = [](const auto &a, const auto &b) {
+        static_assert(sizeof(a) == sizeof(b) && sizeof(a) % 4 == 0);
+        uint32_t wa[sizeof(a) / 4], wb[sizeof(b) / 4];
+        __builtin_memcpy(wa, &a, sizeof(a));
+        __builtin_memcpy(wb, &b, sizeof(b));
+        bool same = true;
+        for (size_t i = 0; i < sizeof(a) / 4; i++) {
+            same = same && wa[i] == wb[i];
+        }
+        return same;
+    };
+    bool same = sameWords(stored_aabb, leaf_aabb) && sameWords(stored, would);
+    // the slot after growth is the slot
+    same = same &&
+        !(leaf_aabb.pMin.x < slot.pMin.x) && !(leaf_aabb.pMin.y < slot.pMin.y) &&
+        !(leaf_aabb.pMin.z < slot.pMin.z) && !(leaf_aabb.pMax.x > slot.pMax.x) &&
+        !(leaf_aabb.pMax.y > slot.pMax.y) && !(leaf_aabb.pMax.z > slot.pMax.z);
+    return same;
+}
+
 // Upper levels of a refit: several leaves of a world grow them concurrently.
 void BVH::growAncestors(int32_t child_idx, const math::AABB &leaf_aabb)
 {

@@ -213,8 +213,27 @@ MADRONA_HD inline Entity makeHingeJoint(
 // ---- registration and task graph (host) ------------------------------------------
 MADRONA_HOST_API inline void registerTypes(ECSRegistry &registry,
                                            Solver solver = Solver::XPBD);
+// This backend only (the reference's setupBroadphaseTasks takes two arguments:
+// simulators pass the third behind their SIM_WAVE_API switch).
+// CarriedOver is the simulator's PROMISE about this broadphase: since the last
+// Changed broadphase of the previous replay of this task graph (of the launch
+// graph it is replayed in), no node has
+//   - written Position, Rotation, Scale, ObjectID or Velocity of a registered
+//     body,
+//   - registered or removed a body,
+//   - called BVH::rebuildOnUpdate() or PhysicsSystem::reset().
+// Its leaf refresh then finds the boxes and transforms it would store already
+// stored, and a replay that directly follows a replay of the same launch graph
+// leaves the launch out (MWHIP_NODE_CARRIED; when exactly: DESIGN.md section 30,
+// INTEGRATION.md section 3).  A task graph needs a Changed broadphase behind a
+// CarriedOver one, or building its launch graph fails.
+// MADRONA_MWHIP_CARRY_BROADPHASE=2 checks the promise on the device
+// (kErrPhysics when a leaf box, a leaf transform or a slot would change, or a
+// rebuild is pending); =0 runs every broadphase.
+enum class BroadphaseInputs : uint32_t { Changed, CarriedOver };
 MADRONA_HOST_API inline TaskGraphNodeID setupBroadphaseTasks(
-    TaskGraphBuilder &builder, Span<const TaskGraphNodeID> deps);
+    TaskGraphBuilder &builder, Span<const TaskGraphNodeID> deps,
+    BroadphaseInputs inputs = BroadphaseInputs::Changed);
 MADRONA_HOST_API inline TaskGraphNodeID setupPhysicsStepTasks(
     TaskGraphBuilder &builder, Span<const TaskGraphNodeID> deps,
     CountT num_substeps, Solver solver = Solver::XPBD);

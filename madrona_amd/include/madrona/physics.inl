@@ -1598,7 +1598,16 @@ __device__ inline void rebuildTreeStaged(broadphase::BVH &bvh, uint32_t lane,
 // 4096 wavefronts -- took 3.2 and 1.6 us off the first two launches of a step
 // and added 1.6 to the one that rebuilds: 0.4 % of the step, inside the noise
 // of the headline, not kept)
-template <bool WithRebuild>
+// The first broadphase of a step follows nodes that leave every input of this
+// kernel alone (observations, the input ring, the movement system: forces and
+// torques only), so when the previous thing the executor ran was the same step
+// it stores what is stored.  Simulators say so with BroadphaseInputs::CarriedOver
+// and the runtime leaves the launch out of such replays.
+// Verify (MADRONA_MWHIP_CARRY_BROADPHASE=2, in place of such a launch): a lane
+// compares what it would store with what is stored (BVH::leafUpdateIsStored),
+// the wavefront raises kErrPhysics on a difference or a pending rebuild, and
+// nothing is stored or rebuilt.
+template <bool WithRebuild, bool Verify = false>
 __global__ void __launch_bounds__(64)
 bvhRefreshKernel(EcsState *S, void *, uint32_t, uint32_t)
 {
@@ -1626,6 +1635,7 @@ bvhRefreshKernel(EcsState *S, void *, uint32_t, uint32_t)
          world += (int32_t)gridDim.x) {
         const BVH::RefreshView view = BVH::loadRefreshView(trees + world);
         const math::AABB *body_aabbs = nullptr;
+        [[maybe_unused]] bool broken = !view.refit.refit;
         for (int32_t leaf = (int32_t)lane; leaf < view.numLeaves; leaf += 64) {
             // ---- round 3 ----
             if (body_aabbs == nullptr) {
@@ -1685,10 +1695,19 @@ bvhRefreshKernel(EcsState *S, void *, uint32_t, uint32_t)
                 obj_aabb = loadGlobal(body_aabbs + obj_id.idx);
             }
 
-            BVH::applyLeafUpdate(view.refit, leaf, leaf_parent, slot, pos, rot,
-                                 scale, vel.linear, obj_aabb);
+            if constexpr (Verify) {
+                broken = broken || !BVH::leafUpdateIsStored(view.refit, leaf, slot,
+                    pos, rot, scale, vel.linear, obj_aabb);
+            } else {
+                BVH::applyLeafUpdate(view.refit, leaf, leaf_parent, slot, pos, rot,
+                                     scale, vel.linear, obj_aabb);
+            }
         }
-        if constexpr (WithRebuild) {
+        if constexpr (Verify) {
+            if (__builtin_amdgcn_ballot_w64(broken) != 0ull) {
+                mwhip::raiseError(S, mwhip::kErrPhysics);
+            }
+        } else if constexpr (WithRebuild) {
             if (!view.refit.refit) {
                 // (a rebuild is pending: the leaf boxes just stored are what it
                 // builds from)
@@ -2196,7 +2215,8 @@ MADRONA_HOST_API inline void registerTypes(ECSRegistry &registry, Solver solver)
 
 MADRONA_HOST_API inline TaskGraphNodeID setupBroadphaseTasks(
     TaskGraphBuilder &builder,
-    Span<const TaskGraphNodeID> deps);
+    Span<const TaskGraphNodeID> deps,
+    BroadphaseInputs inputs);
 
 namespace detail {
 
@@ -2362,9 +2382,12 @@ MADRONA_HOST_API inline TaskGraphNodeID setupCandidateTasks(
 // (*rebuilt_out = true) -- MADRONA_MWHIP_BVH_REFRESH: 0 = the ParallelFor, 1 =
 // the refresh kernel with a rebuild launch of its own behind it, 2 (default) =
 // the refresh kernel rebuilds
+// carried: BroadphaseInputs::CarriedOver -- the node is flagged
+// MWHIP_NODE_CARRIED, and the runtime is told what it reads and which kernel
+// checks the promise in its place
 MADRONA_HOST_API inline TaskGraphNodeID setupLeafRefreshTasks(
     TaskGraphBuilder &builder, Span<const TaskGraphNodeID> deps,
-    bool with_rebuild = false, bool *rebuilt_out = nullptr)
+    bool with_rebuild = false, bool *rebuilt_out = nullptr, bool carried = false)
 {
     using namespace base;
     using broadphase::LeafID;
@@ -2374,8 +2397,13 @@ MADRONA_HOST_API inline TaskGraphNodeID setupLeafRefreshTasks(
         return rebuild ? (const void *)&kernels::bvhRefreshKernel<true> :
                          (const void *)&kernels::bvhRefreshKernel<false>;
     };
+    [[maybe_unused]] auto verify_stub = [] __host__ (bool rebuild) -> const void * {
+        return rebuild ? (const void *)&kernels::bvhRefreshKernel<true, true> :
+                         (const void *)&kernels::bvhRefreshKernel<false, true>;
+    };
 #else
     auto refresh_stub = [](bool) -> const void * { return nullptr; };
+    auto verify_stub = [](bool) -> const void * { return nullptr; };
 #endif
 
     if (rebuilt_out != nullptr) {
@@ -2395,14 +2423,38 @@ MADRONA_HOST_API inline TaskGraphNodeID setupLeafRefreshTasks(
         if (rebuilt_out != nullptr) {
             *rebuilt_out = rebuild;
         }
+        if (carried) {
+            desc.kind |= MWHIP_NODE_CARRIED;
+            const uint32_t reads[] = {
+                TypeTracker::typeID<Position>(), TypeTracker::typeID<Rotation>(),
+                TypeTracker::typeID<Scale>(), TypeTracker::typeID<ObjectID>(),
+                TypeTracker::typeID<Velocity>() };
+            mwhip::check(mwhip_carried_reads(builder.exec(), reads, 5),
+                         "carried_reads");
+            mwhip::check(mwhip_carried_check(builder.exec(), desc.kernel,
+                                             verify_stub(rebuild)), "carried_check");
+        }
         return builder.addRuntimeNode(desc, -1, deps);
     }
 #else
     (void)with_rebuild;
 #endif
-    return builder.addToGraph<ParallelForNode<Context,
+    auto update = builder.addToGraph<ParallelForNode<Context,
         broadphase::updateLeafAndRefitEntry,
             LeafID, Position, Rotation, Scale, ObjectID, Velocity>>(deps);
+#if MADRONA_ON_HOST
+    if (carried) {
+        // (the ParallelFor flavour has no checking kernel: mode 2 runs it)
+        const uint32_t reads[] = {
+            TypeTracker::typeID<Position>(), TypeTracker::typeID<Rotation>(),
+            TypeTracker::typeID<Scale>(), TypeTracker::typeID<ObjectID>(),
+            TypeTracker::typeID<Velocity>() };
+        mwhip::check(mwhip_carried_reads(builder.exec(), reads, 5),
+                     "carried_reads");
+        builder.markCarried(update);
+    }
+#endif
+    return update;
 }
 
 MADRONA_HOST_API inline TaskGraphNodeID setupPostIntegrationTasks(
@@ -2415,7 +2467,8 @@ MADRONA_HOST_API inline TaskGraphNodeID setupPostIntegrationTasks(
 
 MADRONA_HOST_API inline TaskGraphNodeID setupBroadphaseTasks(
     TaskGraphBuilder &builder,
-    Span<const TaskGraphNodeID> deps)
+    Span<const TaskGraphNodeID> deps,
+    BroadphaseInputs inputs)
 {
     using namespace base;
     using broadphase::LeafID;
@@ -2429,8 +2482,10 @@ MADRONA_HOST_API inline TaskGraphNodeID setupBroadphaseTasks(
     auto bvh_stub = [](bool) -> const void * { return nullptr; };
 #endif
 
+    const bool carried = inputs == BroadphaseInputs::CarriedOver;
     bool rebuilt = false;
-    auto update_leaves = detail::setupLeafRefreshTasks(builder, deps, true, &rebuilt);
+    auto update_leaves = detail::setupLeafRefreshTasks(builder, deps, true, &rebuilt,
+                                                       carried);
 
     TaskGraphNodeID bvh_update = update_leaves;
 #if MADRONA_ON_HOST
@@ -2444,6 +2499,10 @@ MADRONA_HOST_API inline TaskGraphNodeID setupBroadphaseTasks(
         desc.kernel = bvh_stub(check_env != nullptr && atoi(check_env) != 0);
         desc.count_mode = MWHIP_COUNT_PER_WORLD;
         desc.threads_per_invocation = 64;
+        // (no rebuild is pending behind a carried refresh: the launch goes too)
+        if (carried) {
+            desc.kind |= MWHIP_NODE_CARRIED;
+        }
         bvh_update = builder.addRuntimeNode(desc, -1, {update_leaves});
     }
 #endif

@@ -164,6 +164,14 @@ public:
         inline NodeID addRuntimeNode(const mwhip_node_desc &desc,
                                      int32_t staged_data_idx,
                                      Span<const NodeID> dependencies);
+        // Backend-facing: flags a staged node MWHIP_NODE_CARRIED (mwhip.h): a
+        // replay that directly follows a replay of the same launch graph
+        // leaves its launches out.  For nodes staged through addToGraph;
+        // addRuntimeNode callers set the bit in desc.kind themselves.
+        inline void markCarried(NodeID node)
+        {
+            staged_[(size_t)node.id].desc.kind |= MWHIP_NODE_CARRIED;
+        }
 
         // Uploads node data blocks and registers all staged nodes.
         inline void flush();

@@ -1231,6 +1231,23 @@ class Simulator:
                                       rows_reused=int(reuse.rows_reused))
             archetype += 1
 
+    def broadphase_stats(self, graph: int = 0) -> Dict[str, int]:
+        """Replays of launch graph `graph` (default: the step graph) so far that
+        left out the launches the simulator flagged as carried over
+        (PhysicsSystem::BroadphaseInputs::CarriedOver), and replays that ran
+        everything: {"carried_replays": n, "full_replays": m}
+        (mwhip_broadphase_carry_stats; HIP backend).  Counted when a replay is
+        queued; does not wait for the stream."""
+        rt = runtime_lib()
+        counters = (C.c_uint64 * 2)()
+        rt.mwhip_broadphase_carry_stats.restype = C.c_int32
+        rt.mwhip_broadphase_carry_stats.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+        graph = graph or int(self.lib.sim_hip_step_graph(self.handle))
+        rc = rt.mwhip_broadphase_carry_stats(self.hip_exec(), graph, counters)
+        if rc != 0:
+            raise RuntimeError(f"mwhip_broadphase_carry_stats({graph}) -> {rc}")
+        return {"carried_replays": int(counters[0]), "full_replays": int(counters[1])}
+
     def snapshot(self) -> "Snapshot":
         """A new, empty Snapshot of this simulator (HIP backend; raises on the
         reference backend, which has no executor to ask)."""

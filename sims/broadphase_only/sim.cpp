@@ -13,7 +13,7 @@ using madrona::base::ObjectID;
 
 namespace bponly {
 
-void Sim::registerTypes(ECSRegistry &registry, const Config &)
+void Sim::registerTypes(ECSRegistry &registry, const Config &cfg)
 {
     base::registerTypes(registry);
     PhysicsSystem::registerTypes(registry);
@@ -31,6 +31,9 @@ void Sim::registerTypes(ECSRegistry &registry, const Config &)
     registry.registerArchetype<Prober>();
 
     registry.exportSingleton<StepCount>((uint32_t)ExportID::StepCount);
+    if ((cfg.flags & plan::flagExportPosition) != 0) {
+        registry.exportColumn<Box, Position>((uint32_t)ExportID::BoxPosition);
+    }
 }
 
 static inline void setupBody(Engine &ctx, Entity e, Vector3 pos, Diag3x3 scale,
@@ -95,6 +98,17 @@ inline void reregisterSystem(Engine &ctx, StepCount &steps)
         Entity e = sim.pillars[i];
         ctx.get<broadphase::LeafID>(e) =
             PhysicsSystem::registerEntity(ctx, e, ctx.get<ObjectID>(e));
+    }
+}
+
+// (plan::flagCarriedNudge) moves the world's first box without telling anyone
+inline void nudgeSystem(Engine &ctx, StepCount &)
+{
+    Sim &sim = ctx.data();
+    if (sim.numBoxes > 0) {
+        Vector3 p = ctx.get<Position>(sim.boxes[0]);
+        p.z += 0.125f;
+        ctx.get<Position>(sim.boxes[0]) = p;
     }
 }
 
@@ -266,6 +280,17 @@ void Sim::setupTasks(TaskGraphManager &taskgraph_mgr, const Config &cfg)
     // last step's pairs stay readable until the next step starts
     auto cleanup =
         PhysicsSystem::setupStandaloneBroadphaseCleanupTasks(builder, {});
+
+#if defined(MADRONA_GPU_MODE) && !defined(SIM_PORTABLE)
+    if ((cfg.flags & plan::flagCarried) != 0) {
+        if ((cfg.flags & plan::flagCarriedNudge) != 0) {
+            cleanup = builder.addToGraph<ParallelForNode<Engine,
+                nudgeSystem, StepCount>>({cleanup});
+        }
+        cleanup = PhysicsSystem::setupBroadphaseTasks(builder, {cleanup},
+            PhysicsSystem::BroadphaseInputs::CarriedOver);
+    }
+#endif
 
     auto drift = builder.addToGraph<ParallelForNode<Engine,
         driftSystem, Position, Velocity, Drift>>({cleanup});

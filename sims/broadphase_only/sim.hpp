@@ -60,6 +60,15 @@ inline constexpr uint32_t flagPlan = 1u << 1;
 inline constexpr uint32_t flagNoPillars = 1u << 2;
 inline constexpr uint32_t maxLeavesShift = 4;     // 2 bits
 inline constexpr uint32_t layoutShift = 8;        // 3 bits
+// MI355X backend only (tests of BroadphaseInputs::CarriedOver, physics.hpp):
+// a CarriedOver broadphase opens the step, in front of the drift -- nothing
+// between the step's own broadphase and it writes a body ...
+inline constexpr uint32_t flagCarried = 1u << 12;
+// ... unless this is set: a node in front of it moves each world's first box
+// (a broken promise, for MADRONA_MWHIP_CARRY_BROADPHASE=2 to find)
+inline constexpr uint32_t flagCarriedNudge = 1u << 13;
+// the boxes' Position column is exported: every replay stays full
+inline constexpr uint32_t flagExportPosition = 1u << 15;
 
 enum class MaxLeaves : uint32_t { Exact = 0, Staged64 = 1, InPlace65 = 2 };
 
@@ -108,7 +117,7 @@ inline float probeHalf(int32_t k)
 }
 }
 
-enum class ExportID : uint32_t { StepCount, NumExports };
+enum class ExportID : uint32_t { StepCount, BoxPosition, NumExports };
 
 struct Drift { Vector3 v; };
 struct StepCount { int32_t n; };

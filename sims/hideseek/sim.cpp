@@ -1000,8 +1000,16 @@ void Sim::setupTasks(TaskGraphManager &taskgraph_mgr, const Config &)
             ExternalTorque
         >>({});
 
+    // Between the step's last broadphase and this one run the observation
+    // systems (read only), the input ring (actions) and movementSystem (forces
+    // and torques; it reads the rotation): the leaves are up to date.
+#ifdef SIM_WAVE_API
+    auto broadphase_setup_sys = PhysicsSystem::setupBroadphaseTasks(
+        builder, {move_sys}, PhysicsSystem::BroadphaseInputs::CarriedOver);
+#else
     auto broadphase_setup_sys =
         PhysicsSystem::setupBroadphaseTasks(builder, {move_sys});
+#endif
 
 #ifdef SIM_WAVE_API
     // the lock queries test a BVH leaf per lane

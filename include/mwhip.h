@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded() and mwhip_digest_*() / mwhip_set_step_digest() (a per-world hash of chosen columns computed on the device) and mwhip_view_*() / mwhip_set_step_view() (padded per-world tensors of a table's columns) and mwhip_write_*() / mwhip_set_step_write() (padded per-world tensors scattered into a table's columns) and mwhip_reduce_term / mwhip_reduce_*() / mwhip_set_step_reduce() (per-world sums, extrema, counts and alarms of a table's columns) and MWHIP_NODE_CARRIED / mwhip_broadphase_carry_stats() (launches a steady replay leaves out, a bit of mwhip_node_desc::kind that earlier libraries never set); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
+#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded() and mwhip_digest_*() / mwhip_set_step_digest() (a per-world hash of chosen columns computed on the device) and mwhip_view_*() / mwhip_set_step_view() (padded per-world tensors of a table's columns) and mwhip_write_*() / mwhip_set_step_write() (padded per-world tensors scattered into a table's columns) and mwhip_reduce_term / mwhip_reduce_*() / mwhip_set_step_reduce() (per-world sums, extrema, counts and alarms of a table's columns) and mwhip_gather_source / mwhip_gather_*() / mwhip_set_step_gather() (the cells of the entities a run of handles in device memory names) and MWHIP_NODE_CARRIED / mwhip_broadphase_carry_stats() (launches a steady replay leaves out, a bit of mwhip_node_desc::kind that earlier libraries never set); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
 
 typedef struct mwhip_exec mwhip_exec; /* opaque; == MWCudaExecutor::Impl */
 
@@ -988,6 +988,98 @@ void *mwhip_reduce_buffer(mwhip_exec *exec, uint64_t reduce, uint32_t term,
 int32_t *mwhip_reduce_counts(mwhip_exec *exec, uint64_t reduce);
 int32_t *mwhip_reduce_alarm(mwhip_exec *exec, uint64_t reduce);
 int mwhip_set_step_reduce(mwhip_exec *exec, uint64_t reduce, int on);
+
+/* Entity gathers (added under ABI 9): N entity handles read from device memory
+ * turned into, per listed component, the cell the entity each handle names
+ * has, plus where that entity lives, by one kernel that goes through the
+ * entity store as Context::get<T>(e) does (DESIGN.md §31;
+ * madrona_amd/gather_ref.py is the same definition in numpy).
+ * The SOURCE is a run of records: num_records records of record_bytes each
+ * from src on, and in each record handles_per_record consecutive 8-byte Entity
+ * cells ({ uint32 gen; int32 id }) from byte first_byte on.  N = num_records *
+ * handles_per_record; handle i is read at
+ *   src + (i / handles_per_record) * record_bytes + first_byte
+ *       + (i % handles_per_record) * 8.
+ * A handle h NAMES row r of table a exactly when h.id >= 0, a is a registered
+ * archetype, 0 <= r < numRows(a), the Entity cell of that row (column 0) equals
+ * h bit for bit and the row's WorldID cell (column 1) is not -1.  (A row
+ * destroyed in place and a temporary's row hold Entity::none(), id -1: a
+ * negative id names nothing.)  Such a row is unique if it exists.  A compute leaves
+ *   archetype[i]  (int32) a, or -1 when handle i names nothing;
+ *   world[i]      (int32) that row's WorldID cell, or -1 likewise;
+ *   G_c[i]        for each listed component c, the row's cell of c; all zero
+ *                 when handle i names nothing or table a has no column of c.
+ * Every byte of every output is rewritten by every compute.  Handles are
+ * arbitrary bits (a stale generation, Entity::none(), an id nobody has, zero
+ * padding, anything a caller wrote): the kernel dereferences nothing behind a
+ * check that failed.  Row counts, column addresses, the entity store's size
+ * and the handles themselves are read on the device when the kernel runs: a
+ * gather made before a table or the entity store grew, or before a sort
+ * swapped a column with its twin, stays right.  n == 0 is allowed (only
+ * archetype and world are produced); Entity (component 0) and WorldID
+ * (component 1) may be listed like any other component.
+ *
+ * src is the caller's: it must be 4-byte aligned and stay valid and in place
+ * while the gather exists.  An exported tensor (pinned), a world view's slab
+ * (mwhip_view_buffer), a gather's own buffer, any device allocation are valid
+ * sources.  A table column's own address is NOT: the sort swaps a column with
+ * its twin.  To read a column of handles, make a world view of it and gather
+ * through the view's slab (handles_per_record > 1 and first_byte address
+ * handles inside wider cells, e.g. Entity buttons[4] of a 40-byte cell).
+ *
+ * mwhip_gather_buffer: device address of uint8 G_c[N][cell_bytes] of listed
+ * component `column` (position in the list), 256-byte aligned, owned by the
+ * executor and valid until the gather is destroyed; NULL for an unknown handle
+ * or a column index out of range.  mwhip_gather_archetypes / mwhip_gather_worlds:
+ * int32 [N], likewise.
+ * mwhip_set_step_gather(on != 0): every replay of every STEP graph of the
+ * executor (packed ones included; render graphs are untouched) recomputes the
+ * gather directly behind the step views -- so a gather may read a step view's
+ * slab of the same replay -- and before the step reduces, the pack node and
+ * the output rings: a step view of a handle column, a step gather over its
+ * slab and an output ring over mwhip_gather_buffer() record
+ * [K][W][rows][handles][cell_bytes] of referenced entities with nothing but
+ * graph launches on the stream.  Up to MWHIP_MAX_STEP_GATHERS step gathers,
+ * ONE launch for all of them; mwhip_profile lists it with role "gather",
+ * algo_bytes = bytes written (the buffers, archetype and world in full) +
+ * bytes read (the handles, and per handle that named an entity its slot, its
+ * row's Entity and WorldID cells and the listed cells).  on == 0 takes it out
+ * again.  The set lives in the executor, not in a graph: changing it waits for
+ * the stream and rebuilds the launch graphs (handles stay valid).  Destroying a
+ * step gather unsets it.  Gathers are derived state: snapshots do not save
+ * them (a restore followed by a compute gives the restored worlds' gather).
+ * Handles are unique in the process; mwhip_destroy frees what is left.
+ * Errors (non-zero, text in mwhip_last_error(), nothing changed or allocated):
+ * -3 for an unknown handle or one of another executor ("gather N is not one of
+ * this executor's"; looked up first, so also with a null executor); -2 for a
+ * null src, src / record_bytes / first_byte not a multiple of 4,
+ * handles_per_record == 0, first_byte + 8 * handles_per_record > record_bytes,
+ * num_records == 0, N > 2^31 - 1, n > MWHIP_GATHER_MAX_COLUMNS, a component
+ * that is not registered, a component listed twice, a ninth step gather; -10
+ * for buffers that cannot be allocated.
+ * (No reference counterpart.) */
+#define MWHIP_GATHER_MAX_COLUMNS 32
+#define MWHIP_MAX_STEP_GATHERS 8
+typedef struct mwhip_gather_source {
+    const void *src;                /* device address of record 0 */
+    uint64_t num_records;
+    uint32_t record_bytes;
+    uint32_t first_byte;            /* of handle 0 inside a record */
+    uint32_t handles_per_record;
+    uint32_t pad_;
+} mwhip_gather_source;
+int mwhip_gather_create(mwhip_exec *exec, const mwhip_gather_source *source,
+                        const uint32_t *component_ids, uint32_t n, uint64_t *gather_out);
+void mwhip_gather_destroy(mwhip_exec *exec, uint64_t gather);
+/* waits for the executor's stream */
+int mwhip_gather_compute(mwhip_exec *exec, uint64_t gather);
+/* queued on the executor's stream behind the replays queued so far */
+int mwhip_gather_compute_async(mwhip_exec *exec, uint64_t gather);
+void *mwhip_gather_buffer(mwhip_exec *exec, uint64_t gather, uint32_t column,
+                          uint64_t *bytes_out, uint32_t *cell_bytes_out);
+int32_t *mwhip_gather_archetypes(mwhip_exec *exec, uint64_t gather);
+int32_t *mwhip_gather_worlds(mwhip_exec *exec, uint64_t gather);
+int mwhip_set_step_gather(mwhip_exec *exec, uint64_t gather, int on);
 
 #ifdef __cplusplus
 }

@@ -5,7 +5,8 @@
 // output rings; snapshot.hip: saving and restoring all world state; digest.hip:
 // per-world state digests; world_view.hip: padded per-world views of a table's
 // columns; world_write.hip: the same tensors scattered into a table's columns;
-// world_reduce.hip: per-world reductions of a table's columns).
+// world_reduce.hip: per-world reductions of a table's columns;
+// entity_gather.hip: the cells of the entities a run of handles names).
 // Not installed.
 #pragma once
 #include "runtime_internal.hpp"
@@ -267,6 +268,7 @@ struct mwhip_digest_rec;        // (digest.hip)
 struct mwhip_view_rec;          // (world_view.hip)
 struct mwhip_write_rec;         // (world_write.hip)
 struct mwhip_reduce_rec;        // (world_reduce.hip)
+struct mwhip_gather_rec;        // (entity_gather.hip)
 
 // What a replay carries besides its task graphs.  Every launch graph is built
 // from it (the input rings and the step writes open a step graph, the rest are tail stages:
@@ -303,6 +305,9 @@ struct ReplayExtras {
     // mwhip_set_step_reduce: those every step replay recomputes, in one launch
     // behind the step views
     std::vector<uint64_t> stepReduces;
+    // mwhip_set_step_gather: those every step replay recomputes, in one launch
+    // directly behind the step views (whose slabs they may read)
+    std::vector<uint64_t> stepGathers;
 };
 
 struct mwhip_exec {
@@ -423,6 +428,7 @@ struct mwhip_exec {
     ExecObjectTable<mwhip_view_rec> views;
     ExecObjectTable<mwhip_write_rec> writes;
     ExecObjectTable<mwhip_reduce_rec> reduces;     // mwhip_reduce_create
+    ExecObjectTable<mwhip_gather_rec> gathers;     // mwhip_gather_create
 };
 
 // Bumped by what changes device memory or fails without naming an executor
@@ -500,6 +506,9 @@ MWHIP_RT int stepDigestStage(mwhip_exec *exec, const LaunchGraph &lg,
 MWHIP_RT int stepViewStage(mwhip_exec *exec, const LaunchGraph &lg,
                            std::vector<KernelLaunch> &out);
       // (world_view.hip)
+MWHIP_RT int stepGatherStage(mwhip_exec *exec, const LaunchGraph &lg,
+                             std::vector<KernelLaunch> &out);
+      // (entity_gather.hip)
 MWHIP_RT int stepReduceStage(mwhip_exec *exec, const LaunchGraph &lg,
                              std::vector<KernelLaunch> &out);
       // (world_reduce.hip)

@@ -684,6 +684,7 @@ extern "C" void mwhip_destroy(mwhip_exec *exec)
     exec->views.clear();
     exec->writes.clear();
     exec->reduces.clear();
+    exec->gathers.clear();
     for (void *p : exec->allocations) {
         (void)hipFree(p);
     }

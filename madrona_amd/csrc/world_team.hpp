@@ -1,7 +1,8 @@
 // What a TEAM of lanes of one wavefront does for one world of a table: shared
 // by the world views (worldViewKernel, world_view.hip), which copy a world's
 // rows out of the table, and the world writes (worldWriteKernel,
-// world_write.hip), which copy them in.  A team is T lanes (a power of two,
+// world_write.hip), which copy them in; the entity gathers (entityGatherKernel,
+// entity_gather.hip) copy single cells with the same teams.  A team is T lanes (a power of two,
 // 1 .. 64) of a wavefront; t is a lane's number in its team.  Device code of
 // libmadrona_hip.so; included behind exec_internal.hpp (TableHdr); not installed.
 #pragma once
@@ -39,6 +40,21 @@ __device__ inline void teamCopy(char *dst, const char *src, uint64_t n, uint32_t
         done = head + (num_words << 2);
     }
     for (uint64_t i = done + t; i < n; i += T) d8[i] = s8[i];
+}
+
+// n zero bytes by the T lanes of a team
+__device__ inline void teamZero(char *dst, uint64_t n, uint32_t t, uint32_t T)
+{
+    const uint64_t d = (uint64_t)dst;
+    GlobalU8 *d8 = (GlobalU8 *)d;
+    uint64_t head = (16ull - (d & 15ull)) & 15ull;
+    head = head < n ? head : n;
+    for (uint64_t i = t; i < head; i += T) d8[i] = (uint8_t)0;
+    const uint64_t num_vec = (n - head) >> 4;
+    GlobalU4 *d4 = (GlobalU4 *)(d + head);
+    const CopyU4 zero = { 0u, 0u, 0u, 0u };
+    for (uint64_t i = t; i < num_vec; i += T) d4[i] = zero;
+    for (uint64_t i = head + (num_vec << 4) + t; i < n; i += T) d8[i] = (uint8_t)0;
 }
 
 // one cell by one lane

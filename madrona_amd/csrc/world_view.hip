@@ -33,8 +33,8 @@
 // world's slabs: no atomics, no spin-waits, no workgroup waits for another, no
 // LDS.  (copyChunk of copy_chunk.hpp moves a chunk with a whole workgroup; a
 // team is a part of a wavefront, so only its vector types are shared.  What a
-// team does that the world writes need too -- teamCopy, cellCopy, teamRange --
-// is in world_team.hpp.)
+// team does that the world writes and the entity gathers need too -- teamCopy,
+// teamZero, cellCopy, teamRange -- is in world_team.hpp.)
 #include "exec_internal.hpp"
 #include "world_team.hpp"
 
@@ -73,21 +73,7 @@ using madrona::mwhip::GlobalU32;
 using madrona::mwhip::GlobalU8;
 using madrona::mwhip::cellCopy;
 using madrona::mwhip::teamCopy;
-
-// n zero bytes by the T lanes of a team
-__device__ inline void teamZero(char *dst, uint64_t n, uint32_t t, uint32_t T)
-{
-    const uint64_t d = (uint64_t)dst;
-    GlobalU8 *d8 = (GlobalU8 *)d;
-    uint64_t head = (16ull - (d & 15ull)) & 15ull;
-    head = head < n ? head : n;
-    for (uint64_t i = t; i < head; i += T) d8[i] = (uint8_t)0;
-    const uint64_t num_vec = (n - head) >> 4;
-    GlobalU4 *d4 = (GlobalU4 *)(d + head);
-    const CopyU4 zero = { 0u, 0u, 0u, 0u };
-    for (uint64_t i = t; i < num_vec; i += T) d4[i] = zero;
-    for (uint64_t i = head + (num_vec << 4) + t; i < n; i += T) d8[i] = (uint8_t)0;
-}
+using madrona::mwhip::teamZero;
 
 // Rows [from, to) of the table, T at a time: those whose WorldID cell is w are
 // appended to world w's slabs behind the `have` rows already there (rows past

@@ -176,8 +176,8 @@ friend class MWCudaExecutor;
 
 namespace detail {
 
-// What MWHipSnapshot, MWHipDigest, MWHipWorldView, MWHipWorldWrite and
-// MWHipWorldReduce share: the move-only handle
+// What MWHipSnapshot, MWHipDigest, MWHipWorldView, MWHipWorldWrite,
+// MWHipWorldReduce and MWHipEntityGather share: the move-only handle
 // of an object that belongs to an executor (mwhip_<kind>_create / _destroy,
 // include/mwhip.h).  Kind: { name, destroy(exec, handle) }.
 template <typename Kind>
@@ -249,6 +249,10 @@ struct WorldWriteKind {
 struct WorldReduceKind {
     static constexpr const char *name = "world reduce";
     static void destroy(mwhip_exec *exec, uint64_t handle) { mwhip_reduce_destroy(exec, handle); }
+};
+struct EntityGatherKind {
+    static constexpr const char *name = "entity gather";
+    static void destroy(mwhip_exec *exec, uint64_t handle) { mwhip_gather_destroy(exec, handle); }
 };
 
 }
@@ -509,6 +513,70 @@ private:
     uint32_t num_terms_;
     int32_t gpu_id_;
     bool is_float_[MWHIP_REDUCE_MAX_TERMS];
+
+friend class MWCudaExecutor;
+};
+
+// The cells of the entities a run of N handles in device memory names: per
+// listed component uint8 [N][cell bytes] on the device (zero where a handle
+// names nothing or its table has no such column), plus int32 [N] archetype and
+// world of each (-1 where it names nothing), written in full by one kernel that
+// goes through the entity store as Context::get<T>(e) does but trusts no bit
+// of a handle (mwhip_gather_*, include/mwhip.h: the exact definition and what
+// a valid source is -- never a table column's own address; read a column of
+// handles through a world view's slab).  An extension of this backend.
+// Belongs to the executor that made it and must not outlive it, nor its source.
+class MWHipEntityGather : public detail::ExecObject<detail::EntityGatherKind> {
+public:
+    MWHipEntityGather() : num_handles_(0), gpu_id_(0) {}
+
+    // waits for the executor's stream
+    void compute() { req(mwhip_gather_compute(exec_, handle_), "compute"); }
+    // queued on the executor's stream behind the replays queued so far
+    void computeAsync() { req(mwhip_gather_compute_async(exec_, handle_), "computeAsync"); }
+
+    // uint8 [numHandles()][cell bytes] of listed component `column` (position
+    // in the list given to makeEntityGather), owned by the executor
+    py::Tensor columnTensor(uint32_t column) const
+    {
+        uint64_t bytes = 0;
+        uint32_t cell = 0;
+        void *ptr = mwhip_gather_buffer(exec_, handle_, column, &bytes, &cell);
+        req(ptr != nullptr ? 0 : -1, "columnTensor");
+        const int64_t dims[2] = { (int64_t)num_handles_, (int64_t)cell };
+        return py::Tensor(ptr, py::TensorElementType::UInt8, Span<const int64_t>(dims, 2),
+                          Optional<int>::make((int)gpu_id_));
+    }
+
+    // int32 [numHandles()]: the archetype of the entity each handle names, -1: none
+    py::Tensor archetypesTensor() const
+    {
+        return perHandle(mwhip_gather_archetypes(exec_, handle_), "archetypesTensor");
+    }
+
+    // int32 [numHandles()]: the world that entity is in, -1: none
+    py::Tensor worldsTensor() const
+    {
+        return perHandle(mwhip_gather_worlds(exec_, handle_), "worldsTensor");
+    }
+
+    uint64_t numHandles() const { return num_handles_; }
+
+private:
+    MWHipEntityGather(mwhip_exec *exec, uint64_t gather, uint64_t num_handles, int32_t gpu_id)
+        : ExecObject(exec, gather), num_handles_(num_handles), gpu_id_(gpu_id)
+    {}
+
+    py::Tensor perHandle(void *ptr, const char *what) const
+    {
+        req(ptr != nullptr ? 0 : -1, what);
+        const int64_t dims[1] = { (int64_t)num_handles_ };
+        return py::Tensor(ptr, py::TensorElementType::Int32, Span<const int64_t>(dims, 1),
+                          Optional<int>::make((int)gpu_id_));
+    }
+
+    uint64_t num_handles_;
+    int32_t gpu_id_;
 
 friend class MWCudaExecutor;
 };
@@ -876,6 +944,28 @@ public:
     {
         req(mwhip_set_step_reduce(exec_, reduce != nullptr ? reduce->handle() : 0, on ? 1 : 0),
             "setStepReduce");
+    }
+
+    // the cells of `components` (component ids) of the entities the handles of
+    // `source` name (see MWHipEntityGather and mwhip_gather_source)
+    MWHipEntityGather makeEntityGather(const mwhip_gather_source &source,
+                                       Span<const uint32_t> components)
+    {
+        uint64_t gather = 0;
+        req(mwhip_gather_create(exec_, &source, components.data(),
+            (uint32_t)components.size(), &gather), "makeEntityGather");
+        return MWHipEntityGather(exec_, gather,
+                                 source.num_records * source.handles_per_record, gpu_id_);
+    }
+
+    // on: every replay of a step graph recomputes `gather` directly behind its
+    // step views, whose slabs it may read, and in front of its pack node and
+    // output rings (up to MWHIP_MAX_STEP_GATHERS gathers, one launch for all);
+    // off: no longer
+    void setStepGather(const MWHipEntityGather *gather, bool on)
+    {
+        req(mwhip_set_step_gather(exec_, gather != nullptr ? gather->handle() : 0, on ? 1 : 0),
+            "setStepGather");
     }
 
     // Device-resident rings (extensions of this backend, include/mwhip.h).

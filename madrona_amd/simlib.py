@@ -130,6 +130,13 @@ class ReduceTerm(C.Structure):
                 ("flags", C.c_uint32), ("limit", C.c_float)]
 
 
+class GatherSource(C.Structure):
+    """mwhip_gather_source (include/mwhip.h)."""
+    _fields_ = [("src", C.c_void_p), ("num_records", C.c_uint64),
+                ("record_bytes", C.c_uint32), ("first_byte", C.c_uint32),
+                ("handles_per_record", C.c_uint32), ("pad_", C.c_uint32)]
+
+
 class SortStats(C.Structure):
     """mwhip_sort_counters (include/mwhip.h)"""
     _fields_ = [(name, C.c_uint64) for name in
@@ -258,6 +265,23 @@ def runtime_lib() -> C.CDLL:
         fn.argtypes = [C.c_void_p, C.c_uint64]
     lib.mwhip_set_step_reduce.restype = C.c_int
     lib.mwhip_set_step_reduce.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
+    lib.mwhip_gather_create.restype = C.c_int
+    lib.mwhip_gather_create.argtypes = [C.c_void_p, C.POINTER(GatherSource),
+                                        C.POINTER(C.c_uint32), C.c_uint32,
+                                        C.POINTER(C.c_uint64)]
+    lib.mwhip_gather_destroy.restype = None
+    lib.mwhip_gather_destroy.argtypes = [C.c_void_p, C.c_uint64]
+    for fn in (lib.mwhip_gather_compute, lib.mwhip_gather_compute_async):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_uint64]
+    lib.mwhip_gather_buffer.restype = C.c_void_p
+    lib.mwhip_gather_buffer.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32,
+                                        C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    for fn in (lib.mwhip_gather_archetypes, lib.mwhip_gather_worlds):
+        fn.restype = C.c_void_p
+        fn.argtypes = [C.c_void_p, C.c_uint64]
+    lib.mwhip_set_step_gather.restype = C.c_int
+    lib.mwhip_set_step_gather.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
     return lib
 
 
@@ -279,7 +303,7 @@ class _Checked:
 
 
 class _ExecObject(_Checked):
-    """What Snapshot, StateDigest, WorldView and WorldWrite are: something a simulator's
+    """What Snapshot, StateDigest, WorldView, WorldWrite, WorldReduce and EntityGather are: something a simulator's
     executor owns, named by `handle` there, kept in one of the simulator's
     lists (`_list`) while it is open.  close() frees it and takes it off the
     list (a snapshot too, which used to stay on it until the simulator closed); Simulator.close() frees the executor and orphans
@@ -716,6 +740,19 @@ class WorldView(_ExecObject):
         self._live()
         return self._wrap(("", "counts"), self.counts_ptr, np.int32, (self.num_worlds,))
 
+    def handle_source(self, name: str, first_byte: int = 0, handles: int = 1):
+        """The slab of column `name` as a source of Simulator.entity_gather():
+        (ptr, num_records, record_bytes, first_byte, handles_per_record) with a
+        record per cell, worlds * max_rows of them, and in each `handles`
+        Entity cells from byte `first_byte` on.  The padding cells are records
+        like any other (zero handles, whatever those name)."""
+        ptr, cell = self._buffers[name]
+        self._live()
+        if first_byte < 0 or handles < 1 or first_byte + 8 * handles > cell:
+            raise ValueError(f"{name}: {handles} handles from byte {first_byte} do not fit "
+                             f"cells of {cell} bytes")
+        return (ptr, self.num_worlds * self.max_rows, cell, int(first_byte), int(handles))
+
     def every_step(self, on: bool = True) -> None:
         """Every replay of a step graph recomputes this view (waits for the
         stream and rebuilds the launch graphs); on=False turns it off again."""
@@ -1042,6 +1079,164 @@ class WorldReduce(_ExecObject):
         self._every_step = bool(on)
 
 
+class EntityGather(_ExecObject):
+    """The cells of the entities that N handles in device memory name: per
+    listed component uint8 [N, cell_bytes] (zero where a handle names nothing
+    or its table has no such column), plus int32 [N] `archetypes` and `worlds`
+    (-1 where it names nothing).  madrona_amd/gather_ref.py is the exact
+    definition; mwhip_gather_*, include/mwhip.h, computes it with one kernel
+    through the entity store, trusting no bit of a handle.  HIP backend only.
+    The source is read when the kernel runs and must stay where it is while the
+    gather exists (a tensor given as the source is kept alive by this object).
+    compute() waits for the executor's stream, compute_async() queues behind
+    the replays queued so far; tensor(name), `archetypes` and `worlds` are
+    zero-copy torch tensors over the device buffers, which every compute
+    rewrites in full; every_step() makes every replay of a step graph recompute
+    the gather directly behind its step views (so a gather over a step view's
+    slab follows the step) and before its output rings: a ring over
+    buffer_ptr(name) records [K, N, ...].  close() frees it; Simulator.close()
+    orphans what is left."""
+
+    _kind, _destroy, _list = "entity gather", "mwhip_gather_destroy", "_gathers"
+
+    def __init__(self, sim: "Simulator", source, components):
+        if not hasattr(sim.lib, "sim_hip_column_ids"):
+            raise RuntimeError("this simulator library has no sim_hip_column_ids: rebuild it")
+        components = list(components)
+        if len(set(components)) != len(components):
+            raise ValueError("entity_gather(): a component is listed twice")
+        comps = (C.c_uint32 * max(len(components), 1))()
+        for p, name in enumerate(components):
+            comps[p] = self._component_id(sim, name)
+        self._source = None
+        if isinstance(source, tuple):
+            ptr, num_records, record_bytes, first_byte, per = (int(v) for v in source)
+        else:
+            import torch
+
+            four_byte = (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ())
+            if not isinstance(source, torch.Tensor) or not source.is_cuda:
+                raise TypeError("entity_gather(): the source is a torch tensor on the device or "
+                                "a (ptr, num_records, record_bytes, first_byte, "
+                                "handles_per_record) tuple")
+            if not ((source.dtype in four_byte and source.dim() >= 1 and source.shape[-1] == 2)
+                    or (source.dtype == torch.uint8 and source.dim() >= 1
+                        and source.shape[-1] == 8)):
+                raise TypeError(f"entity_gather(): handles are int32 / uint32 [..., 2] or uint8 "
+                                f"[..., 8], not {source.dtype} {tuple(source.shape)}")
+            if not source.is_contiguous():
+                raise ValueError("entity_gather(): the source tensor must be contiguous")
+            self._source = source       # (stays where it is while the gather exists)
+            ptr, num_records = source.data_ptr(), source.numel() * source.element_size() // 8
+            record_bytes, first_byte, per = 8, 0, 1
+        self._sim = sim
+        self.components = components
+        self.num_handles = num_records * per
+        self._rt = runtime_lib()
+        self._exec = sim.hip_exec()
+        self._tensors = {}
+        self._every_step = False
+        self.handle = 0
+        src = GatherSource(ptr, num_records, record_bytes, first_byte, per, 0)
+        handle = C.c_uint64(0)
+        self._check(self._rt.mwhip_gather_create(self._exec, C.byref(src), comps,
+                                                 len(components), C.byref(handle)),
+                    "mwhip_gather_create")
+        self.handle = int(handle.value)
+        self._buffers = {}
+        for p, name in enumerate(components):
+            nbytes, cell = C.c_uint64(0), C.c_uint32(0)
+            buf = self._rt.mwhip_gather_buffer(self._exec, self.handle, p, C.byref(nbytes),
+                                               C.byref(cell))
+            assert buf and nbytes.value == self.num_handles * cell.value
+            self._buffers[name] = (int(buf), int(cell.value))
+        self.archetypes_ptr = int(self._rt.mwhip_gather_archetypes(self._exec, self.handle) or 0)
+        self.worlds_ptr = int(self._rt.mwhip_gather_worlds(self._exec, self.handle) or 0)
+
+    @staticmethod
+    def _component_id(sim: "Simulator", name: str) -> int:
+        """A component is named by the part of a dump-list column name behind
+        the dot; every table's column of that name must be the same component."""
+        ids = set()
+        for idx, column in enumerate(sim._columns):
+            if column[0].split(".", 1)[-1] != name:
+                continue
+            arch, comp = C.c_uint32(0), C.c_uint32(0)
+            if sim.lib.sim_hip_column_ids(sim.handle, idx, C.byref(arch), C.byref(comp)) != 0:
+                raise RuntimeError(f"sim_hip_column_ids({column[0]}) failed")
+            ids.add(int(comp.value))
+        if not ids:
+            raise KeyError(f"entity_gather(): no column of the dump list is named "
+                           f"'<table>.{name}'")
+        if len(ids) != 1:
+            raise KeyError(f"entity_gather(): {name!r} names different components "
+                           f"{sorted(ids)} in different tables")
+        return ids.pop()
+
+    def _orphan(self) -> None:
+        super()._orphan()
+        self._tensors = {}
+        self._source = None
+
+    def compute(self) -> "EntityGather":
+        """Rewrites every buffer, archetypes and worlds; waits for the
+        executor's stream."""
+        self._check(self._rt.mwhip_gather_compute(self._exec, self._live()),
+                    "mwhip_gather_compute")
+        return self
+
+    def compute_async(self) -> None:
+        self._check(self._rt.mwhip_gather_compute_async(self._exec, self._live()),
+                    "mwhip_gather_compute_async")
+
+    def buffer_ptr(self, name: str) -> int:
+        """Device address of component `name`'s [N, cell_bytes] bytes."""
+        self._live()
+        return self._buffers[name][0]
+
+    def cell_bytes(self, name: str) -> int:
+        return self._buffers[name][1]
+
+    _wrap = WorldView._wrap
+
+    def tensor(self, name: str, dtype=None):
+        """torch uint8 [N, cell_bytes] over the device buffer of component
+        `name` (no copy), or, with a numpy dtype, [N, cell_bytes // itemsize]
+        of that type."""
+        self._live()
+        ptr, cell = self._buffers[name]
+        dt = np.dtype(np.uint8 if dtype is None else dtype)
+        if cell % dt.itemsize != 0:
+            raise TypeError(f"{name}: cells of {cell} bytes do not hold whole {dt} items")
+        return self._wrap((name, dt.str), ptr, dt.type,
+                          (self.num_handles, cell // dt.itemsize))
+
+    @property
+    def archetypes(self):
+        """torch int32 [N] over the device buffer (no copy): the archetype of
+        the entity each handle names, -1 where it names nothing."""
+        self._live()
+        return self._wrap(("", "archetypes"), self.archetypes_ptr, np.int32,
+                          (self.num_handles,))
+
+    @property
+    def worlds(self):
+        """torch int32 [N] over the device buffer (no copy): the world of the
+        entity each handle names, -1 where it names nothing."""
+        self._live()
+        return self._wrap(("", "worlds"), self.worlds_ptr, np.int32, (self.num_handles,))
+
+    def every_step(self, on: bool = True) -> None:
+        """Every replay of a step graph recomputes this gather (waits for the
+        stream and rebuilds the launch graphs); on=False turns it off again."""
+        handle = self._live()
+        if not on and not self._every_step:
+            return
+        self._check(self._rt.mwhip_set_step_gather(self._exec, handle, 1 if on else 0),
+                    "mwhip_set_step_gather")
+        self._every_step = bool(on)
+
+
 class Simulator:
     """One simulator instance behind the C API (either backend)."""
 
@@ -1071,6 +1266,7 @@ class Simulator:
         self._views: List["WorldView"] = []
         self._writes: List["WorldWrite"] = []
         self._reduces: List["WorldReduce"] = []
+        self._gathers: List["EntityGather"] = []
         self._tensor_info: Dict[str, Tuple[int, np.dtype, Tuple[int, ...], bool]] = {}
         for i in range(self.lib.sim_num_tensors(self.handle)):
             info = SimTensorInfo()
@@ -1088,10 +1284,10 @@ class Simulator:
     def close(self) -> None:
         if self.handle:
             # sim_destroy frees the executor and with it its snapshots, digests,
-            # world views, world writes and world reduces, and forgets its output
-            # rings (the trajectories keep their tensors)
+            # world views, world writes, world reduces and entity gathers, and
+            # forgets its output rings (the trajectories keep their tensors)
             for open_ones in (self._snapshots, self._trajectories, self._digests, self._views,
-                              self._writes, self._reduces):
+                              self._writes, self._reduces, self._gathers):
                 for obj in open_ones:
                     obj._orphan()
                 open_ones.clear()
@@ -1298,6 +1494,20 @@ class Simulator:
         reduce = WorldReduce(self, table, terms)
         self._reduces.append(reduce)
         return reduce
+
+    def entity_gather(self, source, components) -> "EntityGather":
+        """An EntityGather of `components` (named by the part of a dump-list
+        column name behind the dot, e.g. "Position"; none: only archetypes and
+        worlds) through the handles of `source`: a torch tensor on the device,
+        contiguous, int32 / uint32 [..., 2] or uint8 [..., 8], or a (ptr,
+        num_records, record_bytes, first_byte, handles_per_record) tuple such
+        as WorldView.handle_source() gives.  HIP backend; raises on the
+        reference backend, which has no executor to ask."""
+        if self.backend != "hip":
+            raise RuntimeError(f"entity gathers need the HIP backend, this is {self.backend!r}")
+        gather = EntityGather(self, source, components)
+        self._gathers.append(gather)
+        return gather
 
     def record(self, names: List[str], steps: int, on_render: bool = False) -> "Trajectory":
         """Records the exported tensors `names` on the device from the next

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded() and mwhip_digest_*() / mwhip_set_step_digest() (a per-world hash of chosen columns computed on the device) and mwhip_view_*() / mwhip_set_step_view() (padded per-world tensors of a table's columns) and mwhip_write_*() / mwhip_set_step_write() (padded per-world tensors scattered into a table's columns) and mwhip_reduce_term / mwhip_reduce_*() / mwhip_set_step_reduce() (per-world sums, extrema, counts and alarms of a table's columns) and mwhip_gather_source / mwhip_gather_*() / mwhip_set_step_gather() (the cells of the entities a run of handles in device memory names) and MWHIP_NODE_CARRIED / mwhip_broadphase_carry_stats() (launches a steady replay leaves out, a bit of mwhip_node_desc::kind that earlier libraries never set); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
+#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded() and mwhip_digest_*() / mwhip_set_step_digest() (a per-world hash of chosen columns computed on the device) and mwhip_view_*() / mwhip_set_step_view() (padded per-world tensors of a table's columns) and mwhip_write_*() / mwhip_set_step_write() (padded per-world tensors scattered into a table's columns) and mwhip_reduce_term / mwhip_reduce_*() / mwhip_set_step_reduce() (per-world sums, extrema, counts and alarms of a table's columns) and mwhip_gather_source / mwhip_gather_*() / mwhip_set_step_gather() (the cells of the entities a run of handles in device memory names) and mwhip_scatter_*() / mwhip_set_step_scatter() (cells written into the entities such a run of handles names, the highest index winning among duplicates) and MWHIP_NODE_CARRIED / mwhip_broadphase_carry_stats() (launches a steady replay leaves out, a bit of mwhip_node_desc::kind that earlier libraries never set); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
 
 typedef struct mwhip_exec mwhip_exec; /* opaque; == MWCudaExecutor::Impl */
 
@@ -1080,6 +1080,96 @@ void *mwhip_gather_buffer(mwhip_exec *exec, uint64_t gather, uint32_t column,
 int32_t *mwhip_gather_archetypes(mwhip_exec *exec, uint64_t gather);
 int32_t *mwhip_gather_worlds(mwhip_exec *exec, uint64_t gather);
 int mwhip_set_step_gather(mwhip_exec *exec, uint64_t gather, int on);
+
+/* Entity scatters (added under ABI 9): the batched ctx.get<T>(e) = v, the other
+ * direction of an entity gather (madrona_amd/scatter_ref.py is
+ * the same definition in numpy).  The SOURCE of the N handles is a
+ * mwhip_gather_source, read and checked exactly as a gather's: the same
+ * alignment rules, the same definition of "handle i NAMES row r of table a"
+ * (id >= 0, a registered, 0 <= r < numRows(a), the row's Entity cell equal to
+ * the handle bit for bit, its WorldID cell not -1), and the same warning that a
+ * table column's own address is no source.  A scatter owns, all zero at creation,
+ *   in_c[i]       (uint8 [N][cell_bytes], in) per listed component c;
+ *   select[i]     (int32 [N], in);
+ *   archetype[i], world[i], written[i]   (int32 [N], out).
+ * An apply is the sequential loop for i = 0 .. N - 1: if select[i] != 0 and
+ * handle i names (a, r), then for every listed component c that table a has a
+ * column of, that column's cell of row r becomes in_c[i].  So among selected
+ * handles that name the same entity THE HIGHEST INDEX WINS, whatever the
+ * scheduling.  Every apply rewrites in full
+ *   archetype[i], world[i]   as a gather does: -1, -1 when handle i names
+ *                 nothing, whatever select says;
+ *   written[i]    1 exactly when select[i] != 0, handle i names an entity and
+ *                 no selected handle of higher index names the same entity
+ *                 (also when the table has none of the listed columns), else 0.
+ * Every other byte of every table is unchanged: unlisted columns, Entity and
+ * WorldID (which cannot be listed), the headers, the rows of handles that lost,
+ * were not selected or name nothing.  The buffers, select and the source are
+ * not modified.  No rows are created or destroyed, and state derived from the
+ * cells written is the simulator's business, as for a world write.  Handles are
+ * arbitrary bits: nothing is dereferenced behind a check that failed, and a
+ * cell is stored only behind the full check of its own handle.  Row counts,
+ * column addresses and the entity store's size are read on the device when
+ * the kernels run: a scatter made before a table or the entity store grew, or
+ * before a sort swapped a column with its twin, stays right.
+ *
+ * An apply is three launches ordered by the stream: one clears the scatter's
+ * claim table (slots = the power of two >= 2N, at most 2^31; uint32 keys[slots],
+ * entity id + 1, and uint32 best[slots], handle index + 1), one resolves every
+ * handle, stores archetype and world and claims the entity for the highest
+ * selected index (compare-and-swap, atomic max), one resolves again, stores
+ * written and copies the winners' cells.  No workgroup waits for another.
+ *
+ * mwhip_scatter_buffer: device address of in_c of listed component `column`
+ * (position in the list), 256-byte aligned, owned by the executor and valid
+ * until the scatter is destroyed; NULL for an unknown handle or a column index
+ * out of range.  mwhip_scatter_select / _archetypes / _worlds / _written: int32
+ * [N], likewise.  One allocation holds all of them and the claim table.
+ * mwhip_set_step_scatter(on != 0): every replay of every STEP graph of the
+ * executor (packed ones included; render graphs are untouched) applies the
+ * scatter directly behind the step writes and in front of the first task-graph
+ * node, so an input ring whose destination is a buffer, select or a handle
+ * tensor of the caller's feeds the apply of the replay it runs in.  Up to
+ * MWHIP_MAX_STEP_SCATTERS step scatters, THREE launches for all of them (each
+ * scatter has its own claim table in them); mwhip_profile lists them with
+ * roles "scatter.zero", "scatter.claim" and "scatter.write"; algo_bytes: the
+ * claim tables; per handle 20 bytes (handle, select, archetype, world) + per
+ * handle that named an entity 24 (its slot, its row's Entity and WorldID
+ * cells); per handle 16 (handle, select, written) + per named handle 24 + per
+ * winner twice the listed cells.  Two step scatters could name one entity in
+ * one launch: a scatter that lists a component which a set step scatter already
+ * lists is refused (distinct components are distinct columns).  The step writes
+ * run one launch earlier: on the same cell a step scatter wins over a step
+ * write.  A step scatter over a step view's slab reads the view the PREVIOUS
+ * replay left, which is the state this replay starts from.  While a step
+ * scatter is set, replays run every launch (no carried broadphase).  on == 0
+ * takes it out again; changing the set waits for the stream and rebuilds the
+ * launch graphs (handles stay valid).  Destroying a step scatter unsets it.
+ * Handles are unique in the process; mwhip_destroy frees what is left.
+ * Errors (non-zero, text in mwhip_last_error(), nothing changed or allocated):
+ * -3 for an unknown handle or one of another executor ("scatter N is not one
+ * of this executor's"; looked up first, so also with a null executor); -2 for
+ * everything mwhip_gather_create refuses about a source and a component list
+ * (n > MWHIP_SCATTER_MAX_COLUMNS), n == 0, the Entity (0) or WorldID (1)
+ * component listed, a ninth step scatter, a component clash among step
+ * scatters; -10 for buffers that cannot be allocated.
+ * (No reference counterpart.) */
+#define MWHIP_SCATTER_MAX_COLUMNS 32
+#define MWHIP_MAX_STEP_SCATTERS 8
+int mwhip_scatter_create(mwhip_exec *exec, const mwhip_gather_source *source,
+                         const uint32_t *component_ids, uint32_t n, uint64_t *scatter_out);
+void mwhip_scatter_destroy(mwhip_exec *exec, uint64_t scatter);
+/* waits for the executor's stream */
+int mwhip_scatter_apply(mwhip_exec *exec, uint64_t scatter);
+/* queued on the executor's stream behind the replays queued so far */
+int mwhip_scatter_apply_async(mwhip_exec *exec, uint64_t scatter);
+void *mwhip_scatter_buffer(mwhip_exec *exec, uint64_t scatter, uint32_t column,
+                           uint64_t *bytes_out, uint32_t *cell_bytes_out);
+int32_t *mwhip_scatter_select(mwhip_exec *exec, uint64_t scatter);
+int32_t *mwhip_scatter_archetypes(mwhip_exec *exec, uint64_t scatter);
+int32_t *mwhip_scatter_worlds(mwhip_exec *exec, uint64_t scatter);
+int32_t *mwhip_scatter_written(mwhip_exec *exec, uint64_t scatter);
+int mwhip_set_step_scatter(mwhip_exec *exec, uint64_t scatter, int on);
 
 #ifdef __cplusplus
 }

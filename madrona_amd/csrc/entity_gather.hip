@@ -34,6 +34,7 @@
 // destination is one contiguous run of 64 cells of a 256-byte aligned buffer.
 // No atomics, no LDS, no spin-waits, no workgroup waits for another.
 #include "exec_internal.hpp"
+#include "entity_resolve.hpp"
 #include "world_team.hpp"
 
 namespace {
@@ -51,15 +52,11 @@ struct GatherPlanColumn {
 
 struct GatherPlan {
     const EcsState *state;  // on the device
-    const char *src;        // the caller's: numRecords records of recordBytes
+    HandleSource source;    // numRecords records of the caller's
     int32_t *archetypes;    // [numHandles]
     int32_t *worlds;        // [numHandles]
     uint32_t numHandles;    // N = numRecords * perRecord <= 2^31 - 1
-    uint32_t recordBytes;
-    uint32_t firstByte;
-    uint32_t perRecord;
     uint32_t numColumns;
-    uint32_t pad_;
     GatherPlanColumn columns[MWHIP_GATHER_MAX_COLUMNS];
 };
 
@@ -70,59 +67,12 @@ struct GatherArgs {
     const GatherPlan *plans[MWHIP_MAX_STEP_GATHERS];
 };
 
-using madrona::mwhip::GlobalU32;
+using madrona::mwhip::HandleSource;
+using madrona::mwhip::Resolved;
 using madrona::mwhip::cellCopy;
+using madrona::mwhip::resolveHandle;
 using madrona::mwhip::teamCopy;
 using madrona::mwhip::teamZero;
-
-// Where a handle's entity is, if it names one.
-struct Resolved {
-    int32_t archetype;      // -1: names nothing
-    int32_t world;
-    int32_t row;
-};
-
-// Steps 1 and 2 of the header comment for handle i (valid: i < numHandles).
-__device__ inline Resolved resolveHandle(const GatherPlan *plan, uint32_t i, bool valid)
-{
-    Resolved out = { -1, -1, 0 };
-    if (!valid) return out;
-    const EcsState *S = plan->state;
-
-    const uint32_t per = plan->perRecord;
-    const uint32_t rec = i / per;
-    const uint32_t k = i - rec * per;
-    const GlobalU32 *h = (const GlobalU32 *)(uint64_t)(
-        plan->src + (uint64_t)rec * plan->recordBytes + plan->firstByte + (uint64_t)k * 8ull);
-    const uint32_t gen = h[0];
-    const int32_t id = (int32_t)h[1];
-
-    // (the device copy: the store may have grown since the plan was made)
-    if (id < 0 || id >= S->entityCapacity) return out;
-    const GlobalU32 *slot = (const GlobalU32 *)(uint64_t)(S->entities + id);
-    static_assert(sizeof(EntitySlot) == 12 && offsetof(EntitySlot, gen) == 8);
-    const uint32_t archetype = slot[0];
-    const int32_t row = (int32_t)slot[1];
-    // a stale handle, or a free slot (whose first two words are list links)
-    if (slot[2] != gen) return out;
-
-    // a free slot whose generation the handle happens to carry: its "archetype"
-    // and "row" are free-list links
-    if (archetype >= S->numArchetypeSlots) return out;
-    const TableHdr *hdr = S->tables + archetype;
-    if (hdr->registered == 0u) return out;
-    if (row < 0 || row >= hdr->numRows) return out;
-
-    // the row itself has the last word: it holds this entity, and it is live
-    const GlobalU32 *cell = (const GlobalU32 *)(uint64_t)hdr->columns[0] + 2ull * (uint32_t)row;
-    const int32_t world = ((const int32_t *)hdr->columns[1])[row];
-    if (cell[0] != gen || (int32_t)cell[1] != id || world == -1) return out;
-
-    out.archetype = (int32_t)archetype;
-    out.world = world;
-    out.row = row;
-    return out;
-}
 
 // one wavefront, 64 consecutive handles of one gather
 __device__ inline void gatherWave(const GatherPlan *plan, uint32_t item, uint32_t lane)
@@ -133,13 +83,14 @@ __device__ inline void gatherWave(const GatherPlan *plan, uint32_t item, uint32_
     const uint32_t i = first + lane;
     const bool valid = lane < in_wave;
 
-    const Resolved r = resolveHandle(plan, i, valid);
+    // steps 1 and 2 of the header comment (entity_resolve.hpp)
+    const EcsState *S = plan->state;
+    const Resolved r = resolveHandle(S, plan->source, i, valid);
     if (valid) {
         plan->archetypes[i] = r.archetype;
         plan->worlds[i] = r.world;
     }
 
-    const EcsState *S = plan->state;
     void *const *col_ptrs = S->colPtr;
     const uint32_t num_slots = S->numComponentSlots;
     const uint32_t num_columns = plan->numColumns;
@@ -337,60 +288,73 @@ MWHIP_RT int stepGatherStage(mwhip_exec *exec, const LaunchGraph &lg,
     return 0;
 }
 
+// What mwhip_gather_create and mwhip_scatter_create refuse about a source and
+// a component list, before anything is allocated (`what`: the entry point, in
+// front of the text).
+MWHIP_RT int checkHandleRequest(mwhip_exec *exec, const char *what,
+                                const mwhip_gather_source *source,
+                                const uint32_t *component_ids, uint32_t n, const void *out)
+{
+    if (exec == nullptr || !exec->stateBuilt || out == nullptr) {
+        return fail(-2, "%s: no executor state", what);
+    }
+    if (source == nullptr || source->src == nullptr) {
+        return fail(-2, "%s: no source (src == NULL)", what);
+    }
+    if (((uint64_t)source->src & 3ull) != 0ull || source->record_bytes % 4u != 0u ||
+            source->first_byte % 4u != 0u) {
+        return fail(-2, "%s: src %p, record_bytes %u and first_byte %u must be "
+                    "multiples of 4", what, source->src, source->record_bytes,
+                    source->first_byte);
+    }
+    if (source->handles_per_record == 0u) {
+        return fail(-2, "%s: handles_per_record == 0", what);
+    }
+    if ((uint64_t)source->first_byte + 8ull * source->handles_per_record >
+            (uint64_t)source->record_bytes) {
+        return fail(-2, "%s: %u handles from byte %u do not fit a record of %u bytes", what,
+                    source->handles_per_record, source->first_byte, source->record_bytes);
+    }
+    if (source->num_records == 0ull) {
+        return fail(-2, "%s: num_records == 0", what);
+    }
+    if (source->num_records > 0x7FFFFFFFull / source->handles_per_record) {
+        return fail(-2, "%s: %llu records x %u handles is more than %u handles", what,
+                    (unsigned long long)source->num_records, source->handles_per_record,
+                    0x7FFFFFFFu);
+    }
+    if (n > MWHIP_GATHER_MAX_COLUMNS) {
+        return fail(-2, "%s: %u components (at most %u)", what, n,
+                    (uint32_t)MWHIP_GATHER_MAX_COLUMNS);
+    }
+    if (n != 0u && component_ids == nullptr) {
+        return fail(-2, "%s: %u components and no list", what, n);
+    }
+    for (uint32_t p = 0; p < n; p++) {
+        const uint32_t component = component_ids[p];
+        if (component >= exec->components.size() || !exec->components[component].registered ||
+                component >= exec->hostState.numComponentSlots) {
+            return fail(-2, "%s: column %u: component %u is not registered", what, p,
+                        component);
+        }
+        for (uint32_t q = 0; q < p; q++) {
+            if (component_ids[q] == component) {
+                return fail(-2, "%s: component %u is listed twice (positions %u "
+                            "and %u)", what, component, q, p);
+            }
+        }
+    }
+    return 0;
+}
+
 extern "C" int mwhip_gather_create(mwhip_exec *exec, const mwhip_gather_source *source,
                                    const uint32_t *component_ids, uint32_t n,
                                    uint64_t *gather_out)
 {
     carryStale(exec);
     // (every refusal comes before anything is allocated)
-    if (exec == nullptr || !exec->stateBuilt || gather_out == nullptr) {
-        return fail(-2, "gather_create: no executor state");
-    }
-    if (source == nullptr || source->src == nullptr) {
-        return fail(-2, "gather_create: no source (src == NULL)");
-    }
-    if (((uint64_t)source->src & 3ull) != 0ull || source->record_bytes % 4u != 0u ||
-            source->first_byte % 4u != 0u) {
-        return fail(-2, "gather_create: src %p, record_bytes %u and first_byte %u must be "
-                    "multiples of 4", source->src, source->record_bytes, source->first_byte);
-    }
-    if (source->handles_per_record == 0u) {
-        return fail(-2, "gather_create: handles_per_record == 0");
-    }
-    if ((uint64_t)source->first_byte + 8ull * source->handles_per_record >
-            (uint64_t)source->record_bytes) {
-        return fail(-2, "gather_create: %u handles from byte %u do not fit a record of %u bytes",
-                    source->handles_per_record, source->first_byte, source->record_bytes);
-    }
-    if (source->num_records == 0ull) {
-        return fail(-2, "gather_create: num_records == 0");
-    }
-    if (source->num_records > 0x7FFFFFFFull / source->handles_per_record) {
-        return fail(-2, "gather_create: %llu records x %u handles is more than %u handles",
-                    (unsigned long long)source->num_records, source->handles_per_record,
-                    0x7FFFFFFFu);
-    }
-    if (n > MWHIP_GATHER_MAX_COLUMNS) {
-        return fail(-2, "gather_create: %u components (at most %u)", n,
-                    (uint32_t)MWHIP_GATHER_MAX_COLUMNS);
-    }
-    if (n != 0u && component_ids == nullptr) {
-        return fail(-2, "gather_create: %u components and no list", n);
-    }
-    for (uint32_t p = 0; p < n; p++) {
-        const uint32_t component = component_ids[p];
-        if (component >= exec->components.size() || !exec->components[component].registered ||
-                component >= exec->hostState.numComponentSlots) {
-            return fail(-2, "gather_create: column %u: component %u is not registered", p,
-                        component);
-        }
-        for (uint32_t q = 0; q < p; q++) {
-            if (component_ids[q] == component) {
-                return fail(-2, "gather_create: component %u is listed twice (positions %u "
-                            "and %u)", component, q, p);
-            }
-        }
-    }
+    int rc = checkHandleRequest(exec, "gather_create", source, component_ids, n, gather_out);
+    if (rc != 0) return rc;
 
     HIPCHK(hipSetDevice(exec->cfg.gpu_id));
     std::unique_ptr<mwhip_gather_rec> gather(new mwhip_gather_rec {});
@@ -421,13 +385,11 @@ extern "C" int mwhip_gather_create(mwhip_exec *exec, const mwhip_gather_source *
         gather->worldsDev = (int32_t *)(gather->bufDev + worlds_at);
         GatherPlan plan {};
         plan.state = exec->stateDev;
-        plan.src = (const char *)source->src;
+        plan.source = { (const char *)source->src, source->record_bytes, source->first_byte,
+                        source->handles_per_record, 0u };
         plan.archetypes = gather->archetypesDev;
         plan.worlds = gather->worldsDev;
         plan.numHandles = num_handles;
-        plan.recordBytes = source->record_bytes;
-        plan.firstByte = source->first_byte;
-        plan.perRecord = source->handles_per_record;
         plan.numColumns = n;
         for (uint32_t p = 0; p < n; p++) {
             const uint32_t cell = gather->cellBytes[p];

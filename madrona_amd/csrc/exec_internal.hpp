@@ -6,7 +6,8 @@
 // per-world state digests; world_view.hip: padded per-world views of a table's
 // columns; world_write.hip: the same tensors scattered into a table's columns;
 // world_reduce.hip: per-world reductions of a table's columns;
-// entity_gather.hip: the cells of the entities a run of handles names).
+// entity_gather.hip: the cells of the entities a run of handles names;
+// entity_scatter.hip: cells written into those entities).
 // Not installed.
 #pragma once
 #include "runtime_internal.hpp"
@@ -269,9 +270,10 @@ struct mwhip_view_rec;          // (world_view.hip)
 struct mwhip_write_rec;         // (world_write.hip)
 struct mwhip_reduce_rec;        // (world_reduce.hip)
 struct mwhip_gather_rec;        // (entity_gather.hip)
+struct mwhip_scatter_rec;       // (entity_scatter.hip)
 
 // What a replay carries besides its task graphs.  Every launch graph is built
-// from it (the input rings and the step writes open a step graph, the rest are tail stages:
+// from it (the input rings, the step writes and the step scatters open a step graph, the rest are tail stages:
 // instantiateLaunchGraph), so it changes only through changeReplayExtras.
 struct ReplayExtras {
     // mwhip_set_input_ring
@@ -308,6 +310,9 @@ struct ReplayExtras {
     // mwhip_set_step_gather: those every step replay recomputes, in one launch
     // directly behind the step views (whose slabs they may read)
     std::vector<uint64_t> stepGathers;
+    // mwhip_set_step_scatter: those every step replay applies, in three launches
+    // directly behind the step writes (no two of them list the same component)
+    std::vector<uint64_t> stepScatters;
 };
 
 struct mwhip_exec {
@@ -429,6 +434,7 @@ struct mwhip_exec {
     ExecObjectTable<mwhip_write_rec> writes;
     ExecObjectTable<mwhip_reduce_rec> reduces;     // mwhip_reduce_create
     ExecObjectTable<mwhip_gather_rec> gathers;     // mwhip_gather_create
+    ExecObjectTable<mwhip_scatter_rec> scatters;   // mwhip_scatter_create
 };
 
 // Bumped by what changes device memory or fails without naming an executor
@@ -509,6 +515,13 @@ MWHIP_RT int stepViewStage(mwhip_exec *exec, const LaunchGraph &lg,
 MWHIP_RT int stepGatherStage(mwhip_exec *exec, const LaunchGraph &lg,
                              std::vector<KernelLaunch> &out);
       // (entity_gather.hip)
+MWHIP_RT int checkHandleRequest(mwhip_exec *exec, const char *what,
+                                const mwhip_gather_source *source,
+                                const uint32_t *component_ids, uint32_t n, const void *out);
+      // (entity_gather.hip)
+MWHIP_RT int stepScatterStage(mwhip_exec *exec, const LaunchGraph &lg,
+                              std::vector<KernelLaunch> &out);
+      // (entity_scatter.hip)
 MWHIP_RT int stepReduceStage(mwhip_exec *exec, const LaunchGraph &lg,
                              std::vector<KernelLaunch> &out);
       // (world_reduce.hip)

@@ -685,6 +685,7 @@ extern "C" void mwhip_destroy(mwhip_exec *exec)
     exec->writes.clear();
     exec->reduces.clear();
     exec->gathers.clear();
+    exec->scatters.clear();
     for (void *p : exec->allocations) {
         (void)hipFree(p);
     }

@@ -379,6 +379,10 @@ static int buildLaunchList(mwhip_exec *exec, const std::vector<uint32_t> &tg_ids
         // (mwhip_set_step_write, world_write.hip)
         int rc = stepWriteStage(exec, lg, lg.launches);
         if (rc != 0) return rc;
+        // the step scatters, one launch later: on the same cell a step scatter
+        // wins over a step write (mwhip_set_step_scatter, entity_scatter.hip)
+        rc = stepScatterStage(exec, lg, lg.launches);
+        if (rc != 0) return rc;
     }
     for (uint32_t tg_id : tg_ids) {
         if (tg_id >= exec->taskGraphs.size()) {
@@ -1190,13 +1194,14 @@ MWHIP_RT int instantiateLaunchGraph(mwhip_exec *exec,
     if (rc != 0) return rc;
 
     // Carried launches (MWHIP_NODE_CARRIED): whether this
-    // graph may ever leave them out is decided here -- a step write can write
-    // what they read in every replay, and so can the owner of an exported
+    // graph may ever leave them out is decided here -- a step write or a step
+    // scatter can write what they read in every replay, and so can the owner of an exported
     // column -- and which replay does is replayGraph's business (runtime.hip).
     for (const KernelLaunch &k : lg->launches) {
         lg->hasCarried = lg->hasCarried || k.carried;
     }
-    lg->carryAllowed = lg->hasCarried && exec->extras.stepWrites.empty();
+    lg->carryAllowed = lg->hasCarried && exec->extras.stepWrites.empty() &&
+        exec->extras.stepScatters.empty();
     for (uint32_t component : exec->carriedReads) {
         lg->carryAllowed = lg->carryAllowed &&
             std::find(exec->exportedComponents.begin(), exec->exportedComponents.end(),

@@ -2,7 +2,8 @@
 // by the world views (worldViewKernel, world_view.hip), which copy a world's
 // rows out of the table, and the world writes (worldWriteKernel,
 // world_write.hip), which copy them in; the entity gathers (entityGatherKernel,
-// entity_gather.hip) copy single cells with the same teams.  A team is T lanes (a power of two,
+// entity_gather.hip) and the entity scatters (scatterWriteKernel,
+// entity_scatter.hip) copy single cells with the same teams.  A team is T lanes (a power of two,
 // 1 .. 64) of a wavefront; t is a lane's number in its team.  Device code of
 // libmadrona_hip.so; included behind exec_internal.hpp (TableHdr); not installed.
 #pragma once

@@ -177,7 +177,7 @@ friend class MWCudaExecutor;
 namespace detail {
 
 // What MWHipSnapshot, MWHipDigest, MWHipWorldView, MWHipWorldWrite,
-// MWHipWorldReduce and MWHipEntityGather share: the move-only handle
+// MWHipWorldReduce, MWHipEntityGather and MWHipEntityScatter share: the move-only handle
 // of an object that belongs to an executor (mwhip_<kind>_create / _destroy,
 // include/mwhip.h).  Kind: { name, destroy(exec, handle) }.
 template <typename Kind>
@@ -253,6 +253,10 @@ struct WorldReduceKind {
 struct EntityGatherKind {
     static constexpr const char *name = "entity gather";
     static void destroy(mwhip_exec *exec, uint64_t handle) { mwhip_gather_destroy(exec, handle); }
+};
+struct EntityScatterKind {
+    static constexpr const char *name = "entity scatter";
+    static void destroy(mwhip_exec *exec, uint64_t handle) { mwhip_scatter_destroy(exec, handle); }
 };
 
 }
@@ -565,6 +569,84 @@ public:
 private:
     MWHipEntityGather(mwhip_exec *exec, uint64_t gather, uint64_t num_handles, int32_t gpu_id)
         : ExecObject(exec, gather), num_handles_(num_handles), gpu_id_(gpu_id)
+    {}
+
+    py::Tensor perHandle(void *ptr, const char *what) const
+    {
+        req(ptr != nullptr ? 0 : -1, what);
+        const int64_t dims[1] = { (int64_t)num_handles_ };
+        return py::Tensor(ptr, py::TensorElementType::Int32, Span<const int64_t>(dims, 1),
+                          Optional<int>::make((int)gpu_id_));
+    }
+
+    uint64_t num_handles_;
+    int32_t gpu_id_;
+
+friend class MWCudaExecutor;
+};
+
+// The batched ctx.get<T>(e) = v: per listed component uint8 [N][cell bytes] on
+// the device and int32 [N] select, filled by the caller; apply() stores cell i
+// into the entity handle i of the source names, where select[i] != 0, and among
+// selected handles that name the same entity the highest index wins.  int32 [N]
+// archetype and world (-1 where a handle names nothing) and written (1 where
+// handle i's cells are the ones now in the table) are rewritten by every apply.
+// The other direction of an MWHipEntityGather, with its source and its handle
+// checks (mwhip_scatter_*, include/mwhip.h: the exact definition).  Entity and
+// WorldID cannot be listed; no rows are created or destroyed.  An extension of
+// this backend.  Belongs to the executor that made it and must not outlive it,
+// nor its source.
+class MWHipEntityScatter : public detail::ExecObject<detail::EntityScatterKind> {
+public:
+    MWHipEntityScatter() : num_handles_(0), gpu_id_(0) {}
+
+    // waits for the executor's stream
+    void apply() { req(mwhip_scatter_apply(exec_, handle_), "apply"); }
+    // queued on the executor's stream behind the replays queued so far
+    void applyAsync() { req(mwhip_scatter_apply_async(exec_, handle_), "applyAsync"); }
+
+    // uint8 [numHandles()][cell bytes] of listed component `column` (position
+    // in the list given to makeEntityScatter), owned by the executor: the input
+    py::Tensor columnTensor(uint32_t column) const
+    {
+        uint64_t bytes = 0;
+        uint32_t cell = 0;
+        void *ptr = mwhip_scatter_buffer(exec_, handle_, column, &bytes, &cell);
+        req(ptr != nullptr ? 0 : -1, "columnTensor");
+        const int64_t dims[2] = { (int64_t)num_handles_, (int64_t)cell };
+        return py::Tensor(ptr, py::TensorElementType::UInt8, Span<const int64_t>(dims, 2),
+                          Optional<int>::make((int)gpu_id_));
+    }
+
+    // int32 [numHandles()]: non-zero where handle i's cells are to be stored (input)
+    py::Tensor selectTensor() const
+    {
+        return perHandle(mwhip_scatter_select(exec_, handle_), "selectTensor");
+    }
+
+    // int32 [numHandles()]: the archetype of the entity each handle names, -1: none
+    py::Tensor archetypesTensor() const
+    {
+        return perHandle(mwhip_scatter_archetypes(exec_, handle_), "archetypesTensor");
+    }
+
+    // int32 [numHandles()]: the world that entity is in, -1: none
+    py::Tensor worldsTensor() const
+    {
+        return perHandle(mwhip_scatter_worlds(exec_, handle_), "worldsTensor");
+    }
+
+    // int32 [numHandles()]: 1 where the last apply stored handle i's cells
+    py::Tensor writtenTensor() const
+    {
+        return perHandle(mwhip_scatter_written(exec_, handle_), "writtenTensor");
+    }
+
+    uint64_t numHandles() const { return num_handles_; }
+
+private:
+    MWHipEntityScatter(mwhip_exec *exec, uint64_t scatter, uint64_t num_handles, int32_t gpu_id)
+        : ExecObject(exec, scatter), num_handles_(num_handles), gpu_id_(gpu_id)
     {}
 
     py::Tensor perHandle(void *ptr, const char *what) const
@@ -966,6 +1048,28 @@ public:
     {
         req(mwhip_set_step_gather(exec_, gather != nullptr ? gather->handle() : 0, on ? 1 : 0),
             "setStepGather");
+    }
+
+    // cells of `components` (component ids; neither Entity nor WorldID) written
+    // into the entities the handles of `source` name (see MWHipEntityScatter)
+    MWHipEntityScatter makeEntityScatter(const mwhip_gather_source &source,
+                                         Span<const uint32_t> components)
+    {
+        uint64_t scatter = 0;
+        req(mwhip_scatter_create(exec_, &source, components.data(),
+            (uint32_t)components.size(), &scatter), "makeEntityScatter");
+        return MWHipEntityScatter(exec_, scatter,
+                                  source.num_records * source.handles_per_record, gpu_id_);
+    }
+
+    // on: every replay of a step graph applies `scatter` directly behind its
+    // step writes (on the same cell the scatter wins) and in front of its first
+    // node (up to MWHIP_MAX_STEP_SCATTERS scatters that list disjoint
+    // components, three launches for all); off: no longer
+    void setStepScatter(const MWHipEntityScatter *scatter, bool on)
+    {
+        req(mwhip_set_step_scatter(exec_, scatter != nullptr ? scatter->handle() : 0,
+                                   on ? 1 : 0), "setStepScatter");
     }
 
     // Device-resident rings (extensions of this backend, include/mwhip.h).

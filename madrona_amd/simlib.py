@@ -282,6 +282,24 @@ def runtime_lib() -> C.CDLL:
         fn.argtypes = [C.c_void_p, C.c_uint64]
     lib.mwhip_set_step_gather.restype = C.c_int
     lib.mwhip_set_step_gather.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
+    lib.mwhip_scatter_create.restype = C.c_int
+    lib.mwhip_scatter_create.argtypes = [C.c_void_p, C.POINTER(GatherSource),
+                                         C.POINTER(C.c_uint32), C.c_uint32,
+                                         C.POINTER(C.c_uint64)]
+    lib.mwhip_scatter_destroy.restype = None
+    lib.mwhip_scatter_destroy.argtypes = [C.c_void_p, C.c_uint64]
+    for fn in (lib.mwhip_scatter_apply, lib.mwhip_scatter_apply_async):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_uint64]
+    lib.mwhip_scatter_buffer.restype = C.c_void_p
+    lib.mwhip_scatter_buffer.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32,
+                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    for fn in (lib.mwhip_scatter_select, lib.mwhip_scatter_archetypes,
+               lib.mwhip_scatter_worlds, lib.mwhip_scatter_written):
+        fn.restype = C.c_void_p
+        fn.argtypes = [C.c_void_p, C.c_uint64]
+    lib.mwhip_set_step_scatter.restype = C.c_int
+    lib.mwhip_set_step_scatter.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
     return lib
 
 
@@ -303,7 +321,7 @@ class _Checked:
 
 
 class _ExecObject(_Checked):
-    """What Snapshot, StateDigest, WorldView, WorldWrite, WorldReduce and EntityGather are: something a simulator's
+    """What Snapshot, StateDigest, WorldView, WorldWrite, WorldReduce, EntityGather and EntityScatter are: something a simulator's
     executor owns, named by `handle` there, kept in one of the simulator's
     lists (`_list`) while it is open.  close() frees it and takes it off the
     list (a snapshot too, which used to stay on it until the simulator closed); Simulator.close() frees the executor and orphans
@@ -1079,82 +1097,52 @@ class WorldReduce(_ExecObject):
         self._every_step = bool(on)
 
 
-class EntityGather(_ExecObject):
-    """The cells of the entities that N handles in device memory name: per
-    listed component uint8 [N, cell_bytes] (zero where a handle names nothing
-    or its table has no such column), plus int32 [N] `archetypes` and `worlds`
-    (-1 where it names nothing).  madrona_amd/gather_ref.py is the exact
-    definition; mwhip_gather_*, include/mwhip.h, computes it with one kernel
-    through the entity store, trusting no bit of a handle.  HIP backend only.
-    The source is read when the kernel runs and must stay where it is while the
-    gather exists (a tensor given as the source is kept alive by this object).
-    compute() waits for the executor's stream, compute_async() queues behind
-    the replays queued so far; tensor(name), `archetypes` and `worlds` are
-    zero-copy torch tensors over the device buffers, which every compute
-    rewrites in full; every_step() makes every replay of a step graph recompute
-    the gather directly behind its step views (so a gather over a step view's
-    slab follows the step) and before its output rings: a ring over
-    buffer_ptr(name) records [K, N, ...].  close() frees it; Simulator.close()
-    orphans what is left."""
+class _HandleCells(_ExecObject):
+    """What EntityGather and EntityScatter share: a source of N handles, a list
+    of components named as the dump list names them, per component a device
+    buffer of N cells, and int32 [N] archetypes and worlds."""
 
-    _kind, _destroy, _list = "entity gather", "mwhip_gather_destroy", "_gathers"
+    _what = "entity_gather()"   # in messages
 
-    def __init__(self, sim: "Simulator", source, components):
+    @classmethod
+    def _component_list(cls, sim: "Simulator", components):
+        """(the component ids as a C array, the names as a list)"""
         if not hasattr(sim.lib, "sim_hip_column_ids"):
             raise RuntimeError("this simulator library has no sim_hip_column_ids: rebuild it")
         components = list(components)
         if len(set(components)) != len(components):
-            raise ValueError("entity_gather(): a component is listed twice")
+            raise ValueError(f"{cls._what}: a component is listed twice")
         comps = (C.c_uint32 * max(len(components), 1))()
         for p, name in enumerate(components):
-            comps[p] = self._component_id(sim, name)
-        self._source = None
+            comps[p] = cls._component_id(sim, name)
+        return comps, components
+
+    @classmethod
+    def _handle_source(cls, source):
+        """(the tensor to keep alive or None, ptr, num_records, record_bytes,
+        first_byte, handles_per_record) of a source as entity_gather() and
+        entity_scatter() take it"""
         if isinstance(source, tuple):
-            ptr, num_records, record_bytes, first_byte, per = (int(v) for v in source)
-        else:
-            import torch
+            return (None,) + tuple(int(v) for v in source)
+        import torch
 
-            four_byte = (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ())
-            if not isinstance(source, torch.Tensor) or not source.is_cuda:
-                raise TypeError("entity_gather(): the source is a torch tensor on the device or "
-                                "a (ptr, num_records, record_bytes, first_byte, "
-                                "handles_per_record) tuple")
-            if not ((source.dtype in four_byte and source.dim() >= 1 and source.shape[-1] == 2)
-                    or (source.dtype == torch.uint8 and source.dim() >= 1
-                        and source.shape[-1] == 8)):
-                raise TypeError(f"entity_gather(): handles are int32 / uint32 [..., 2] or uint8 "
-                                f"[..., 8], not {source.dtype} {tuple(source.shape)}")
-            if not source.is_contiguous():
-                raise ValueError("entity_gather(): the source tensor must be contiguous")
-            self._source = source       # (stays where it is while the gather exists)
-            ptr, num_records = source.data_ptr(), source.numel() * source.element_size() // 8
-            record_bytes, first_byte, per = 8, 0, 1
-        self._sim = sim
-        self.components = components
-        self.num_handles = num_records * per
-        self._rt = runtime_lib()
-        self._exec = sim.hip_exec()
-        self._tensors = {}
-        self._every_step = False
-        self.handle = 0
-        src = GatherSource(ptr, num_records, record_bytes, first_byte, per, 0)
-        handle = C.c_uint64(0)
-        self._check(self._rt.mwhip_gather_create(self._exec, C.byref(src), comps,
-                                                 len(components), C.byref(handle)),
-                    "mwhip_gather_create")
-        self.handle = int(handle.value)
-        self._buffers = {}
-        for p, name in enumerate(components):
-            nbytes, cell = C.c_uint64(0), C.c_uint32(0)
-            buf = self._rt.mwhip_gather_buffer(self._exec, self.handle, p, C.byref(nbytes),
-                                               C.byref(cell))
-            assert buf and nbytes.value == self.num_handles * cell.value
-            self._buffers[name] = (int(buf), int(cell.value))
-        self.archetypes_ptr = int(self._rt.mwhip_gather_archetypes(self._exec, self.handle) or 0)
-        self.worlds_ptr = int(self._rt.mwhip_gather_worlds(self._exec, self.handle) or 0)
+        four_byte = (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ())
+        if not isinstance(source, torch.Tensor) or not source.is_cuda:
+            raise TypeError(f"{cls._what}: the source is a torch tensor on the device or "
+                            "a (ptr, num_records, record_bytes, first_byte, "
+                            "handles_per_record) tuple")
+        if not ((source.dtype in four_byte and source.dim() >= 1 and source.shape[-1] == 2)
+                or (source.dtype == torch.uint8 and source.dim() >= 1
+                    and source.shape[-1] == 8)):
+            raise TypeError(f"{cls._what}: handles are int32 / uint32 [..., 2] or uint8 "
+                            f"[..., 8], not {source.dtype} {tuple(source.shape)}")
+        if not source.is_contiguous():
+            raise ValueError(f"{cls._what}: the source tensor must be contiguous")
+        return (source, source.data_ptr(), source.numel() * source.element_size() // 8,
+                8, 0, 1)
 
-    @staticmethod
-    def _component_id(sim: "Simulator", name: str) -> int:
+    @classmethod
+    def _component_id(cls, sim: "Simulator", name: str) -> int:
         """A component is named by the part of a dump-list column name behind
         the dot; every table's column of that name must be the same component."""
         ids = set()
@@ -1166,10 +1154,10 @@ class EntityGather(_ExecObject):
                 raise RuntimeError(f"sim_hip_column_ids({column[0]}) failed")
             ids.add(int(comp.value))
         if not ids:
-            raise KeyError(f"entity_gather(): no column of the dump list is named "
+            raise KeyError(f"{cls._what}: no column of the dump list is named "
                            f"'<table>.{name}'")
         if len(ids) != 1:
-            raise KeyError(f"entity_gather(): {name!r} names different components "
+            raise KeyError(f"{cls._what}: {name!r} names different components "
                            f"{sorted(ids)} in different tables")
         return ids.pop()
 
@@ -1177,17 +1165,6 @@ class EntityGather(_ExecObject):
         super()._orphan()
         self._tensors = {}
         self._source = None
-
-    def compute(self) -> "EntityGather":
-        """Rewrites every buffer, archetypes and worlds; waits for the
-        executor's stream."""
-        self._check(self._rt.mwhip_gather_compute(self._exec, self._live()),
-                    "mwhip_gather_compute")
-        return self
-
-    def compute_async(self) -> None:
-        self._check(self._rt.mwhip_gather_compute_async(self._exec, self._live()),
-                    "mwhip_gather_compute_async")
 
     def buffer_ptr(self, name: str) -> int:
         """Device address of component `name`'s [N, cell_bytes] bytes."""
@@ -1226,6 +1203,67 @@ class EntityGather(_ExecObject):
         self._live()
         return self._wrap(("", "worlds"), self.worlds_ptr, np.int32, (self.num_handles,))
 
+
+class EntityGather(_HandleCells):
+    """The cells of the entities that N handles in device memory name: per
+    listed component uint8 [N, cell_bytes] (zero where a handle names nothing
+    or its table has no such column), plus int32 [N] `archetypes` and `worlds`
+    (-1 where it names nothing).  madrona_amd/gather_ref.py is the exact
+    definition; mwhip_gather_*, include/mwhip.h, computes it with one kernel
+    through the entity store, trusting no bit of a handle.  HIP backend only.
+    The source is read when the kernel runs and must stay where it is while the
+    gather exists (a tensor given as the source is kept alive by this object).
+    compute() waits for the executor's stream, compute_async() queues behind
+    the replays queued so far; tensor(name), `archetypes` and `worlds` are
+    zero-copy torch tensors over the device buffers, which every compute
+    rewrites in full; every_step() makes every replay of a step graph recompute
+    the gather directly behind its step views (so a gather over a step view's
+    slab follows the step) and before its output rings: a ring over
+    buffer_ptr(name) records [K, N, ...].  close() frees it; Simulator.close()
+    orphans what is left."""
+
+    _kind, _destroy, _list = "entity gather", "mwhip_gather_destroy", "_gathers"
+
+    def __init__(self, sim: "Simulator", source, components):
+        comps, components = self._component_list(sim, components)
+        # (a tensor stays where it is while the gather exists)
+        self._source, ptr, num_records, record_bytes, first_byte, per = \
+            self._handle_source(source)
+        self._sim = sim
+        self.components = components
+        self.num_handles = num_records * per
+        self._rt = runtime_lib()
+        self._exec = sim.hip_exec()
+        self._tensors = {}
+        self._every_step = False
+        self.handle = 0
+        src = GatherSource(ptr, num_records, record_bytes, first_byte, per, 0)
+        handle = C.c_uint64(0)
+        self._check(self._rt.mwhip_gather_create(self._exec, C.byref(src), comps,
+                                                 len(components), C.byref(handle)),
+                    "mwhip_gather_create")
+        self.handle = int(handle.value)
+        self._buffers = {}
+        for p, name in enumerate(components):
+            nbytes, cell = C.c_uint64(0), C.c_uint32(0)
+            buf = self._rt.mwhip_gather_buffer(self._exec, self.handle, p, C.byref(nbytes),
+                                               C.byref(cell))
+            assert buf and nbytes.value == self.num_handles * cell.value
+            self._buffers[name] = (int(buf), int(cell.value))
+        self.archetypes_ptr = int(self._rt.mwhip_gather_archetypes(self._exec, self.handle) or 0)
+        self.worlds_ptr = int(self._rt.mwhip_gather_worlds(self._exec, self.handle) or 0)
+
+    def compute(self) -> "EntityGather":
+        """Rewrites every buffer, archetypes and worlds; waits for the
+        executor's stream."""
+        self._check(self._rt.mwhip_gather_compute(self._exec, self._live()),
+                    "mwhip_gather_compute")
+        return self
+
+    def compute_async(self) -> None:
+        self._check(self._rt.mwhip_gather_compute_async(self._exec, self._live()),
+                    "mwhip_gather_compute_async")
+
     def every_step(self, on: bool = True) -> None:
         """Every replay of a step graph recomputes this gather (waits for the
         stream and rebuilds the launch graphs); on=False turns it off again."""
@@ -1234,6 +1272,98 @@ class EntityGather(_ExecObject):
             return
         self._check(self._rt.mwhip_set_step_gather(self._exec, handle, 1 if on else 0),
                     "mwhip_set_step_gather")
+        self._every_step = bool(on)
+
+
+class EntityScatter(_HandleCells):
+    """The batched ctx.get<T>(e) = v: per listed component a device buffer of N
+    cells (tensor(name), uint8 [N, cell_bytes]) and int32 [N] `select`, filled
+    by the caller; apply() stores cell i into the entity that handle i of the
+    source names, for every i with select[i] != 0, and among selected handles
+    that name the same entity the highest index wins, as `column[rows] = values`
+    assigned one at a time would.  int32 [N] `archetypes`, `worlds` (-1 where a
+    handle names nothing) and `written` (1 where handle i's cells are the ones
+    now in the table) are rewritten by every apply.  madrona_amd/scatter_ref.py
+    is the exact definition; mwhip_scatter_*, include/mwhip.h, computes it with
+    three launches through the entity store, trusting no bit of a handle.  The
+    other direction of an EntityGather, with the same sources (a tensor given as
+    the source is kept alive by this object).  Entity and WorldID cannot be
+    listed; no rows are made or destroyed; what the simulator derives from the
+    cells written is its own business.  HIP backend only.  apply() waits for the
+    executor's stream, apply_async() queues behind the replays queued so far;
+    every_step() makes every replay of a step graph apply the scatter directly
+    behind its step writes and in front of its first node, so an input ring
+    into buffer_ptr(name), select_ptr or the caller's handle tensor feeds the
+    apply of the replay it runs in.  Step scatters list disjoint components.
+    close() frees it; Simulator.close() orphans what is left."""
+
+    _kind, _destroy, _list = "entity scatter", "mwhip_scatter_destroy", "_scatters"
+    _what = "entity_scatter()"
+
+    def __init__(self, sim: "Simulator", source, components):
+        comps, components = self._component_list(sim, components)
+        self._source, ptr, num_records, record_bytes, first_byte, per = \
+            self._handle_source(source)
+        self._sim = sim
+        self.components = components
+        self.num_handles = num_records * per
+        self._rt = runtime_lib()
+        self._exec = sim.hip_exec()
+        self._tensors = {}
+        self._every_step = False
+        self.handle = 0
+        src = GatherSource(ptr, num_records, record_bytes, first_byte, per, 0)
+        handle = C.c_uint64(0)
+        self._check(self._rt.mwhip_scatter_create(self._exec, C.byref(src), comps,
+                                                  len(components), C.byref(handle)),
+                    "mwhip_scatter_create")
+        self.handle = int(handle.value)
+        self._buffers = {}
+        for p, name in enumerate(components):
+            nbytes, cell = C.c_uint64(0), C.c_uint32(0)
+            buf = self._rt.mwhip_scatter_buffer(self._exec, self.handle, p, C.byref(nbytes),
+                                                C.byref(cell))
+            assert buf and nbytes.value == self.num_handles * cell.value
+            self._buffers[name] = (int(buf), int(cell.value))
+        self.select_ptr = int(self._rt.mwhip_scatter_select(self._exec, self.handle) or 0)
+        self.archetypes_ptr = int(self._rt.mwhip_scatter_archetypes(self._exec, self.handle) or 0)
+        self.worlds_ptr = int(self._rt.mwhip_scatter_worlds(self._exec, self.handle) or 0)
+        self.written_ptr = int(self._rt.mwhip_scatter_written(self._exec, self.handle) or 0)
+
+    def apply(self) -> "EntityScatter":
+        """Stores the selected cells and rewrites archetypes, worlds and
+        written; waits for the executor's stream."""
+        self._check(self._rt.mwhip_scatter_apply(self._exec, self._live()),
+                    "mwhip_scatter_apply")
+        return self
+
+    def apply_async(self) -> None:
+        self._check(self._rt.mwhip_scatter_apply_async(self._exec, self._live()),
+                    "mwhip_scatter_apply_async")
+
+    @property
+    def select(self):
+        """torch int32 [N] over the device buffer (no copy), the caller's to
+        fill: handle i's cells are stored where it is non-zero."""
+        self._live()
+        return self._wrap(("", "select"), self.select_ptr, np.int32, (self.num_handles,))
+
+    @property
+    def written(self):
+        """torch int32 [N] over the device buffer (no copy): 1 where the last
+        apply stored handle i's cells (selected, names an entity, and no
+        selected handle of higher index names the same one)."""
+        self._live()
+        return self._wrap(("", "written"), self.written_ptr, np.int32, (self.num_handles,))
+
+    def every_step(self, on: bool = True) -> None:
+        """Every replay of a step graph applies this scatter (waits for the
+        stream and rebuilds the launch graphs); on=False turns it off again."""
+        handle = self._live()
+        if not on and not self._every_step:
+            return
+        self._check(self._rt.mwhip_set_step_scatter(self._exec, handle, 1 if on else 0),
+                    "mwhip_set_step_scatter")
         self._every_step = bool(on)
 
 
@@ -1267,6 +1397,7 @@ class Simulator:
         self._writes: List["WorldWrite"] = []
         self._reduces: List["WorldReduce"] = []
         self._gathers: List["EntityGather"] = []
+        self._scatters: List["EntityScatter"] = []
         self._tensor_info: Dict[str, Tuple[int, np.dtype, Tuple[int, ...], bool]] = {}
         for i in range(self.lib.sim_num_tensors(self.handle)):
             info = SimTensorInfo()
@@ -1284,10 +1415,11 @@ class Simulator:
     def close(self) -> None:
         if self.handle:
             # sim_destroy frees the executor and with it its snapshots, digests,
-            # world views, world writes, world reduces and entity gathers, and
+            # world views, world writes, world reduces, entity gathers and
+            # entity scatters, and
             # forgets its output rings (the trajectories keep their tensors)
             for open_ones in (self._snapshots, self._trajectories, self._digests, self._views,
-                              self._writes, self._reduces, self._gathers):
+                              self._writes, self._reduces, self._gathers, self._scatters):
                 for obj in open_ones:
                     obj._orphan()
                 open_ones.clear()
@@ -1508,6 +1640,18 @@ class Simulator:
         gather = EntityGather(self, source, components)
         self._gathers.append(gather)
         return gather
+
+    def entity_scatter(self, source, components) -> "EntityScatter":
+        """An EntityScatter of `components` (named as entity_gather() names
+        them; at least one, neither Entity nor WorldID) through the handles of
+        `source`, which takes every form entity_gather() takes,
+        WorldView.handle_source() included.  HIP backend; raises on the
+        reference backend, which has no executor to ask."""
+        if self.backend != "hip":
+            raise RuntimeError(f"entity scatters need the HIP backend, this is {self.backend!r}")
+        scatter = EntityScatter(self, source, components)
+        self._scatters.append(scatter)
+        return scatter
 
     def record(self, names: List[str], steps: int, on_render: bool = False) -> "Trajectory":
         """Records the exported tensors `names` on the device from the next

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded() and mwhip_digest_*() / mwhip_set_step_digest() (a per-world hash of chosen columns computed on the device) and mwhip_view_*() / mwhip_set_step_view() (padded per-world tensors of a table's columns) and mwhip_write_*() / mwhip_set_step_write() (padded per-world tensors scattered into a table's columns) and mwhip_reduce_term / mwhip_reduce_*() / mwhip_set_step_reduce() (per-world sums, extrema, counts and alarms of a table's columns) and mwhip_gather_source / mwhip_gather_*() / mwhip_set_step_gather() (the cells of the entities a run of handles in device memory names) and mwhip_scatter_*() / mwhip_set_step_scatter() (cells written into the entities such a run of handles names, the highest index winning among duplicates) and MWHIP_NODE_CARRIED / mwhip_broadphase_carry_stats() (launches a steady replay leaves out, a bit of mwhip_node_desc::kind that earlier libraries never set); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
+#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded() and mwhip_digest_*() / mwhip_set_step_digest() (a per-world hash of chosen columns computed on the device) and mwhip_view_*() / mwhip_set_step_view() (padded per-world tensors of a table's columns) and mwhip_write_*() / mwhip_set_step_write() (padded per-world tensors scattered into a table's columns) and mwhip_reduce_term / mwhip_reduce_*() / mwhip_set_step_reduce() (per-world sums, extrema, counts and alarms of a table's columns) and mwhip_gather_source / mwhip_gather_*() / mwhip_set_step_gather() (the cells of the entities a run of handles in device memory names) and mwhip_scatter_*() / mwhip_set_step_scatter() (cells written into the entities such a run of handles names, the highest index winning among duplicates) and mwhip_rays_desc / mwhip_ray_args / mwhip_set_ray_kernel() / mwhip_rays_*() / mwhip_set_step_rays() (tensors of rays cast through the worlds' broadphase BVHs by a kernel the simulator's code object registers) and MWHIP_NODE_CARRIED / mwhip_broadphase_carry_stats() (launches a steady replay leaves out, a bit of mwhip_node_desc::kind that earlier libraries never set); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
 
 typedef struct mwhip_exec mwhip_exec; /* opaque; == MWCudaExecutor::Impl */
 
@@ -1170,6 +1170,152 @@ int32_t *mwhip_scatter_archetypes(mwhip_exec *exec, uint64_t scatter);
 int32_t *mwhip_scatter_worlds(mwhip_exec *exec, uint64_t scatter);
 int32_t *mwhip_scatter_written(mwhip_exec *exec, uint64_t scatter);
 int mwhip_set_step_scatter(mwhip_exec *exec, uint64_t scatter, int on);
+
+/* Ray queries (added under ABI 9): N = F x R rays -- F fans of R >= 1 rays that
+ * share an origin and a world -- cast through the worlds' broadphase BVHs
+ * (broadphase::BVH::traceRay / traceRayShared, <madrona/broadphase.hpp>) by one
+ * kernel, the batched form of what a lidar system does (DESIGN.md §33;
+ * madrona_amd/ray_ref.py is the same definition in numpy).  Ray i = f * R + r
+ * is ray r of fan f.
+ * INPUTS.  world, count and origin are each either a buffer the query owns or
+ * a SOURCE of the caller's, mwhip_ray_source: record k is read at
+ * src + k * record_bytes + first_byte; src, record_bytes and first_byte are
+ * multiples of 4; the source is read on the device when the kernel runs and
+ * must stay valid and in place while the query exists (an exported tensor, a
+ * world view's slab or counts, any device allocation; NOT a table column's own
+ * address, which the sort swaps with its twin -- as for a gather).  Owned
+ * buffers are 256-byte aligned and zero at creation (t_max: +inf); the caller
+ * and input rings write them.
+ *   world[f]    int32 per fan.  fans_per_world > 0 replaces it by the rule
+ *               world = f / fans_per_world (the shape of a world view's slab):
+ *               desc.world is then ignored and no world buffer is owned.
+ *   count[w]    optional int32 per WORLD (desc.count.src != NULL; e.g. a
+ *               view's counts), only with fans_per_world > 0: fan f with
+ *               f % fans_per_world >= count[world] is SKIPPED.
+ *   origin[f]   3 floats per fan (possibly inside a wider record).
+ *   dir[i]      3 floats per ray, always owned, used as given: hit_t is in
+ *               units of its length, as in traceRay.
+ *   t_max[i]    float per ray, always owned.
+ * OUTPUTS, owned, every one rewritten in full by every compute, valid until
+ * the query is destroyed:
+ *   status[i]   int32: MWHIP_RAYS_HIT 1, MWHIP_RAYS_MISS 0, MWHIP_RAYS_SKIPPED
+ *               -1, MWHIP_RAYS_BAD_WORLD -2 (world not in [0, numWorlds)),
+ *               MWHIP_RAYS_BAD_RAY -3 (a non-finite component of origin or
+ *               direction, an all-zero direction, a NaN t_max).  Checked in that
+ *               order: world, count, origin (per fan), then direction and t_max
+ *               (per ray).  Nothing behind a failed check is read: no count of a
+ *               bad world, no origin of a skipped fan, no tree for a negative
+ *               status.
+ *   hit_t[i]    float, 0 on anything but a HIT;
+ *   hit[i]      8 bytes, Entity { uint32 gen; int32 id }, Entity::none()
+ *               (0xFFFFFFFF, -1) on anything but a HIT: the buffer is a valid
+ *               mwhip_gather_source with record_bytes 8;
+ *   normal[i]   3 floats, zero on anything but a HIT.
+ * A ray sees the tree as the LAST BROADPHASE PASS left it (the precondition of
+ * BVH::traceRay: leaf boxes are refreshed by PhysicsSystem::setupBroadphaseTasks,
+ * not by writes to Position); spheres are transparent, as in traceRayIntoLeaf.
+ * A world whose tree NO broadphase pass has built yet -- before the first step,
+ * or restored from a snapshot taken then -- holds nothing a ray could meet:
+ * its rays are MISS and the tree's memory is not touched.  (While a rebuild of
+ * a built tree is pending, a ray walks the old tree, as BVH::traceRay does.)
+ *
+ * THE KERNEL lives in the simulator's code object (the physics headers,
+ * phys_impl/ray_query.inl), because traceRayShared and its LDS scratch do:
+ * PhysicsSystem::setupBroadphaseTasks hands its host stub over with
+ * mwhip_set_ray_kernel (NULL is ignored).  Its single argument is a
+ * mwhip_ray_args by value, whose plans (mwhip_ray_plan, device-resident) the
+ * runtime fills: both code objects compile these two structs from this header.
+ * A work item is a wavefront = two groups of 32 lanes.  rays_per_fan >= 8
+ * (groups_per_fan = ceil(R / 32) > 0): a group holds up to 32 rays of ONE fan
+ * and goes through traceRayShared; smaller R (groups_per_fan == 0): rays are
+ * packed one per lane through plain traceRay.  Same bits either way.  A simulator
+ * that registered none (no broadphase) has no ray queries.
+ *
+ * mwhip_rays_buffer: device address and size of owned buffer `which`
+ * (MWHIP_RAYS_BUF_*); NULL (-2) for world / origin when a source was given (or
+ * fans_per_world > 0), NULL (-3) for an unknown handle.
+ * mwhip_set_step_rays(on != 0): every replay of every STEP graph recomputes the
+ * query behind the step views (origins and counts may be a step view's of the
+ * same replay) and in front of the step gathers (a step gather over `hit` sees
+ * this replay's hits), the step reduces, the pack node and the output rings (a
+ * ring over an output records [K][N]...).  Up to MWHIP_MAX_STEP_RAYS, ONE launch
+ * for all, listed by mwhip_profile as "rays" with role "rays"; none when none
+ * is set.  Changing the set waits for the stream and rebuilds the launch graphs;
+ * destroying a step query unsets it.  Ray queries are derived state: snapshots
+ * do not save them.
+ * Errors (non-zero, text in mwhip_last_error(), nothing changed or allocated):
+ * -3 for an unknown handle or one of another executor ("ray query N is not one
+ * of this executor's"; looked up first, so also with a null executor); -2 for
+ * no registered kernel ("this simulator registered no ray kernel"), num_fans ==
+ * 0, rays_per_fan == 0, F x R > 2^31 - 1, a source whose src / record_bytes /
+ * first_byte is not a multiple of 4 or whose record is too short for its item,
+ * a count source without fans_per_world, a fifth step query; -10 for buffers
+ * that cannot be allocated.
+ * (No reference counterpart.) */
+#define MWHIP_MAX_STEP_RAYS 4
+#define MWHIP_RAYS_HIT 1
+#define MWHIP_RAYS_MISS 0
+#define MWHIP_RAYS_SKIPPED (-1)
+#define MWHIP_RAYS_BAD_WORLD (-2)
+#define MWHIP_RAYS_BAD_RAY (-3)
+#define MWHIP_RAYS_BUF_WORLD 0u
+#define MWHIP_RAYS_BUF_ORIGIN 1u
+#define MWHIP_RAYS_BUF_DIR 2u
+#define MWHIP_RAYS_BUF_T_MAX 3u
+#define MWHIP_RAYS_BUF_HIT_T 4u
+#define MWHIP_RAYS_BUF_HIT 5u
+#define MWHIP_RAYS_BUF_NORMAL 6u
+#define MWHIP_RAYS_BUF_STATUS 7u
+#define MWHIP_RAYS_NUM_BUFS 8u
+typedef struct mwhip_ray_source {
+    const void *src;                /* device address of record 0; NULL: none */
+    uint32_t record_bytes;
+    uint32_t first_byte;            /* of the item inside a record */
+} mwhip_ray_source;
+typedef struct mwhip_rays_desc {
+    uint32_t num_fans;              /* F */
+    uint32_t rays_per_fan;          /* R >= 1 */
+    uint32_t fans_per_world;        /* > 0: world[f] = f / fans_per_world */
+    uint32_t pad_;
+    mwhip_ray_source world;         /* src == NULL: an owned buffer */
+    mwhip_ray_source count;         /* src == NULL: no counts */
+    mwhip_ray_source origin;        /* src == NULL: an owned buffer */
+} mwhip_rays_desc;
+/* what the kernel reads of one query (device-resident, filled by the runtime;
+ * first_byte is already added to the three sources) */
+typedef struct mwhip_ray_plan {
+    void *state;                    /* the executor's ecs state on the device */
+    const char *world_src;          /* unused when fans_per_world > 0 */
+    const char *count_src;          /* NULL: none */
+    const char *origin_src;
+    const float *dir;               /* [N][3] */
+    const float *t_max;             /* [N] */
+    float *hit_t;                   /* [N] */
+    uint32_t *hit;                  /* [N][2] */
+    float *normal;                  /* [N][3] */
+    int32_t *status;                /* [N] */
+    uint32_t world_stride, count_stride, origin_stride;     /* bytes */
+    uint32_t num_fans, rays_per_fan, fans_per_world;
+    uint32_t groups_per_fan;        /* 0: packed, a ray per lane */
+    uint32_t pad_;
+} mwhip_ray_plan;
+/* the kernel's argument, by value: items[p] wavefronts work on plans[p] */
+typedef struct mwhip_ray_args {
+    uint32_t num_plans;
+    uint32_t pad_;
+    uint32_t items[MWHIP_MAX_STEP_RAYS];
+    const mwhip_ray_plan *plans[MWHIP_MAX_STEP_RAYS];
+} mwhip_ray_args;
+/* the simulator's ray kernel: __global__ void(mwhip_ray_args), 256 threads */
+int mwhip_set_ray_kernel(mwhip_exec *exec, const void *kernel);
+int mwhip_rays_create(mwhip_exec *exec, const mwhip_rays_desc *desc, uint64_t *rays_out);
+void mwhip_rays_destroy(mwhip_exec *exec, uint64_t rays);
+/* waits for the executor's stream */
+int mwhip_rays_compute(mwhip_exec *exec, uint64_t rays);
+/* queued on the executor's stream behind the replays queued so far */
+int mwhip_rays_compute_async(mwhip_exec *exec, uint64_t rays);
+void *mwhip_rays_buffer(mwhip_exec *exec, uint64_t rays, uint32_t which, uint64_t *bytes_out);
+int mwhip_set_step_rays(mwhip_exec *exec, uint64_t rays, int on);
 
 #ifdef __cplusplus
 }

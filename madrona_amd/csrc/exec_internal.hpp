@@ -7,7 +7,8 @@
 // columns; world_write.hip: the same tensors scattered into a table's columns;
 // world_reduce.hip: per-world reductions of a table's columns;
 // entity_gather.hip: the cells of the entities a run of handles names;
-// entity_scatter.hip: cells written into those entities).
+// entity_scatter.hip: cells written into those entities; ray_query.hip: rays
+// cast through the worlds' broadphase BVHs by the simulator's kernel).
 // Not installed.
 #pragma once
 #include "runtime_internal.hpp"
@@ -271,6 +272,7 @@ struct mwhip_write_rec;         // (world_write.hip)
 struct mwhip_reduce_rec;        // (world_reduce.hip)
 struct mwhip_gather_rec;        // (entity_gather.hip)
 struct mwhip_scatter_rec;       // (entity_scatter.hip)
+struct mwhip_rays_rec;          // (ray_query.hip)
 
 // What a replay carries besides its task graphs.  Every launch graph is built
 // from it (the input rings, the step writes and the step scatters open a step graph, the rest are tail stages:
@@ -313,6 +315,9 @@ struct ReplayExtras {
     // mwhip_set_step_scatter: those every step replay applies, in three launches
     // directly behind the step writes (no two of them list the same component)
     std::vector<uint64_t> stepScatters;
+    // mwhip_set_step_rays: those every step replay recomputes, in one launch
+    // behind the step views and in front of the step gathers
+    std::vector<uint64_t> stepRays;
 };
 
 struct mwhip_exec {
@@ -406,6 +411,9 @@ struct mwhip_exec {
     std::unordered_map<const void *, const void *> carriedChecks;
     std::vector<uint32_t> exportedComponents;
     const void *pforGroupKernel = nullptr;  // mwhip_set_pfor_group_kernel
+    // mwhip_set_ray_kernel: the simulator's rayQueryKernel (null: it has no
+    // broadphase, hence no ray queries)
+    const void *rayKernel = nullptr;
     void *pforBodyScratch = nullptr;        // 8 bytes: where report mode writes
     // MADRONA_MWHIP_EXEC_CONFIG_FILE (the reference's
     // MADRONA_MWGPU_EXEC_CONFIG_FILE, cuda_exec.cpp:2115-2172): per task-graph
@@ -435,6 +443,7 @@ struct mwhip_exec {
     ExecObjectTable<mwhip_reduce_rec> reduces;     // mwhip_reduce_create
     ExecObjectTable<mwhip_gather_rec> gathers;     // mwhip_gather_create
     ExecObjectTable<mwhip_scatter_rec> scatters;   // mwhip_scatter_create
+    ExecObjectTable<mwhip_rays_rec> rays;          // mwhip_rays_create
 };
 
 // Bumped by what changes device memory or fails without naming an executor
@@ -519,6 +528,9 @@ MWHIP_RT int checkHandleRequest(mwhip_exec *exec, const char *what,
                                 const mwhip_gather_source *source,
                                 const uint32_t *component_ids, uint32_t n, const void *out);
       // (entity_gather.hip)
+MWHIP_RT int stepRaysStage(mwhip_exec *exec, const LaunchGraph &lg,
+                           std::vector<KernelLaunch> &out);
+      // (ray_query.hip)
 MWHIP_RT int stepScatterStage(mwhip_exec *exec, const LaunchGraph &lg,
                               std::vector<KernelLaunch> &out);
       // (entity_scatter.hip)

@@ -686,6 +686,7 @@ extern "C" void mwhip_destroy(mwhip_exec *exec)
     exec->reduces.clear();
     exec->gathers.clear();
     exec->scatters.clear();
+    exec->rays.clear();
     for (void *p : exec->allocations) {
         (void)hipFree(p);
     }

@@ -177,7 +177,7 @@ friend class MWCudaExecutor;
 namespace detail {
 
 // What MWHipSnapshot, MWHipDigest, MWHipWorldView, MWHipWorldWrite,
-// MWHipWorldReduce, MWHipEntityGather and MWHipEntityScatter share: the move-only handle
+// MWHipWorldReduce, MWHipEntityGather, MWHipEntityScatter and MWHipRayQuery share: the move-only handle
 // of an object that belongs to an executor (mwhip_<kind>_create / _destroy,
 // include/mwhip.h).  Kind: { name, destroy(exec, handle) }.
 template <typename Kind>
@@ -257,6 +257,10 @@ struct EntityGatherKind {
 struct EntityScatterKind {
     static constexpr const char *name = "entity scatter";
     static void destroy(mwhip_exec *exec, uint64_t handle) { mwhip_scatter_destroy(exec, handle); }
+};
+struct RayQueryKind {
+    static constexpr const char *name = "ray query";
+    static void destroy(mwhip_exec *exec, uint64_t handle) { mwhip_rays_destroy(exec, handle); }
 };
 
 }
@@ -580,6 +584,106 @@ private:
     }
 
     uint64_t num_handles_;
+    int32_t gpu_id_;
+
+friend class MWCudaExecutor;
+};
+
+// N = F x R rays, F fans of R rays that share an origin and a world, cast
+// through the worlds' broadphase BVHs (BVH::traceRay / traceRayShared) by one
+// kernel of the simulator's code object: per ray int32 status (MWHIP_RAYS_HIT,
+// _MISS, _SKIPPED, _BAD_WORLD, _BAD_RAY), float hit_t, an Entity and a normal,
+// with the conventions of a lidar system's outputs (0, Entity::none(), zero on
+// anything but a hit).  mwhip_rays_*, include/mwhip.h, is the exact definition:
+// which inputs are owned buffers and which the caller's sources, and that a ray
+// sees the tree as the last broadphase pass left it, spheres being transparent.
+// Needs a simulator that sets up a broadphase.  An extension of this backend.
+// Belongs to the executor that made it and must not outlive it, nor its sources.
+class MWHipRayQuery : public detail::ExecObject<detail::RayQueryKind> {
+public:
+    MWHipRayQuery() : num_fans_(0), num_rays_(0), gpu_id_(0) {}
+
+    // waits for the executor's stream
+    void compute() { req(mwhip_rays_compute(exec_, handle_), "compute"); }
+    // queued on the executor's stream behind the replays queued so far
+    void computeAsync() { req(mwhip_rays_compute_async(exec_, handle_), "computeAsync"); }
+
+    // inputs the query owns: int32 [numFans()] (no world source, no
+    // fans_per_world), float [numFans()][3] (no origin source), float
+    // [numRays()][3], float [numRays()]
+    py::Tensor worldsTensor() const
+    {
+        return tensor(MWHIP_RAYS_BUF_WORLD, py::TensorElementType::Int32, num_fans_, 0,
+                      "worldsTensor");
+    }
+    py::Tensor originsTensor() const
+    {
+        return tensor(MWHIP_RAYS_BUF_ORIGIN, py::TensorElementType::Float32, num_fans_, 3,
+                      "originsTensor");
+    }
+    py::Tensor directionsTensor() const
+    {
+        return tensor(MWHIP_RAYS_BUF_DIR, py::TensorElementType::Float32, num_rays_, 3,
+                      "directionsTensor");
+    }
+    py::Tensor tMaxTensor() const
+    {
+        return tensor(MWHIP_RAYS_BUF_T_MAX, py::TensorElementType::Float32, num_rays_, 0,
+                      "tMaxTensor");
+    }
+
+    // outputs: float [numRays()], int32 [numRays()][2] (gen, id), float
+    // [numRays()][3], int32 [numRays()]
+    py::Tensor hitTTensor() const
+    {
+        return tensor(MWHIP_RAYS_BUF_HIT_T, py::TensorElementType::Float32, num_rays_, 0,
+                      "hitTTensor");
+    }
+    py::Tensor hitsTensor() const
+    {
+        return tensor(MWHIP_RAYS_BUF_HIT, py::TensorElementType::Int32, num_rays_, 2,
+                      "hitsTensor");
+    }
+    py::Tensor normalsTensor() const
+    {
+        return tensor(MWHIP_RAYS_BUF_NORMAL, py::TensorElementType::Float32, num_rays_, 3,
+                      "normalsTensor");
+    }
+    py::Tensor statusTensor() const
+    {
+        return tensor(MWHIP_RAYS_BUF_STATUS, py::TensorElementType::Int32, num_rays_, 0,
+                      "statusTensor");
+    }
+
+    // the hits as the source of an entity gather or scatter
+    mwhip_gather_source handleSource() const
+    {
+        void *ptr = mwhip_rays_buffer(exec_, handle_, MWHIP_RAYS_BUF_HIT, nullptr);
+        req(ptr != nullptr ? 0 : -1, "handleSource");
+        return mwhip_gather_source { ptr, num_rays_, 8u, 0u, 1u, 0u };
+    }
+
+    uint64_t numFans() const { return num_fans_; }
+    uint64_t numRays() const { return num_rays_; }
+
+private:
+    MWHipRayQuery(mwhip_exec *exec, uint64_t rays, uint64_t num_fans, uint64_t num_rays,
+                  int32_t gpu_id)
+        : ExecObject(exec, rays), num_fans_(num_fans), num_rays_(num_rays), gpu_id_(gpu_id)
+    {}
+
+    py::Tensor tensor(uint32_t which, py::TensorElementType type, uint64_t rows,
+                      int64_t inner, const char *what) const
+    {
+        void *ptr = mwhip_rays_buffer(exec_, handle_, which, nullptr);
+        req(ptr != nullptr ? 0 : -1, what);
+        const int64_t dims[2] = { (int64_t)rows, inner };
+        return py::Tensor(ptr, type, Span<const int64_t>(dims, inner != 0 ? 2 : 1),
+                          Optional<int>::make((int)gpu_id_));
+    }
+
+    uint64_t num_fans_;
+    uint64_t num_rays_;
     int32_t gpu_id_;
 
 friend class MWCudaExecutor;
@@ -1070,6 +1174,26 @@ public:
     {
         req(mwhip_set_step_scatter(exec_, scatter != nullptr ? scatter->handle() : 0,
                                    on ? 1 : 0), "setStepScatter");
+    }
+
+    // desc.num_fans fans of desc.rays_per_fan rays through the worlds'
+    // broadphase BVHs (see MWHipRayQuery and mwhip_rays_desc)
+    MWHipRayQuery makeRayQuery(const mwhip_rays_desc &desc)
+    {
+        uint64_t rays = 0;
+        req(mwhip_rays_create(exec_, &desc, &rays), "makeRayQuery");
+        return MWHipRayQuery(exec_, rays, desc.num_fans,
+                             (uint64_t)desc.num_fans * desc.rays_per_fan, gpu_id_);
+    }
+
+    // on: every replay of a step graph recomputes `rays` behind its step views
+    // (whose slabs and counts it may read) and in front of its step gathers
+    // (which may read the hits), its pack node and its output rings (up to
+    // MWHIP_MAX_STEP_RAYS queries, one launch for all); off: no longer
+    void setStepRays(const MWHipRayQuery *rays, bool on)
+    {
+        req(mwhip_set_step_rays(exec_, rays != nullptr ? rays->handle() : 0, on ? 1 : 0),
+            "setStepRays");
     }
 
     // Device-resident rings (extensions of this backend, include/mwhip.h).

@@ -1750,6 +1750,9 @@ bvhUpdateKernel(EcsState *S, void *, uint32_t, uint32_t)
         rebuildTreeStaged<Check>(bvh, lane, staging, check_staging, S);
     }
 }
+
+// the ray queries' kernel (mwhip_rays_*): rayQueryKernel
+#include <madrona/phys_impl/ray_query.inl>
 }
 #endif // __HIPCC__
 
@@ -2480,6 +2483,18 @@ MADRONA_HOST_API inline TaskGraphNodeID setupBroadphaseTasks(
     };
 #else
     auto bvh_stub = [](bool) -> const void * { return nullptr; };
+#endif
+#if defined(__HIPCC__)
+    [[maybe_unused]] auto ray_stub = [] __host__ () -> const void * {
+        return (const void *)&kernels::rayQueryKernel;
+    };
+#else
+    auto ray_stub = []() -> const void * { return nullptr; };
+#endif
+#if MADRONA_ON_HOST
+    // a simulator with a broadphase has ray queries (mwhip_rays_create): the
+    // kernel is in this code object, the runtime launches it
+    mwhip::check(mwhip_set_ray_kernel(builder.exec(), ray_stub()), "set_ray_kernel");
 #endif
 
     const bool carried = inputs == BroadphaseInputs::CarriedOver;

@@ -137,6 +137,18 @@ class GatherSource(C.Structure):
                 ("handles_per_record", C.c_uint32), ("pad_", C.c_uint32)]
 
 
+class RaySource(C.Structure):
+    """mwhip_ray_source (include/mwhip.h)."""
+    _fields_ = [("src", C.c_void_p), ("record_bytes", C.c_uint32), ("first_byte", C.c_uint32)]
+
+
+class RaysDesc(C.Structure):
+    """mwhip_rays_desc (include/mwhip.h)."""
+    _fields_ = [("num_fans", C.c_uint32), ("rays_per_fan", C.c_uint32),
+                ("fans_per_world", C.c_uint32), ("pad_", C.c_uint32),
+                ("world", RaySource), ("count", RaySource), ("origin", RaySource)]
+
+
 class SortStats(C.Structure):
     """mwhip_sort_counters (include/mwhip.h)"""
     _fields_ = [(name, C.c_uint64) for name in
@@ -300,6 +312,19 @@ def runtime_lib() -> C.CDLL:
         fn.argtypes = [C.c_void_p, C.c_uint64]
     lib.mwhip_set_step_scatter.restype = C.c_int
     lib.mwhip_set_step_scatter.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
+    lib.mwhip_rays_create.restype = C.c_int
+    lib.mwhip_rays_create.argtypes = [C.c_void_p, C.POINTER(RaysDesc), C.POINTER(C.c_uint64)]
+    lib.mwhip_rays_destroy.restype = None
+    lib.mwhip_rays_destroy.argtypes = [C.c_void_p, C.c_uint64]
+    for fn in (lib.mwhip_rays_compute, lib.mwhip_rays_compute_async):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_uint64]
+    lib.mwhip_rays_buffer.restype = C.c_void_p
+    lib.mwhip_rays_buffer.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
+    lib.mwhip_set_step_rays.restype = C.c_int
+    lib.mwhip_set_step_rays.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
+    lib.mwhip_set_ray_kernel.restype = C.c_int
+    lib.mwhip_set_ray_kernel.argtypes = [C.c_void_p, C.c_void_p]
     return lib
 
 
@@ -321,7 +346,7 @@ class _Checked:
 
 
 class _ExecObject(_Checked):
-    """What Snapshot, StateDigest, WorldView, WorldWrite, WorldReduce, EntityGather and EntityScatter are: something a simulator's
+    """What Snapshot, StateDigest, WorldView, WorldWrite, WorldReduce, EntityGather, EntityScatter and RayQuery are: something a simulator's
     executor owns, named by `handle` there, kept in one of the simulator's
     lists (`_list`) while it is open.  close() frees it and takes it off the
     list (a snapshot too, which used to stay on it until the simulator closed); Simulator.close() frees the executor and orphans
@@ -1367,6 +1392,167 @@ class EntityScatter(_HandleCells):
         self._every_step = bool(on)
 
 
+class RayQuery(_ExecObject):
+    """N = fans x rays_per_fan rays cast through the worlds' broadphase BVHs by
+    one kernel (mwhip_rays_*, include/mwhip.h; madrona_amd/ray_ref.py is the
+    exact definition).  The rays of a fan share an origin and a world.  Inputs:
+    worlds() int32 [F], origins() float32 [F, 3] (each owned unless a source
+    was given -- a device tensor or (ptr, record_bytes, first_byte), read when
+    the kernel runs and kept in place while the query exists; fans_per_world >
+    0 replaces worlds() by world = f // fans_per_world, and `count`, an int32
+    per world such as a view's counts, then SKIPS fans f % fans_per_world >=
+    count[world]), directions() float32 [N, 3] (used as given) and t_max()
+    float32 [N] (+inf at creation).  Outputs, rewritten in full by every
+    compute: status() int32 [N] (HIT 1, MISS 0, SKIPPED -1, BAD_WORLD -2,
+    BAD_RAY -3), hit_t() float32 [N], hits() int32 [N, 2] (gen, id;
+    Entity::none() = -1, -1 on anything but a hit), normals() float32 [N, 3].
+    All are zero-copy torch tensors over the device buffers; what torch writes
+    into the inputs on its own stream must have landed before a compute or a
+    step reads it (torch.cuda.synchronize(): the executor's stream is
+    non-blocking, the ordering is the caller's).  A world whose tree no
+    broadphase pass has built yet (before its first step) gives MISS.  A ray sees the
+    tree as the last broadphase pass of the step left it; spheres are
+    transparent.  handle_source() is what entity_gather() / entity_scatter()
+    take to go from hits to cells.  compute() waits for the executor's stream,
+    compute_async() queues behind the replays queued so far; every_step() makes
+    every replay of a step graph recompute the query behind its step views and
+    in front of its step gathers and output rings.  HIP backend only."""
+
+    _kind, _destroy, _list = "ray query", "mwhip_rays_destroy", "_ray_queries"
+    HIT, MISS, SKIPPED, BAD_WORLD, BAD_RAY = 1, 0, -1, -2, -3
+    _BUFS = {"world": 0, "origin": 1, "dir": 2, "t_max": 3, "hit_t": 4, "hit": 5, "normal": 6,
+             "status": 7}
+
+    @staticmethod
+    def _source(what: str, source, item_bytes: int):
+        """(the tensor to keep alive or None, RaySource) of None, a device
+        tensor whose rows are the records, or (ptr, record_bytes, first_byte)"""
+        if source is None:
+            return None, RaySource(None, 0, 0)
+        if isinstance(source, tuple):
+            ptr, record_bytes, first_byte = (int(v) for v in source)
+            return None, RaySource(ptr, record_bytes, first_byte)
+        import torch
+
+        if not isinstance(source, torch.Tensor) or not source.is_cuda:
+            raise TypeError(f"ray_query(): {what} is a torch tensor on the device or a "
+                            "(ptr, record_bytes, first_byte) tuple")
+        if source.element_size() != 4 or not source.is_contiguous() or source.dim() < 1:
+            raise TypeError(f"ray_query(): the {what} tensor must be contiguous with 4-byte "
+                            f"items, not {source.dtype} {tuple(source.shape)}")
+        record = item_bytes if source.dim() == 1 else int(source.shape[-1]) * 4
+        if record < item_bytes:
+            raise TypeError(f"ray_query(): rows of {record} bytes are too short for {what}")
+        return source, RaySource(source.data_ptr(), record, 0)
+
+    def __init__(self, sim: "Simulator", fans: int, rays_per_fan: int, world=None, origin=None,
+                 fans_per_world: int = 0, count=None):
+        self._sim = sim
+        self.num_fans, self.rays_per_fan = int(fans), int(rays_per_fan)
+        self.num_rays = self.num_fans * self.rays_per_fan
+        self.fans_per_world = int(fans_per_world)
+        self._rt = runtime_lib()
+        self._exec = sim.hip_exec()
+        self._tensors = {}
+        self._every_step = False
+        self.handle = 0
+        desc = RaysDesc(self.num_fans, self.rays_per_fan, self.fans_per_world, 0)
+        keep_w, desc.world = self._source("world", world, 4)
+        keep_c, desc.count = self._source("count", count, 4)
+        keep_o, desc.origin = self._source("origin", origin, 12)
+        self._sources = (keep_w, keep_c, keep_o)    # (stay where they are)
+        handle = C.c_uint64(0)
+        self._check(self._rt.mwhip_rays_create(self._exec, C.byref(desc), C.byref(handle)),
+                    "mwhip_rays_create")
+        self.handle = int(handle.value)
+        self._owned = {"world": world is None and self.fans_per_world == 0,
+                       "origin": origin is None}
+
+    def _orphan(self) -> None:
+        super()._orphan()
+        self._tensors = {}
+        self._sources = ()
+
+    _wrap = WorldView._wrap
+
+    def buffer_ptr(self, name: str) -> int:
+        """Device address of owned buffer `name`: world, origin, dir, t_max,
+        hit_t, hit, normal or status."""
+        handle = self._live()
+        nbytes = C.c_uint64(0)
+        ptr = self._rt.mwhip_rays_buffer(self._exec, handle, self._BUFS[name], C.byref(nbytes))
+        if not ptr:
+            raise RuntimeError(f"mwhip_rays_buffer({name}): "
+                               f"{self._rt.mwhip_last_error().decode()}")
+        return int(ptr)
+
+    def _tensor(self, name, dtype, shape):
+        self._live()
+        if not self._owned.get(name, True):
+            raise RuntimeError(f"this ray query owns no {name} buffer: " + (
+                "fans_per_world gives each fan its world" if name == "world"
+                and self.fans_per_world else f"a {name} source was given"))
+        if name not in self._tensors:
+            self._wrap(name, self.buffer_ptr(name), dtype, shape)
+        return self._tensors[name]
+
+    def worlds(self):
+        """int32 [F] (owned: no world source and no fans_per_world)"""
+        return self._tensor("world", np.int32, (self.num_fans,))
+
+    def origins(self):
+        """float32 [F, 3] (owned: no origin source)"""
+        return self._tensor("origin", np.float32, (self.num_fans, 3))
+
+    def directions(self):
+        """float32 [N, 3]"""
+        return self._tensor("dir", np.float32, (self.num_rays, 3))
+
+    def t_max(self):
+        """float32 [N], +inf at creation"""
+        return self._tensor("t_max", np.float32, (self.num_rays,))
+
+    def hit_t(self):
+        """float32 [N], 0 on anything but a hit"""
+        return self._tensor("hit_t", np.float32, (self.num_rays,))
+
+    def hits(self):
+        """int32 [N, 2] (gen, id), -1, -1 on anything but a hit"""
+        return self._tensor("hit", np.int32, (self.num_rays, 2))
+
+    def normals(self):
+        """float32 [N, 3], zero on anything but a hit"""
+        return self._tensor("normal", np.float32, (self.num_rays, 3))
+
+    def status(self):
+        """int32 [N]: HIT 1, MISS 0, SKIPPED -1, BAD_WORLD -2, BAD_RAY -3"""
+        return self._tensor("status", np.int32, (self.num_rays,))
+
+    def handle_source(self):
+        """The hits as a source of Simulator.entity_gather() / entity_scatter():
+        (ptr, num_records, record_bytes, first_byte, handles_per_record)."""
+        return (self.buffer_ptr("hit"), self.num_rays, 8, 0, 1)
+
+    def compute(self) -> "RayQuery":
+        """Rewrites every output; waits for the executor's stream."""
+        self._check(self._rt.mwhip_rays_compute(self._exec, self._live()), "mwhip_rays_compute")
+        return self
+
+    def compute_async(self) -> None:
+        self._check(self._rt.mwhip_rays_compute_async(self._exec, self._live()),
+                    "mwhip_rays_compute_async")
+
+    def every_step(self, on: bool = True) -> None:
+        """Every replay of a step graph recomputes this query (waits for the
+        stream and rebuilds the launch graphs); on=False turns it off again."""
+        handle = self._live()
+        if not on and not self._every_step:
+            return
+        self._check(self._rt.mwhip_set_step_rays(self._exec, handle, 1 if on else 0),
+                    "mwhip_set_step_rays")
+        self._every_step = bool(on)
+
+
 class Simulator:
     """One simulator instance behind the C API (either backend)."""
 
@@ -1398,6 +1584,7 @@ class Simulator:
         self._reduces: List["WorldReduce"] = []
         self._gathers: List["EntityGather"] = []
         self._scatters: List["EntityScatter"] = []
+        self._ray_queries: List["RayQuery"] = []
         self._tensor_info: Dict[str, Tuple[int, np.dtype, Tuple[int, ...], bool]] = {}
         for i in range(self.lib.sim_num_tensors(self.handle)):
             info = SimTensorInfo()
@@ -1415,11 +1602,12 @@ class Simulator:
     def close(self) -> None:
         if self.handle:
             # sim_destroy frees the executor and with it its snapshots, digests,
-            # world views, world writes, world reduces, entity gathers and
-            # entity scatters, and
+            # world views, world writes, world reduces, entity gathers,
+            # entity scatters and ray queries, and
             # forgets its output rings (the trajectories keep their tensors)
             for open_ones in (self._snapshots, self._trajectories, self._digests, self._views,
-                              self._writes, self._reduces, self._gathers, self._scatters):
+                              self._writes, self._reduces, self._gathers, self._scatters,
+                              self._ray_queries):
                 for obj in open_ones:
                     obj._orphan()
                 open_ones.clear()
@@ -1652,6 +1840,22 @@ class Simulator:
         scatter = EntityScatter(self, source, components)
         self._scatters.append(scatter)
         return scatter
+
+    def ray_query(self, fans: int, rays_per_fan: int, world=None, origin=None,
+                  fans_per_world: int = 0, count=None) -> "RayQuery":
+        """A RayQuery of `fans` fans of `rays_per_fan` rays through the worlds'
+        broadphase BVHs (HIP backend, a simulator with a broadphase).  `world`
+        (int32 per fan), `origin` (3 floats per fan) and `count` (int32 per
+        world, with fans_per_world) are device tensors whose rows are the
+        records or (ptr, record_bytes, first_byte); None: world and origin are
+        buffers the query owns (worlds(), origins()).  fans_per_world > 0:
+        world = f // fans_per_world, the shape of a world view's slab.
+        Simulator.close() frees what is left open."""
+        if self.backend != "hip":
+            raise RuntimeError(f"ray queries need the HIP backend, this is {self.backend!r}")
+        query = RayQuery(self, fans, rays_per_fan, world, origin, fans_per_world, count)
+        self._ray_queries.append(query)
+        return query
 
     def record(self, names: List[str], steps: int, on_render: bool = False) -> "Trajectory":
         """Records the exported tensors `names` on the device from the next

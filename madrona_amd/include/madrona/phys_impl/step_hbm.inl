@@ -129,15 +129,22 @@ __device__ inline uint32_t constraintLevels(uint32_t lane, uint32_t n,
 }
 
 // A static body does not order the constraints that touch it as long as the
-// solver's writes to it are no-ops.  Positions are (x += 0), but the reference
-// renormalises the rotation in every positional update (xpbd.cpp
-// applyPositionalUpdate), so that only holds while the rotation is a fixed
-// point of normalize() -- e.g. not for a tilted body that was switched to
-// Static mid-flight; such a body orders its constraints like a dynamic one.
-__device__ inline bool staticBodyIsInert(math::Quat q)
+// solver's writes to it are no-ops.  The reference renormalises the rotation in
+// every positional update (xpbd.cpp applyPositionalUpdate), so that only holds
+// while the rotation is a fixed point of normalize() -- e.g. not for a tilted
+// body that was switched to Static mid-flight.  Its position update is
+// x += 0 * n, which leaves every value as it is except -0.0: -0.0 + 0.0 is
+// +0.0, so a position with a -0.0 component is not a fixed point either (until
+// the first constraint has turned it into +0.0, which then stays).  A static
+// body that is not inert orders its constraints like a dynamic one.
+__device__ inline bool staticBodyIsInert(math::Vector3 x, math::Quat q)
 {
     math::Quat n = q.normalize();
-    return n.w == q.w && n.x == q.x && n.y == q.y && n.z == q.z;
+    const bool neg_zero =
+        (__builtin_bit_cast(uint32_t, x.x) == 0x80000000u) |
+        (__builtin_bit_cast(uint32_t, x.y) == 0x80000000u) |
+        (__builtin_bit_cast(uint32_t, x.z) == 0x80000000u);
+    return n.w == q.w && n.x == q.x && n.y == q.y && n.z == q.z && !neg_zero;
 }
 
 __device__ inline uint64_t bodyKey(Context &ctx, Loc loc)
@@ -145,6 +152,7 @@ __device__ inline uint64_t bodyKey(Context &ctx, Loc loc)
     if (ctx.getDirect<ResponseType>(RGDCols::ResponseType, loc) ==
             ResponseType::Static &&
         staticBodyIsInert(
+            ctx.getDirect<base::Position>(RGDCols::Position, loc),
             ctx.getDirect<base::Rotation>(RGDCols::Rotation, loc))) {
         return 0;
     }

@@ -868,6 +868,9 @@ __device__ __attribute__((always_inline)) inline FramedWorld loadWorldFramed(
     return out;
 }
 
+// the constraint solve of a substep over the block (solveSubstepConstraints)
+#include "step_solve.inl"
+
 // Wavefronts per SIMD.  The step is bound by instruction issue and by the
 // latency of its LDS / HBM round trips (SQ counters, profiles/r06_phys_occupancy_
 // counters.jsonl: one wavefront per SIMD issues 59 % of its cycles and waits
@@ -1066,7 +1069,7 @@ physicsStepLdsKernel(EcsState *S, void *node_data, uint32_t, uint32_t)
                 uint32_t end = (uint32_t)w->primOffset[k] + w->primCount[k];
                 prim_end = end > prim_end ? end : prim_end;
                 solved = !((uint32_t)w->resp[k] == (uint32_t)ResponseType::Static &&
-                           staticBodyIsInert(w->poses[k].q));
+                           staticBodyIsInert(w->poses[k].x, w->poses[k].q));
                 w->solverKey[k] = solved ? (uint8_t)(k + 1) : (uint8_t)0;
             }
             const uint64_t solved_mask = wave::groupBallot<LPW>(solved);
@@ -1649,127 +1652,10 @@ physicsStepLdsKernel(EcsState *S, void *node_data, uint32_t, uint32_t)
             wave::phaseFence();
             PHYS_PROF(5);
 
-            // ---- position solve: contacts, then joints, level by level ----------
-            // (the levels of the first window of contacts -- all of them, in
-            // every world seen so far -- serve the velocity solve as well: same
-            // contacts, same bodies)
-            uint32_t first_level = 0, first_max_level = 0;
-            for (uint32_t base = 0; base < num_contacts; base += LPW) {
-                const uint32_t n = num_contacts - base < (uint32_t)LPW ?
-                    num_contacts - base : (uint32_t)LPW;
-                const uint32_t i = base + lane;
-                uint32_t key_a = 0, key_b = 0;
-                if (lane < n) {
-                    key_a = ldsBodyKey(w, w->contacts()[i].refBody());
-                    key_b = ldsBodyKey(w, w->contacts()[i].altBody());
-                }
-                uint32_t level = constraintLevels<LPW>(lane, n, key_a, key_b);
-                uint32_t max_level = wave::maxReduce<LPW>(lane < n ? level : 0);
-                if (base == 0) {
-                    first_level = level;
-                    first_max_level = max_level;
-                }
-
-                for (uint32_t l = 0; l <= max_level; l++) {
-                    // two lanes per contact, a body each (xpbd::paired): the
-                    // level's contacts in index order over the world's teams
-                    const uint64_t members =
-                        wave::groupBallot<LPW>(lane < n && level == l);
-                    const uint32_t count = (uint32_t)__builtin_popcountll(members);
-                    for (uint32_t first = 0; first < count; first += LPW / 2) {
-                        const uint32_t team = first + (lane >> 1);
-                        if (team < count) {
-                            const uint32_t ci =
-                                base + wave::nthSetBit<LPW>(members, team);
-                            const bool second = (lane & 1u) != 0u;
-                            float lambda_n[4] { 0.f, 0.f, 0.f, 0.f };
-                            xpbd::paired::handleContact(second, store,
-                                w->contacts()[ci].view(), lambda_n);
-                            if (!second) {
-                                w->lambdas[ci] = lambda_n[0];
-                            }
-                        }
-                    }
-                    wave::phaseFence();
-                }
-            }
-
-            // (at most maxJointBodies of them: one window)
-            if (num_joints > 0) {
-                const uint32_t n = (uint32_t)num_joints;
-                Loc l1 { 0, 0 }, l2 { 0, 0 };
-                uint32_t key_a = 0, key_b = 0;
-                if (lane < n) {
-                    l1 = Loc { 0, (int32_t)w->jointBodies[lane][0] };
-                    l2 = Loc { 0, (int32_t)w->jointBodies[lane][1] };
-                    key_a = ldsBodyKey(w, l1.row);
-                    key_b = ldsBodyKey(w, l2.row);
-                }
-                uint32_t level = constraintLevels<LPW>(lane, n, key_a, key_b);
-                uint32_t max_level = wave::maxReduce<LPW>(lane < n ? level : 0);
-
-                for (uint32_t l = 0; l <= max_level; l++) {
-                    // (two lanes per joint, an end each; at most maxJointBodies
-                    // joints: one round of teams)
-                    const uint64_t members =
-                        wave::groupBallot<LPW>(lane < n && level == l);
-                    const uint32_t team = lane >> 1;
-                    if (team < (uint32_t)__builtin_popcountll(members)) {
-                        const uint32_t j = wave::nthSetBit<LPW>(members, team);
-                        const bool second = (lane & 1u) != 0u;
-                        const Loc me { 0, (int32_t)w->jointBodies[j][second ? 1 : 0] };
-                        // (rows beyond the block's: out of the sorted table)
-                        xpbd::paired::handleJointConstraint(second, store, me,
-                            j < (uint32_t)Block::maxJoints ? w->joints[j] : joints[j]);
-                    }
-                    wave::phaseFence();
-                }
-            }
-
-            PHYS_PROF(4);
-            // ---- velocities -----------------------------------------------------
-            for (int32_t k = (int32_t)lane; k < num_bodies; k += LPW) {
-                w->vel[k] = xpbd::deriveVelocity(w->poses[k].x, w->poses[k].q,
-                    store.prevState(Loc { 0, k }), w->sys.h);
-            }
-            wave::phaseFence();
-            PHYS_PROF(4);
-
-            for (uint32_t base = 0; base < num_contacts; base += LPW) {
-                const uint32_t n = num_contacts - base < (uint32_t)LPW ?
-                    num_contacts - base : (uint32_t)LPW;
-                const uint32_t i = base + lane;
-                uint32_t level = first_level;
-                uint32_t max_level = first_max_level;
-                if (base != 0) {
-                    uint32_t key_a = 0, key_b = 0;
-                    if (lane < n) {
-                        key_a = ldsBodyKey(w, w->contacts()[i].refBody());
-                        key_b = ldsBodyKey(w, w->contacts()[i].altBody());
-                    }
-                    level = constraintLevels<LPW>(lane, n, key_a, key_b);
-                    max_level = wave::maxReduce<LPW>(lane < n ? level : 0);
-                }
-
-                for (uint32_t l = 0; l <= max_level; l++) {
-                    const uint64_t members =
-                        wave::groupBallot<LPW>(lane < n && level == l);
-                    const uint32_t count = (uint32_t)__builtin_popcountll(members);
-                    for (uint32_t first = 0; first < count; first += LPW / 2) {
-                        const uint32_t team = first + (lane >> 1);
-                        if (team < count) {
-                            const uint32_t ci =
-                                base + wave::nthSetBit<LPW>(members, team);
-                            float lambda_n[4] { w->lambdas[ci], 0.f, 0.f, 0.f };
-                            xpbd::paired::solveVelocitiesForContact(
-                                (lane & 1u) != 0u, store,
-                                w->contacts()[ci].view(), lambda_n, w->sys.h,
-                                w->sys.restitutionThreshold);
-                        }
-                    }
-                    wave::phaseFence();
-                }
-            }
+            // ---- position solve, velocities, velocity solve (step_solve.inl) ----
+            solveSubstepConstraints<MAXB, LPW>(lane, w, store, num_bodies,
+                num_contacts, num_joints, joints,
+                [&](int slot) { (void)slot; PHYS_PROF(slot); });
             PHYS_PROF(11);
         }
 

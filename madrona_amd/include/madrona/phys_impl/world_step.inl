@@ -3,7 +3,8 @@
 // code is split by what it does: step_wave.inl (wavefront primitives),
 // step_narrowphase.inl (cooperative SAT / clipping / manifolds), step_hbm.inl
 // (the step out of HBM + shared pieces), step_lds.inl (the step with the world
-// in LDS), step_order.inl (the order / frame kernel in front of it).
+// in LDS; step_solve.inl, which it includes: its constraint solve),
+// step_order.inl (the order / frame kernel in front of it).
 //
 // Worlds are independent, and everything the physics step does is per world:
 // find candidate pairs, then per substep integrate, collide, solve positions,

@@ -3,6 +3,9 @@
 // tests can diff the two function by function without a GPU.
 #include <madrona/physics.hpp>
 #include <madrona/physics_assets.hpp>
+#include <madrona/phys_impl/xpbd.hpp>
+
+#include "solver_world.hpp"
 
 #include <cstring>
 #include <vector>
@@ -206,6 +209,25 @@ API void amd_collide_pair(const float *verts, uint32_t num_verts,
     (void)unsupported;
 
     free(buf);
+}
+
+// One world through the overlay's scalar solver routines over an array-backed
+// body store (the math physicsStepKernel runs), behind the C ABI of
+// oracle/ref_shims/xpbd_ref_shim.cpp's ref_solve_world.
+API int32_t amd_solve_world(const float *bodies, const int32_t *body_types,
+                            int32_t num_bodies,
+                            const float *contacts, const int32_t *contact_ints,
+                            int32_t num_contacts,
+                            const float *joints, const int32_t *joint_ints,
+                            int32_t num_joints,
+                            const float *sys, uint32_t phase_mask,
+                            float *bodies_out, float *lambdas)
+{
+    solver_world::Body work[solver_world::kMaxBodies];
+    return solver_world::solveWorldScalar(
+        bodies, body_types, num_bodies, contacts, contact_ints, num_contacts,
+        joints, joint_ints, num_joints, sys, phase_mask, bodies_out, lambdas,
+        work);
 }
 
 }

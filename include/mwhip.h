@@ -296,6 +296,28 @@ enum mwhip_node_kind {
  * flagged node that no unflagged node of the same name follows in the task
  * graph's order: there would be nothing to carry over. */
 #define MWHIP_NODE_CARRIED 0x80000000u
+/* OR-ed into mwhip_node_desc::kind of a ParallelFor node (added under ABI 9 like
+ * the bit above): the simulator named the node as member of a group at compile
+ * time (madrona::SideBySide, taskgraph.hpp).  Such a node is a node like any
+ * other -- its own kernel, its pfor_body -- and, where it says otherwise today,
+ * three fields say more:
+ *   pfor_group_kernel  the group's INLINED kernel, __global__ void(ecs_state *,
+ *                      const mwhip_pfor_inline_group *), which calls every
+ *                      member's body directly; the node's pointer group kernel is
+ *                      the executor's (mwhip_set_pfor_group_kernel)
+ *   component_id       the node's index in that kernel's member list
+ *   archetype_id       bytes of static LDS the node's system uses as scratch
+ *                      (madrona::mwhip::systemScratchLDS; 0: none).  A node whose
+ *                      own kernel carries exactly that much static LDS carries
+ *                      no row-appender marker on top of it: it cannot append
+ *                      rows
+ * Consecutive launches that name the same inlined kernel and pass every
+ * condition of a grouped launch (same dependencies, no carried member, no member
+ * that can append rows, no write clash, same task graph) become ONE launch of
+ * it, whatever registers their own kernels take (DESIGN.md section 34;
+ * MADRONA_MWHIP_GROUP_INLINE=0: never).  Every other member is treated as if the
+ * bit were not set. */
+#define MWHIP_NODE_INLINE_GROUP 0x40000000u
 
 #define MWHIP_SCAN_MAX_SEGMENTS 8
 typedef struct mwhip_scan_params {
@@ -399,6 +421,19 @@ typedef struct mwhip_pfor_group {
     uint32_t num_matching_and_flags[MWHIP_PFOR_GROUP_MAX];
     mwhip_pfor_args query[MWHIP_PFOR_GROUP_MAX];
 } mwhip_pfor_group;
+
+/* Members of an inlined grouped launch (MWHIP_NODE_INLINE_GROUP), in device
+ * memory, indexed by the member's place in the kernel's list.  The grid is
+ * one-dimensional: member i runs in workgroups [first_workgroup[i],
+ * first_workgroup[i] + num_workgroups[i]) of 256 threads, the workgroups a
+ * launch of its own would have had; num_workgroups[i] == 0: not in this launch. */
+typedef struct mwhip_pfor_inline_group {
+    uint32_t first_workgroup[MWHIP_PFOR_GROUP_MAX];
+    uint32_t num_workgroups[MWHIP_PFOR_GROUP_MAX];
+    uint32_t query_offset[MWHIP_PFOR_GROUP_MAX];
+    uint32_t num_matching_and_flags[MWHIP_PFOR_GROUP_MAX];
+    mwhip_pfor_args query[MWHIP_PFOR_GROUP_MAX];
+} mwhip_pfor_inline_group;
 
 /* (the reference's TaskGraph::maxNodeDataBytes is 256; larger here because a
  * node's data is what its kernel reaches with one load from its arguments) */

@@ -194,6 +194,10 @@ struct NodeRec {
     std::string name;
     std::vector<int32_t> deps;
     bool carried = false;       // MWHIP_NODE_CARRIED was set in desc.kind
+    // MWHIP_NODE_INLINE_GROUP was set in desc.kind: desc.pfor_group_kernel is
+    // the group's inlined kernel, desc.component_id the node's place in its
+    // member list, desc.archetype_id its declared scratch LDS
+    bool inlineGroup = false;
 };
 
 struct TaskGraphRec {

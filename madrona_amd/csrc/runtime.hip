@@ -785,7 +785,10 @@ extern "C" int32_t mwhip_tg_add_node(mwhip_exec *exec, uint32_t tg_id,
     NodeRec node;
     node.desc = *desc;
     node.carried = (desc->kind & MWHIP_NODE_CARRIED) != 0u;
-    node.desc.kind = desc->kind & ~MWHIP_NODE_CARRIED;
+    node.inlineGroup = (desc->kind & MWHIP_NODE_INLINE_GROUP) != 0u &&
+        desc->pfor_group_kernel != nullptr &&
+        desc->component_id < MWHIP_PFOR_GROUP_MAX;
+    node.desc.kind = desc->kind & ~(MWHIP_NODE_CARRIED | MWHIP_NODE_INLINE_GROUP);
     node.name = desc->name != nullptr ? desc->name : "node";
     node.desc.name = nullptr;
     for (uint32_t i = 0; i < num_deps; i++) {

@@ -262,6 +262,13 @@ struct KernelLaunch {
     uint32_t pforArg1 = 0;                  // num_matching | exclusive-world flag
     bool rowSnapshot = false;               // the node can append rows: never grouped
     uint32_t pforVgprs = 0;                 // of the node's own kernel (groupLaunches)
+    // MWHIP_NODE_INLINE_GROUP: the inlined kernel the simulator named the node a
+    // member of (nullptr: none), and the node's place in its member list
+    const void *pforInlineKernel = nullptr;
+    uint32_t pforInlineMember = 0;
+    // the kernel's static LDS is all declared scratch (systemScratchLDS): the
+    // row snapshot it got on the safe side is not that of a row appender
+    bool scratchOnlyLds = false;
     uint32_t pforWriteMask = 0xFFFFFFFFu;   // query components the system may write
     mwhip_pfor_args pforArgs {};
     struct Member {                         // of a grouped launch (profiles)

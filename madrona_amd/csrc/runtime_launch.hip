@@ -468,8 +468,16 @@ static int buildLaunchList(mwhip_exec *exec, const std::vector<uint32_t> &tg_ids
                     k.pforArgs = pa;
                     k.rowSnapshot = pa.row_sync != nullptr;
                     k.pforBody = d.pfor_body;
-                    k.pforGroupKernel = d.pfor_group_kernel != nullptr ?
-                        d.pfor_group_kernel : exec->pforGroupKernel;
+                    if (node.inlineGroup) {
+                        k.pforInlineKernel = d.pfor_group_kernel;
+                        k.pforInlineMember = d.component_id;
+                        k.pforGroupKernel = exec->pforGroupKernel;
+                        k.scratchOnlyLds = d.archetype_id != 0u &&
+                            attr.sharedSizeBytes == (size_t)d.archetype_id;
+                    } else {
+                        k.pforGroupKernel = d.pfor_group_kernel != nullptr ?
+                            d.pfor_group_kernel : exec->pforGroupKernel;
+                    }
                     k.pforArg1 = d.arg1;
                     k.pforVgprs = (uint32_t)std::max(attr.numRegs, 0);
                     k.pforWriteMask = d.write_mask;
@@ -917,6 +925,23 @@ static int groupLaunches(mwhip_exec *exec, LaunchGraph &lg)
             k.countMode == MWHIP_COUNT_QUERY_ROWS && k.tgNode >= 0 &&
             k.tgId < exec->taskGraphs.size();
     };
+    // Members of a group the simulator named at compile time (SideBySide,
+    // MWHIP_NODE_INLINE_GROUP): the group's kernel calls every body directly, so
+    // what the cap above guards against -- a long body out of line -- does not
+    // happen and the cap does not apply.  Every other condition does.  A member
+    // "can append rows" when its kernel carries static LDS other than the scratch
+    // its system declared (a snapshot taken on the safe side for declared
+    // scratch alone is dropped in the group: nobody in the launch appends rows).
+    // MADRONA_MWHIP_GROUP_INLINE=0: only the rule above.
+    const bool inline_groups = envU32("MADRONA_MWHIP_GROUP_INLINE", 1) != 0;
+    auto inlineGroupable = [&](const KernelLaunch &k) {
+        return inline_groups && k.pforInlineKernel != nullptr &&
+            k.pforInlineMember < MWHIP_PFOR_GROUP_MAX &&
+            k.dagKernel && !k.carried &&
+            (!k.rowSnapshot || k.scratchOnlyLds) &&
+            k.countMode == MWHIP_COUNT_QUERY_ROWS && k.tgNode >= 0 &&
+            k.tgId < exec->taskGraphs.size();
+    };
     auto depsOf = [&](const KernelLaunch &k) {
         std::vector<int32_t> d = exec->taskGraphs[k.tgId].nodes[(size_t)k.tgNode].deps;
         std::sort(d.begin(), d.end());
@@ -929,6 +954,11 @@ static int groupLaunches(mwhip_exec *exec, LaunchGraph &lg)
     // may write (non-const reference) a component the other names, on a table
     // both queries match.  (What a system reaches through ctx.get() is not in
     // its signature: INTEGRATION.md section 3, MADRONA_MWHIP_GROUP=0.)
+    // The rule reads signatures, so it is stricter than the code: escape_room_
+    // phys' collectObservationsSystem takes Position & and Rotation & and writes
+    // neither.  It still shares a launch with the lidar, whose query (Entity,
+    // Lidar) names neither component; beside a node that did name one of them it
+    // would keep a launch of its own, which costs time, never correctness.
     auto queryOf = [&](const KernelLaunch &k) -> const QueryRec * {
         for (const QueryRec &q : exec->queries) {
             if (q.offset == k.queryOffset) return &q;
@@ -967,6 +997,86 @@ static int groupLaunches(mwhip_exec *exec, LaunchGraph &lg)
     std::vector<KernelLaunch> out;
     for (size_t i = 0; i < lg.launches.size(); ) {
         size_t j = i + 1;
+        if (inlineGroupable(lg.launches[i])) {
+            const std::vector<int32_t> deps = depsOf(lg.launches[i]);
+            uint32_t taken = 1u << lg.launches[i].pforInlineMember;
+            while (j < lg.launches.size() && inlineGroupable(lg.launches[j]) &&
+                   lg.launches[j].tgId == lg.launches[i].tgId &&
+                   lg.launches[j].pforInlineKernel ==
+                       lg.launches[i].pforInlineKernel &&
+                   (taken & (1u << lg.launches[j].pforInlineMember)) == 0u &&
+                   depsOf(lg.launches[j]) == deps) {
+                bool clash = false;
+                for (size_t m = i; m < j; m++) {
+                    clash = clash || conflicts(lg.launches[m], lg.launches[j]);
+                }
+                if (clash) break;
+                taken |= 1u << lg.launches[j].pforInlineMember;
+                j++;
+            }
+            if (j - i >= 2) {
+                // Members with the fewest workgroups first: they start with the
+                // launch and do not trail it.  Each gets the threads a launch of
+                // its own would have had, in workgroups of 256.
+                std::vector<size_t> order;
+                for (size_t m = i; m < j; m++) order.push_back(m);
+                auto workgroupsOf = [&](size_t m) {
+                    const KernelLaunch &k = lg.launches[m];
+                    return std::max((k.grid.x * k.block.x + 255u) / 256u, 1u);
+                };
+                std::stable_sort(order.begin(), order.end(),
+                    [&](size_t a, size_t b) {
+                        return workgroupsOf(a) < workgroupsOf(b);
+                    });
+                mwhip_pfor_inline_group group {};
+                uint32_t next_workgroup = 0;
+                for (size_t m : order) {
+                    const KernelLaunch &k = lg.launches[m];
+                    const uint32_t slot = k.pforInlineMember;
+                    group.first_workgroup[slot] = next_workgroup;
+                    group.num_workgroups[slot] = workgroupsOf(m);
+                    group.query_offset[slot] = k.queryOffset;
+                    group.num_matching_and_flags[slot] = k.pforArg1;
+                    group.query[slot] = k.pforArgs;
+                    // (the members read the live row counts)
+                    group.query[slot].row_sync = nullptr;
+                    next_workgroup += workgroupsOf(m);
+                }
+                KernelLaunch g;
+                g.fn = lg.launches[i].pforInlineKernel;
+                std::string name = "group[";
+                for (size_t m = i; m < j; m++) {
+                    const KernelLaunch &k = lg.launches[m];
+                    name += (m == i ? "" : " | ") + k.name;
+                    g.members.push_back({ k.name, k.queryOffset, k.bytesPerRow,
+                                          k.ioDeclared });
+                }
+                name += "]";
+                mwhip_pfor_inline_group *group_dev = nullptr;
+                int rc = devAllocT(exec, &group_dev, 1);
+                if (rc != 0) return rc;
+                HIPCHK(hipMemcpy(group_dev, &group, sizeof(group),
+                                 hipMemcpyHostToDevice));
+                g.grid = dim3(next_workgroup, 1, 1);
+                g.block = dim3(256, 1, 1);
+                g.setArgs(exec->stateDev,
+                          (const mwhip_pfor_inline_group *)group_dev);
+                g.name = name;
+                g.role = "";
+                g.kind = MWHIP_NODE_KERNEL;
+                g.countMode = MWHIP_COUNT_QUERY_ROWS;
+                g.ioDeclared = 1;
+                for (const auto &mem : g.members) {
+                    g.ioDeclared = g.ioDeclared && mem.ioDeclared != 0u ? 1u : 0u;
+                }
+                g.nodeIndex = lg.launches[i].nodeIndex;
+                g.dagKernel = false;
+                out.push_back(g);
+                i = j;
+                continue;
+            }
+            j = i + 1;
+        }
         if (groupable(lg.launches[i])) {
             const std::vector<int32_t> deps = depsOf(lg.launches[i]);
             while (j < lg.launches.size() && j - i < MWHIP_PFOR_GROUP_MAX &&

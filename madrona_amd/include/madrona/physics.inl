@@ -435,9 +435,15 @@ struct BVH::RayGroupScratch {
 // The scratch of the calling lane's group of 32 in a 1-D workgroup of at most
 // 256 threads (what a CustomParallelForNode<..., 32, 1, ...> runs in); nullptr
 // in any other block shape.  Only kernels that call this carry the LDS.
+// (rayGroupScratchBytes: all of it, what a system that calls this declares as
+// its mwhip::systemScratchLDS)
+inline constexpr uint32_t rayGroupScratchGroups = 8;
+inline constexpr uint32_t rayGroupScratchBytes =
+    rayGroupScratchGroups * (uint32_t)sizeof(BVH::RayGroupScratch);
+
 __device__ inline BVH::RayGroupScratch *rayGroupScratch()
 {
-    constexpr uint32_t groups_per_block = 8;
+    constexpr uint32_t groups_per_block = rayGroupScratchGroups;
     __shared__ BVH::RayGroupScratch scratch[groups_per_block];
     if (blockDim.x > 32u * groups_per_block || blockDim.y != 1u ||
             blockDim.z != 1u) {

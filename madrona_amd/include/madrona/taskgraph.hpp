@@ -27,6 +27,7 @@
 
 #include <mwhip.h>
 
+#include <array>
 #include <cstring>
 #include <functional>
 #include <memory>
@@ -271,11 +272,40 @@ public:
     MADRONA_HOST_API static TaskGraph::NodeID addToGraph(
         TaskGraph::Builder &builder,
         Span<const TaskGraph::NodeID> dependencies);
+
+    // (SideBySide: the same registration, plus the group's inlined kernel and
+    // the node's place in its member list; nullptr: a node on its own)
+    MADRONA_HOST_API static TaskGraph::NodeID addToGraphAsMember(
+        TaskGraph::Builder &builder,
+        Span<const TaskGraph::NodeID> dependencies,
+        const void *inline_group_kernel, uint32_t member_index);
 };
 
 template <typename ContextT, auto Fn, typename... ComponentTs>
 using ParallelForNode =
     CustomParallelForNode<ContextT, Fn, 1, 1, ComponentTs...>;
+
+// This backend's extension: ParallelForNode / CustomParallelForNode<..., 1, ...>
+// members of one ContextT that the simulator runs side by side.  Naming them
+// here is what naming the same dependencies already says -- no member depends
+// on another, none relies on running before or after another -- and it gives the
+// runtime ONE kernel with every member's body inlined: members that pass the
+// runtime's conditions for a grouped launch share one launch of it, however
+// many registers they take.
+// Every member is registered as its own addToGraph registers it and keeps a
+// NodeID of its own, in the members' order:
+//
+//   auto [collect_obs, lidar] = SideBySide<
+//       ParallelForNode<Engine, collectObservationsSystem, ...>,
+//       CustomParallelForNode<Engine, lidarSystem, 32, 1, ...>
+//   >::addToGraph(builder, {post_reset_broadphase});
+template <typename... MemberTs>
+class SideBySide : public NodeBase {
+public:
+    MADRONA_HOST_API static std::array<TaskGraph::NodeID, sizeof...(MemberTs)>
+    addToGraph(TaskGraph::Builder &builder,
+               Span<const TaskGraph::NodeID> dependencies);
+};
 
 struct ClearTmpNodeBase : NodeBase {
     MADRONA_HOST_API static inline TaskGraph::NodeID addToGraph(

@@ -202,18 +202,23 @@ MADRONA_DEVICE inline void invokeSystemRow(ContextT &ctx, void *const *cols,
 // 190-226) -- e.g. one ray per lane in a lidar system.
 template <typename ContextT, auto Fn, int32_t threads_per_invocation,
           typename... ComponentTs>
-MADRONA_DEVICE inline void parallelForTable(StateManager *state_mgr,
+MADRONA_DEVICE MADRONA_ALWAYS_INLINE inline void parallelForTable(
+                                            StateManager *state_mgr,
                                             TableHdr &tbl,
                                             const uint16_t *col_indices,
                                             bool exclusive_world,
                                             int32_t num_rows,
-                                            int32_t rows_before)
+                                            int32_t rows_before,
+                                            uint32_t block_idx,
+                                            uint32_t num_blocks)
 {
     constexpr size_t N = sizeof...(ComponentTs);
 
-    const int32_t tid = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x) /
+    // (block_idx of num_blocks: blockIdx.x of gridDim.x in a launch of its own,
+    // the member's share of the grid in a grouped launch)
+    const int32_t tid = (int32_t)(block_idx * blockDim.x + threadIdx.x) /
         threads_per_invocation;
-    const int32_t stride = (int32_t)(gridDim.x * blockDim.x) /
+    const int32_t stride = (int32_t)(num_blocks * blockDim.x) /
         threads_per_invocation;
 
     // The matched tables form ONE index space (rows_before = rows of the tables
@@ -327,6 +332,17 @@ MADRONA_DEVICE inline void pforRowSnapshot(EcsState *S, PforRowSync *sync,
 template <auto Fn>
 inline constexpr unsigned systemWavesPerSIMD = 0;
 
+// Bytes of static LDS a system uses as scratch (e.g. broadphase::
+// rayGroupScratchBytes for one that calls rayGroupScratch()); 0 = none.  The
+// runtime takes any static LDS of a node's kernel for the marker of a system
+// that can append rows (mwhip::markRowAppender) and keeps such a node out of
+// grouped launches.  A SideBySide member whose kernel carries EXACTLY the bytes
+// declared here has no marker on top of them: it cannot append rows.  Declared
+// like systemWavesPerSIMD; a wrong figure costs the shared launch, not
+// correctness.
+template <auto Fn>
+inline constexpr uint32_t systemScratchLDS = 0;
+
 // ---- a node's body as a __device__ function ----------------------------------
 // Nodes that named the same dependencies and cannot append rows are run side by
 // side in ONE launch (pforGroupKernel below, blockIdx.y = the node): a launch is
@@ -336,11 +352,16 @@ inline constexpr unsigned systemWavesPerSIMD = 0;
 // function (mwhip_node_desc::pfor_body, handed out by the kernel's report mode).
 using PforBodyFn = void (*)(EcsState *, uint32_t, uint32_t, const mwhip_pfor_args *);
 
+// The rows of a node without a row snapshot, for workgroup block_idx of the
+// num_blocks that run the node: what the pointer group (parallelForBody) and
+// the inlined group (pforInlineGroupKernel) share.  (always_inline: with two
+// callers the compiler otherwise keeps a long body out of line, which is what
+// the inlined group exists to avoid.)
 template <typename ContextT, auto Fn, int32_t threads_per_invocation,
           typename... ComponentTs>
-__device__ __attribute__((noinline)) void parallelForBody(
+MADRONA_DEVICE __attribute__((always_inline)) inline void parallelForRows(
     EcsState *S, uint32_t query_offset, uint32_t num_matching_and_flags,
-    const mwhip_pfor_args *query_ptr)
+    const mwhip_pfor_args *query_ptr, uint32_t block_idx, uint32_t num_blocks)
 {
     constexpr size_t N = sizeof...(ComponentTs);
     const uint32_t num_matching = num_matching_and_flags & 0x7FFFFFFFu;
@@ -350,22 +371,27 @@ __device__ __attribute__((noinline)) void parallelForBody(
 
     // (never with a row snapshot: nodes that can append rows are not grouped)
     if (query.num_inline == num_matching) {
+        // the row counts in one batch of loads, ...
         int32_t num_rows[MWHIP_PFOR_MAX_INLINE];
 MADRONA_UNROLL
         for (uint32_t a = 0; a < MWHIP_PFOR_MAX_INLINE; a++) {
             num_rows[a] = a >= num_matching ? 0 :
                 ((const TableHdr *)query.tables[a])->numRows;
         }
+        // ... then ONE copy of the system for all tables: the query lives in
+        // memory here, not in the kernel's arguments, so the loop need not be
+        // unrolled (a kernel that inlines several long bodies stays short)
         int32_t rows_before = 0;
-MADRONA_UNROLL
-        for (uint32_t a = 0; a < MWHIP_PFOR_MAX_INLINE; a++) {
-            if (a < num_matching) {
-                parallelForTable<ContextT, Fn, threads_per_invocation,
-                                 ComponentTs...>(
-                    state_mgr, *(TableHdr *)query.tables[a], query.columns[a],
-                    exclusive_world, num_rows[a], rows_before);
-                rows_before += num_rows[a];
-            }
+#pragma nounroll
+        for (uint32_t a = 0; a < num_matching; a++) {
+            const int32_t rows = a == 0 ? num_rows[0] : a == 1 ? num_rows[1] :
+                a == 2 ? num_rows[2] : num_rows[3];
+            static_assert(MWHIP_PFOR_MAX_INLINE == 4);
+            parallelForTable<ContextT, Fn, threads_per_invocation,
+                             ComponentTs...>(
+                state_mgr, *(TableHdr *)query.tables[a], query.columns[a],
+                exclusive_world, rows, rows_before, block_idx, num_blocks);
+            rows_before += rows;
         }
         return;
     }
@@ -379,9 +405,21 @@ MADRONA_UNROLL
         TableHdr &tbl = S->tables[query_values[0]];
         parallelForTable<ContextT, Fn, threads_per_invocation,
                          ComponentTs...>(
-            state_mgr, tbl, col_indices, exclusive_world, tbl.numRows, 0);
+            state_mgr, tbl, col_indices, exclusive_world, tbl.numRows, 0,
+            block_idx, num_blocks);
         query_values += 1 + N;
     }
+}
+
+template <typename ContextT, auto Fn, int32_t threads_per_invocation,
+          typename... ComponentTs>
+__device__ __attribute__((noinline)) void parallelForBody(
+    EcsState *S, uint32_t query_offset, uint32_t num_matching_and_flags,
+    const mwhip_pfor_args *query_ptr)
+{
+    parallelForRows<ContextT, Fn, threads_per_invocation, ComponentTs...>(
+        S, query_offset, num_matching_and_flags, query_ptr, blockIdx.x,
+        gridDim.x);
 }
 
 // blockIdx.y = member of the group; every member strides over its rows with the
@@ -395,6 +433,80 @@ pforGroupKernel(EcsState *S, const mwhip_pfor_group *group)
     const PforBodyFn body = (PforBodyFn)loadInvariant(&group->body[m]);
     body(S, loadInvariant(&group->query_offset[m]),
          loadInvariant(&group->num_matching_and_flags[m]), &group->query[m]);
+}
+
+// ---- a group whose members the simulator names at compile time ---------------
+// SideBySide<NodeA, NodeB, ...> (below): the group kernel calls every member's
+// body directly, so the compiler inlines it -- no function pointer, and a long
+// body (a lidar, a BVH query) keeps the code it has in a launch of its own.
+// The grid is one-dimensional: member I runs in workgroups
+// [first_workgroup[I], first_workgroup[I] + num_workgroups[I]) and strides over
+// its rows with num_workgroups[I] workgroups, the ones a launch of its own would
+// have had.
+template <typename NodeT> struct InlineGroupMember;
+
+template <typename ContextT, auto Fn, int32_t threads_per_invocation,
+          typename... ComponentTs>
+struct InlineGroupMember<CustomParallelForNode<
+    ContextT, Fn, threads_per_invocation, 1, ComponentTs...>> {
+    using Context = ContextT;
+    static constexpr unsigned wavesPerSIMD = systemWavesPerSIMD<Fn>;
+
+    MADRONA_DEVICE __attribute__((always_inline)) static inline void run(
+        EcsState *S, uint32_t query_offset, uint32_t num_matching_and_flags,
+        const mwhip_pfor_args *query, uint32_t block_idx, uint32_t num_blocks)
+    {
+        parallelForRows<ContextT, Fn, threads_per_invocation, ComponentTs...>(
+            S, query_offset, num_matching_and_flags, query, block_idx,
+            num_blocks);
+    }
+};
+
+// the largest non-zero systemWavesPerSIMD among the members: the smallest
+// register budget any of them asked for (0: none asked)
+template <typename... MemberTs>
+constexpr unsigned inlineGroupWavesPerSIMD()
+{
+    unsigned waves = 0;
+    ((waves = InlineGroupMember<MemberTs>::wavesPerSIMD > waves ?
+          InlineGroupMember<MemberTs>::wavesPerSIMD : waves), ...);
+    return waves;
+}
+
+template <typename MemberT, size_t I>
+MADRONA_DEVICE __attribute__((always_inline)) inline bool inlineGroupRunMember(
+    EcsState *S, const mwhip_pfor_inline_group *group, uint32_t workgroup)
+{
+    const uint32_t first = loadInvariant(&group->first_workgroup[I]);
+    const uint32_t count = loadInvariant(&group->num_workgroups[I]);
+    // (count == 0: the member keeps a launch of its own in this graph)
+    if (workgroup - first >= count) {
+        return false;
+    }
+    InlineGroupMember<MemberT>::run(S, loadInvariant(&group->query_offset[I]),
+        loadInvariant(&group->num_matching_and_flags[I]), &group->query[I],
+        workgroup - first, count);
+    return true;
+}
+
+template <typename... MemberTs, size_t... Is>
+MADRONA_DEVICE inline void inlineGroupDispatch(
+    EcsState *S, const mwhip_pfor_inline_group *group, uint32_t workgroup,
+    std::index_sequence<Is...>)
+{
+    (void)(inlineGroupRunMember<MemberTs, Is>(S, group, workgroup) || ...);
+}
+
+template <typename... MemberTs>
+__global__ void __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(inlineGroupWavesPerSIMD<MemberTs...>())))
+pforInlineGroupKernel(EcsState *S, const mwhip_pfor_inline_group *group)
+{
+    static_assert(sizeof...(MemberTs) >= 2 &&
+                  sizeof...(MemberTs) <= MWHIP_PFOR_GROUP_MAX);
+    TraceScope trace_scope(S);
+    inlineGroupDispatch<MemberTs...>(S, group, blockIdx.x,
+        std::index_sequence_for<MemberTs...>());
 }
 
 template <typename ContextT, auto Fn, int32_t threads_per_invocation,
@@ -443,7 +555,8 @@ MADRONA_UNROLL
                 parallelForTable<ContextT, Fn, threads_per_invocation,
                                  ComponentTs...>(
                     state_mgr, *(TableHdr *)query.tables[a], query.columns[a],
-                    exclusive_world, num_rows[a], rows_before);
+                    exclusive_world, num_rows[a], rows_before, blockIdx.x,
+                    gridDim.x);
                 rows_before += num_rows[a];
             }
         }
@@ -468,7 +581,8 @@ MADRONA_UNROLL
         parallelForTable<ContextT, Fn, threads_per_invocation,
                          ComponentTs...>(
             state_mgr, tbl, col_indices, exclusive_world,
-            query.row_sync != nullptr ? pfor_snapshot_rows[a] : tbl.numRows, 0);
+            query.row_sync != nullptr ? pfor_snapshot_rows[a] : tbl.numRows, 0,
+            blockIdx.x, gridDim.x);
         query_values += 1 + N;
     }
 }
@@ -764,6 +878,21 @@ CustomParallelForNode<ContextT, Fn, threads_per_invocation,
     TaskGraph::Builder &builder,
     Span<const TaskGraph::NodeID> dependencies)
 {
+    return addToGraphAsMember(builder, dependencies, nullptr, 0);
+}
+
+template <typename ContextT, auto Fn,
+          int32_t threads_per_invocation,
+          int32_t items_per_invocation,
+          typename... ComponentTs>
+MADRONA_HOST_API TaskGraph::NodeID
+CustomParallelForNode<ContextT, Fn, threads_per_invocation,
+                      items_per_invocation, ComponentTs...>::addToGraphAsMember(
+    TaskGraph::Builder &builder,
+    Span<const TaskGraph::NodeID> dependencies,
+    [[maybe_unused]] const void *inline_group_kernel,
+    [[maybe_unused]] uint32_t member_index)
+{
 #if defined(__HIPCC__)
     [[maybe_unused]] auto kernel_stub = [] __host__ () -> const void * {
         if constexpr (items_per_invocation == 1) {
@@ -815,6 +944,15 @@ CustomParallelForNode<ContextT, Fn, threads_per_invocation,
         desc.pfor_body = mwhip_pfor_body(builder.exec(), desc.kernel);
         desc.pfor_group_kernel = group_stub();
         (void)mwhip_set_pfor_group_kernel(builder.exec(), group_stub());
+        if (inline_group_kernel != nullptr) {
+            // named in a SideBySide: the inlined kernel rides in the field of
+            // the pointer group's (which the executor knows as its default),
+            // the other two facts where a node without the bit leaves zero
+            desc.kind |= MWHIP_NODE_INLINE_GROUP;
+            desc.pfor_group_kernel = inline_group_kernel;
+            desc.component_id = member_index;
+            desc.archetype_id = mwhip::systemScratchLDS<Fn>;
+        }
     }
 #endif
 
@@ -837,6 +975,43 @@ CustomParallelForNode<ContextT, Fn, threads_per_invocation,
 #else
     MADRONA_DEVICE_STUB();
 #endif
+}
+
+template <typename... MemberTs>
+MADRONA_HOST_API std::array<TaskGraph::NodeID, sizeof...(MemberTs)>
+SideBySide<MemberTs...>::addToGraph(
+    TaskGraph::Builder &builder,
+    Span<const TaskGraph::NodeID> dependencies)
+{
+    static_assert(sizeof...(MemberTs) >= 2 &&
+                  sizeof...(MemberTs) <= MWHIP_PFOR_GROUP_MAX,
+        "SideBySide: two to MWHIP_PFOR_GROUP_MAX members");
+#if defined(__HIPCC__)
+    static_assert((std::is_same_v<
+        typename mwhip::InlineGroupMember<MemberTs>::Context,
+        typename mwhip::InlineGroupMember<
+            std::tuple_element_t<0, std::tuple<MemberTs...>>>::Context> && ...),
+        "SideBySide: the members run in one ContextT");
+    [[maybe_unused]] auto kernel_stub = [] __host__ () -> const void * {
+        return (const void *)&mwhip::pforInlineGroupKernel<MemberTs...>;
+    };
+#else
+    auto kernel_stub = []() -> const void * { return nullptr; };
+#endif
+
+    // (not under MADRONA_ON_HOST: the device pass instantiates the members'
+    // own kernels through these calls, as Builder::addToGraph does for a node)
+#if MADRONA_ON_HOST
+    const void *kernel = kernel_stub();
+#else
+    const void *kernel = nullptr;
+#endif
+    uint32_t member_index = 0;
+    // (braced: the members are registered left to right)
+    return std::array<TaskGraph::NodeID, sizeof...(MemberTs)> {
+        MemberTs::addToGraphAsMember(builder, dependencies, kernel,
+                                     member_index++)...
+    };
 }
 
 namespace mwhip {

@@ -11,6 +11,10 @@ def short(name):
     m = re.search(r"parallelForKernelIN\d+(\w+?)6EngineETnDaXadL_ZNS\d_\d+(\w+?System)", name)
     if m:
         return f"parallelForKernel<{m.group(1)}::{m.group(2)}>"
+    if "pforInlineGroupKernel" in name:
+        # (mangled or demangled: the members' systems, in the kernel's order)
+        members = re.findall(r"(?:\d+|::)([A-Za-z]+System)(?=E|\(|,)", name)
+        return "pforInlineGroupKernel<" + " | ".join(dict.fromkeys(members)) + ">"
     name = re.sub(r"madrona::mwhip::\(anonymous namespace\)::", "mwhip::", name)
     name = re.sub(r"\(anonymous namespace\)::", "", name)
     return re.sub(r"\(.*", "", name)[:80]

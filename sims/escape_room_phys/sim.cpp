@@ -1298,6 +1298,11 @@ template <> inline constexpr unsigned
 // 439 spilled dwords, profiles/r06_grabq_variants.jsonl)
 template <> inline constexpr unsigned
     madrona::mwhip::systemWavesPerSIMD<escphys::grabQuerySystem> = 4;
+// (the lidar's only static LDS is the ray groups' scratch: it cannot append
+// rows and may share a launch, SideBySide below)
+template <> inline constexpr uint32_t
+    madrona::mwhip::systemScratchLDS<escphys::lidarSystem> =
+        madrona::phys::broadphase::rayGroupScratchBytes;
 #endif
 namespace escphys {
 #endif
@@ -1326,7 +1331,11 @@ void Sim::setupTasks(TaskGraphManager &taskgraph_mgr, const Config &)
 #endif
 
 #ifdef SIM_WAVE_API
-    // the grab queries test a BVH leaf per lane
+    // the grab queries test a BVH leaf per lane.  (Not in a SideBySide with
+    // movementSystem: at 8192 worlds their 4096 wavefronts take every place on
+    // the chip, so movement's workgroups wait for a place instead of riding
+    // along -- the shared launch measured 45-52 us against 25 + 6 apart,
+    // DESIGN.md section 34.)
     auto grab_query_sys = builder.addToGraph<CustomParallelForNode<Engine,
         grabQuerySystem, ESCPHYS_GRAB_QUERY_LANES, 1,
             LevelState
@@ -1425,6 +1434,29 @@ void Sim::setupTasks(TaskGraphManager &taskgraph_mgr, const Config &)
     auto post_reset_broadphase =
         PhysicsSystem::setupBroadphaseTasks(builder, {compact_buttons});
 
+#ifdef SIM_WAVE_API
+    // (beside one another: both only read; the observations' 16 K rows ride in
+    // the launch of the lidar's 512 K rays)
+    auto [collect_obs, lidar] = SideBySide<
+        ParallelForNode<Engine,
+            collectObservationsSystem,
+                Position,
+                Rotation,
+                Progress,
+                GrabState,
+                OtherAgents,
+                SelfObservation,
+                PartnerObservation,
+                RoomEntityObservations,
+                DoorObservation
+            >,
+        CustomParallelForNode<Engine,
+            lidarSystem, 32, 1,
+                Entity,
+                Lidar
+            >
+        >::addToGraph(builder, {post_reset_broadphase});
+#else
     auto collect_obs = builder.addToGraph<ParallelForNode<Engine,
         collectObservationsSystem,
             Position,
@@ -1448,6 +1480,7 @@ void Sim::setupTasks(TaskGraphManager &taskgraph_mgr, const Config &)
             Entity,
             Lidar
         >>({post_reset_broadphase});      // (beside the observations: both only read)
+#endif
 
     (void)collect_obs;
     (void)lidar;

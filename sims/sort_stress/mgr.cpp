@@ -26,7 +26,8 @@ struct SimTraits {
                              (args.flags >> 4) & 1u,
                              (args.flags >> 5) & 1u,
                              (args.flags >> 6) & 1u,
-                             (args.flags >> 7) & 1u };
+                             (args.flags >> 7) & 1u,
+                             (args.flags >> 8) & 7u };
     }
 
     static void makeInits(const SimCreateArgs &, Sim::WorldInit *) {}

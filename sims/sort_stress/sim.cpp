@@ -44,6 +44,9 @@ void Sim::registerTypes(ECSRegistry &registry, const Config &cfg)
     if (cfg.exportVec3 != 0) {
         registry.exportColumn<Item, Vec3>((uint32_t)ExportID::ItemVec3);
     }
+    if (cfg.groupCase != 0) {
+        registry.registerArchetype<Idle>();
+    }
 #endif
 }
 
@@ -221,6 +224,55 @@ inline void siblingOtherSystem(Engine &, Blob20 &b)
 }
 
 #ifdef MADRONA_GPU_MODE
+// ---- groups named at compile time (Config::groupCase) ------------------------
+// SideBySide groups behind the step's last node; what has to come of each:
+//   1  idle | blob         one member's table (Idle) has no rows: one launch
+//   2  churnTag | blob     with one world churnTag has ONE row: one launch
+//   3  blob | wide32 | quad64   1, 32 and 64 lanes per row: one launch
+//   4  siblingWrite | siblingRead   clash on Quad: two launches, in this order
+//   5  appender | blob     appender can append rows (it never does): its own
+//                          launch, and blob alone keeps its own as well
+inline void groupIdleSystem(Engine &, Key &key)
+{
+    key.v += 1u;
+}
+
+inline void groupBlobSystem(Engine &, Blob20 &b)
+{
+    b.v[3] = b.v[3] * 3u + 1u;
+}
+
+inline void groupChurnTagSystem(Engine &, Churn &churn)
+{
+    churn.scratchSum ^= 0x5A5A0000u + churn.step;
+}
+
+// lane l of 32 owns Wide::v[l]
+inline void groupWide32System(Engine &, Wide &w)
+{
+    const uint32_t lane = threadIdx.x % 32u;
+    w.v[lane] = w.v[lane] * 0.5f + (float)lane;
+}
+
+// lanes 0 .. 3 of 64 own Quad::v[l]
+inline void groupQuad64System(Engine &, Quad &q)
+{
+    const uint32_t lane = threadIdx.x % 64u;
+    if (lane < 4u) {
+        q.v[lane] = q.v[lane] * 0.25f + (float)lane;
+    }
+}
+
+// (carries the row appender's marker; no world reaches step 0xFFFFFFFF)
+inline void groupAppenderSystem(Engine &ctx, Churn &churn)
+{
+    if (churn.step == 0xFFFFFFFFu) {
+        Loc loc = ctx.makeTemporary<Scratch>();
+        ctx.get<Key>(loc).v = 0u;
+    }
+    churn.scratchSum += 7u;
+}
+
 // ---- shape-controlled sort tests (Config::plan) ----------------------------
 static inline uint32_t mixBits(uint32_t x)
 {
@@ -566,6 +618,37 @@ void Sim::setupTasks(TaskGraphManager &taskgraph_mgr, const Config &cfg)
         builder.addToGraph<ParallelForNode<Engine,
             siblingOtherSystem, Blob20>>({reset_tmp});
     }
+
+#ifdef MADRONA_GPU_MODE
+    using BlobNode = ParallelForNode<Engine, groupBlobSystem, Blob20>;
+    switch (cfg.groupCase) {
+    case 1:
+        SideBySide<ParallelForNode<Engine, groupIdleSystem, Key>,
+                   BlobNode>::addToGraph(builder, {reset_tmp});
+        break;
+    case 2:
+        SideBySide<ParallelForNode<Engine, groupChurnTagSystem, Churn>,
+                   BlobNode>::addToGraph(builder, {reset_tmp});
+        break;
+    case 3:
+        SideBySide<BlobNode,
+                   CustomParallelForNode<Engine, groupWide32System, 32, 1, Wide>,
+                   CustomParallelForNode<Engine, groupQuad64System, 64, 1, Quad>
+                  >::addToGraph(builder, {reset_tmp});
+        break;
+    case 4:
+        SideBySide<ParallelForNode<Engine, siblingWriteSystem, Quad>,
+                   ParallelForNode<Engine, siblingReadSystem, Quad, Vec3>
+                  >::addToGraph(builder, {reset_tmp});
+        break;
+    case 5:
+        SideBySide<ParallelForNode<Engine, groupAppenderSystem, Churn>,
+                   BlobNode>::addToGraph(builder, {reset_tmp});
+        break;
+    default:
+        break;
+    }
+#endif
 
 #ifdef MADRONA_GPU_MODE
     {

@@ -130,6 +130,9 @@ struct Reuse2 : public madrona::Archetype<Key, Pair> {};
 struct Reuse3 : public madrona::Archetype<Key, Pair> {};
 struct Reuse4 : public madrona::Archetype<Key, Pair> {};
 
+// Config::groupCase: a table that never holds a row
+struct Idle : public madrona::Archetype<Key> {};
+
 class Engine;
 
 struct Sim : public madrona::WorldBase {
@@ -174,6 +177,11 @@ struct Sim : public madrona::WorldBase {
         // OrderedRows::Reuse; the reference build of the same plan uses plain
         // makeEntity / destroyEntity.
         uint32_t reusePlan;
+        // 1 .. 5 (HIP backend only): groups named at compile time
+        // (madrona::SideBySide) behind the step's last node, one per value --
+        // what the runtime must do with them is in sim.cpp, next to the
+        // groupCase systems (tests/test_inline_group_fallback_gpu.py)
+        uint32_t groupCase;
     };
 
     struct WorldInit {};

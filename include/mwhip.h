@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded() and mwhip_digest_*() / mwhip_set_step_digest() (a per-world hash of chosen columns computed on the device) and mwhip_view_*() / mwhip_set_step_view() (padded per-world tensors of a table's columns) and mwhip_write_*() / mwhip_set_step_write() (padded per-world tensors scattered into a table's columns) and mwhip_reduce_term / mwhip_reduce_*() / mwhip_set_step_reduce() (per-world sums, extrema, counts and alarms of a table's columns) and mwhip_gather_source / mwhip_gather_*() / mwhip_set_step_gather() (the cells of the entities a run of handles in device memory names) and mwhip_scatter_*() / mwhip_set_step_scatter() (cells written into the entities such a run of handles names, the highest index winning among duplicates) and mwhip_rays_desc / mwhip_ray_args / mwhip_set_ray_kernel() / mwhip_rays_*() / mwhip_set_step_rays() (tensors of rays cast through the worlds' broadphase BVHs by a kernel the simulator's code object registers) and MWHIP_NODE_CARRIED / mwhip_broadphase_carry_stats() (launches a steady replay leaves out, a bit of mwhip_node_desc::kind that earlier libraries never set); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
+#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded() and mwhip_digest_*() / mwhip_set_step_digest() (a per-world hash of chosen columns computed on the device) and mwhip_view_*() / mwhip_set_step_view() (padded per-world tensors of a table's columns) and mwhip_write_*() / mwhip_set_step_write() (padded per-world tensors scattered into a table's columns) and mwhip_reduce_term / mwhip_reduce_*() / mwhip_set_step_reduce() (per-world sums, extrema, counts and alarms of a table's columns) and mwhip_gather_source / mwhip_gather_*() / mwhip_set_step_gather() (the cells of the entities a run of handles in device memory names) and mwhip_scatter_*() / mwhip_set_step_scatter() (cells written into the entities such a run of handles names, the highest index winning among duplicates) and mwhip_rays_desc / mwhip_ray_args / mwhip_set_ray_kernel() / mwhip_rays_*() / mwhip_set_step_rays() (tensors of rays cast through the worlds' broadphase BVHs by a kernel the simulator's code object registers) and mwhip_boxes_desc / mwhip_box_args / mwhip_set_box_kernel() / mwhip_boxes_*() / mwhip_set_step_boxes() (tensors of boxes tested through the same BVHs, the whole list of each box's entities, by a second kernel the simulator's code object registers) and MWHIP_NODE_CARRIED / mwhip_broadphase_carry_stats() (launches a steady replay leaves out, a bit of mwhip_node_desc::kind that earlier libraries never set); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
 
 typedef struct mwhip_exec mwhip_exec; /* opaque; == MWCudaExecutor::Impl */
 
@@ -1351,6 +1351,135 @@ int mwhip_rays_compute(mwhip_exec *exec, uint64_t rays);
 int mwhip_rays_compute_async(mwhip_exec *exec, uint64_t rays);
 void *mwhip_rays_buffer(mwhip_exec *exec, uint64_t rays, uint32_t which, uint64_t *bytes_out);
 int mwhip_set_step_rays(mwhip_exec *exec, uint64_t rays, int on);
+
+/* Box queries (added under ABI 9): B = F x G boxes -- F bundles of G >= 1 boxes
+ * that share a world and a centre -- tested through the worlds' broadphase BVHs
+ * by one kernel, the batched form of PhysicsSystem::findEntitiesWithinAABB
+ * (<madrona/physics.hpp>): per box the WHOLE list of the entities that call
+ * reports, in the order it reports them (madrona_amd/box_ref.py
+ * is the same definition in numpy).  Box b = f * G + g is box g of bundle f:
+ *     pMin = centre[f] + lo[b],  pMax = centre[f] + hi[b]      (float32)
+ * INPUTS.  world, count and centre are each either a buffer the query owns or a
+ * SOURCE of the caller's, a mwhip_ray_source with a ray query's rules (record k
+ * at src + k * record_bytes + first_byte, multiples of 4, read on the device
+ * when the kernel runs, in place while the query exists).  Owned buffers are
+ * 256-byte aligned and zero at creation: every box starts empty, and with an
+ * owned centre lo and hi are absolute corners.
+ *   world[f]    int32 per bundle.  bundles_per_world > 0 replaces it by the rule
+ *               world = f / bundles_per_world: desc.world is then ignored and no
+ *               world buffer is owned.
+ *   count[w]    optional int32 per WORLD, only with bundles_per_world > 0:
+ *               bundle f with f % bundles_per_world >= count[world] is SKIPPED.
+ *   centre[f]   3 floats per bundle (possibly inside a wider record).
+ *   lo[b], hi[b]  3 floats per box each, always owned.
+ * OUTPUTS, owned, every one rewritten in full by every compute:
+ *   status[b]   int32: MWHIP_BOXES_OK 0, MWHIP_BOXES_SKIPPED -1,
+ *               MWHIP_BOXES_BAD_WORLD -2 (world not in [0, numWorlds)),
+ *               MWHIP_BOXES_BAD_BOX -3 (a non-finite component of centre, lo, hi
+ *               or of a sum, or pMin > pMax on an axis).  Checked in that order:
+ *               world, count, centre (per bundle), then per box.  Nothing behind
+ *               a failed check is read.
+ *   count[b]    int32: how many entities findEntitiesWithinAABB(ctx of world,
+ *               box, fn) reports; NOT capped by max_hits; 0 unless OK.
+ *   hits[b][k]  k < max_hits, 8 bytes each, Entity { uint32 gen; int32 id }: the
+ *               first min(count, max_hits) entities in report order,
+ *               Entity::none() behind them: the buffer is a valid
+ *               mwhip_gather_source of B x max_hits handles, record_bytes 8.
+ * A box sees the tree as the LAST BROADPHASE PASS left it and the bodies' poses
+ * as they are now, the precondition of a simulator's own node that calls
+ * findEntitiesWithinAABB.  A world whose tree NO broadphase pass has built yet
+ * (numNodes() == 0) gives OK with count 0, its tree untouched.  While a rebuild
+ * of a built tree is pending the old tree is walked, as findEntitiesWithinAABB
+ * does.
+ *
+ * THE KERNEL lives in the simulator's code object (phys_impl/box_query.inl):
+ * PhysicsSystem::setupBroadphaseTasks hands its host stub over with
+ * mwhip_set_box_kernel (NULL is ignored).  Its single argument is a
+ * mwhip_box_args by value whose plans (mwhip_box_plan, device-resident) the
+ * runtime fills.  Two mappings that leave the same words.  Cooperative (the
+ * default): a group of 32 lanes, two per wavefront, owns a chunk of up to 32
+ * boxes of ONE bundle and enumerates the tree's leaves in traversal order, 32
+ * per window, sharing the box-independent half of the hull test.  Packed
+ * (MWHIP_BOXES_PACKED in desc.flags): a box per lane through plain
+ * findEntitiesWithinAABB.  items[p] counts wavefronts either way.
+ *
+ * mwhip_boxes_buffer: device address and size of owned buffer `which`
+ * (MWHIP_BOXES_BUF_*); NULL (-2) for world / centre when a source was given (or
+ * bundles_per_world > 0), NULL (-3) for an unknown handle.
+ * mwhip_set_step_boxes(on != 0): every replay of every STEP graph recomputes the
+ * query directly behind the step ray queries and in front of the step gathers:
+ * centres and counts may be a step view's of the same replay, a step gather over
+ * `hits` sees this replay's hits, an output ring over count or hits records
+ * [K]...  Up to MWHIP_MAX_STEP_BOXES, ONE launch for all, listed by
+ * mwhip_profile as "boxes" with role "boxes"; none when none is set.  Changing
+ * the set waits for the stream and rebuilds the launch graphs; destroying a step
+ * query unsets it.  Box queries are derived state: snapshots do not save them.
+ * Errors (non-zero, text in mwhip_last_error(), nothing changed or allocated):
+ * -3 for an unknown handle or one of another executor (also with a null
+ * executor); -2 for no registered kernel ("this simulator registered no box
+ * kernel"), num_bundles == 0, boxes_per_bundle == 0, max_hits == 0, B x
+ * max_hits > 2^31 - 1, an unknown flag, a bad source (as for rays), a count
+ * source without bundles_per_world, a fifth step query; -10 for buffers that
+ * cannot be allocated.
+ * (No reference counterpart.) */
+#define MWHIP_MAX_STEP_BOXES 4
+#define MWHIP_BOXES_OK 0
+#define MWHIP_BOXES_SKIPPED (-1)
+#define MWHIP_BOXES_BAD_WORLD (-2)
+#define MWHIP_BOXES_BAD_BOX (-3)
+#define MWHIP_BOXES_PACKED 1u          /* mwhip_boxes_desc::flags */
+#define MWHIP_BOXES_BUF_WORLD 0u
+#define MWHIP_BOXES_BUF_CENTRE 1u
+#define MWHIP_BOXES_BUF_LO 2u
+#define MWHIP_BOXES_BUF_HI 3u
+#define MWHIP_BOXES_BUF_STATUS 4u
+#define MWHIP_BOXES_BUF_COUNT 5u
+#define MWHIP_BOXES_BUF_HITS 6u
+#define MWHIP_BOXES_NUM_BUFS 7u
+typedef struct mwhip_boxes_desc {
+    uint32_t num_bundles;           /* F */
+    uint32_t boxes_per_bundle;      /* G >= 1 */
+    uint32_t max_hits;              /* K >= 1 */
+    uint32_t bundles_per_world;     /* > 0: world[f] = f / bundles_per_world */
+    uint32_t flags;                 /* MWHIP_BOXES_PACKED */
+    uint32_t pad_;
+    mwhip_ray_source world;         /* src == NULL: an owned buffer */
+    mwhip_ray_source count;         /* src == NULL: no counts */
+    mwhip_ray_source centre;        /* src == NULL: an owned buffer */
+} mwhip_boxes_desc;
+/* what the kernel reads of one query (device-resident, filled by the runtime;
+ * first_byte is already added to the three sources) */
+typedef struct mwhip_box_plan {
+    void *state;                    /* the executor's ecs state on the device */
+    const char *world_src;          /* unused when bundles_per_world > 0 */
+    const char *count_src;          /* NULL: none */
+    const char *centre_src;
+    const float *lo;                /* [B][3] */
+    const float *hi;                /* [B][3] */
+    int32_t *status;                /* [B] */
+    int32_t *count;                 /* [B] */
+    uint32_t *hits;                 /* [B][K][2] */
+    uint32_t world_stride, count_stride, centre_stride;     /* bytes */
+    uint32_t num_bundles, boxes_per_bundle, max_hits, bundles_per_world;
+    uint32_t chunks_per_bundle;     /* ceil(G / 32); 0: packed, a box per lane */
+} mwhip_box_plan;
+/* the kernel's argument, by value: items[p] wavefronts work on plans[p] */
+typedef struct mwhip_box_args {
+    uint32_t num_plans;
+    uint32_t pad_;
+    uint32_t items[MWHIP_MAX_STEP_BOXES];
+    const mwhip_box_plan *plans[MWHIP_MAX_STEP_BOXES];
+} mwhip_box_args;
+/* the simulator's box kernel: __global__ void(mwhip_box_args), 256 threads */
+int mwhip_set_box_kernel(mwhip_exec *exec, const void *kernel);
+int mwhip_boxes_create(mwhip_exec *exec, const mwhip_boxes_desc *desc, uint64_t *boxes_out);
+void mwhip_boxes_destroy(mwhip_exec *exec, uint64_t boxes);
+/* waits for the executor's stream */
+int mwhip_boxes_compute(mwhip_exec *exec, uint64_t boxes);
+/* queued on the executor's stream behind the replays queued so far */
+int mwhip_boxes_compute_async(mwhip_exec *exec, uint64_t boxes);
+void *mwhip_boxes_buffer(mwhip_exec *exec, uint64_t boxes, uint32_t which, uint64_t *bytes_out);
+int mwhip_set_step_boxes(mwhip_exec *exec, uint64_t boxes, int on);
 
 #ifdef __cplusplus
 }

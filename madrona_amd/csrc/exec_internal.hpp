@@ -8,7 +8,8 @@
 // world_reduce.hip: per-world reductions of a table's columns;
 // entity_gather.hip: the cells of the entities a run of handles names;
 // entity_scatter.hip: cells written into those entities; ray_query.hip: rays
-// cast through the worlds' broadphase BVHs by the simulator's kernel).
+// cast through the worlds' broadphase BVHs by the simulator's kernel;
+// box_query.hip: boxes tested through the same BVHs by its second kernel).
 // Not installed.
 #pragma once
 #include "runtime_internal.hpp"
@@ -277,6 +278,7 @@ struct mwhip_reduce_rec;        // (world_reduce.hip)
 struct mwhip_gather_rec;        // (entity_gather.hip)
 struct mwhip_scatter_rec;       // (entity_scatter.hip)
 struct mwhip_rays_rec;          // (ray_query.hip)
+struct mwhip_boxes_rec;         // (box_query.hip)
 
 // What a replay carries besides its task graphs.  Every launch graph is built
 // from it (the input rings, the step writes and the step scatters open a step graph, the rest are tail stages:
@@ -322,6 +324,9 @@ struct ReplayExtras {
     // mwhip_set_step_rays: those every step replay recomputes, in one launch
     // behind the step views and in front of the step gathers
     std::vector<uint64_t> stepRays;
+    // mwhip_set_step_boxes: those every step replay recomputes, in one launch
+    // directly behind the step ray queries
+    std::vector<uint64_t> stepBoxes;
 };
 
 struct mwhip_exec {
@@ -418,6 +423,8 @@ struct mwhip_exec {
     // mwhip_set_ray_kernel: the simulator's rayQueryKernel (null: it has no
     // broadphase, hence no ray queries)
     const void *rayKernel = nullptr;
+    // mwhip_set_box_kernel: the simulator's boxQueryKernel, likewise
+    const void *boxKernel = nullptr;
     void *pforBodyScratch = nullptr;        // 8 bytes: where report mode writes
     // MADRONA_MWHIP_EXEC_CONFIG_FILE (the reference's
     // MADRONA_MWGPU_EXEC_CONFIG_FILE, cuda_exec.cpp:2115-2172): per task-graph
@@ -448,6 +455,7 @@ struct mwhip_exec {
     ExecObjectTable<mwhip_gather_rec> gathers;     // mwhip_gather_create
     ExecObjectTable<mwhip_scatter_rec> scatters;   // mwhip_scatter_create
     ExecObjectTable<mwhip_rays_rec> rays;          // mwhip_rays_create
+    ExecObjectTable<mwhip_boxes_rec> boxes;        // mwhip_boxes_create
 };
 
 // Bumped by what changes device memory or fails without naming an executor
@@ -535,6 +543,14 @@ MWHIP_RT int checkHandleRequest(mwhip_exec *exec, const char *what,
 MWHIP_RT int stepRaysStage(mwhip_exec *exec, const LaunchGraph &lg,
                            std::vector<KernelLaunch> &out);
       // (ray_query.hip)
+// what `who` (rays_create, boxes_create) refuses about a source of `item_bytes`
+// per record
+MWHIP_RT int checkItemSource(const char *who, const char *name, const mwhip_ray_source &source,
+                             uint32_t item_bytes);
+      // (ray_query.hip)
+MWHIP_RT int stepBoxesStage(mwhip_exec *exec, const LaunchGraph &lg,
+                            std::vector<KernelLaunch> &out);
+      // (box_query.hip)
 MWHIP_RT int stepScatterStage(mwhip_exec *exec, const LaunchGraph &lg,
                               std::vector<KernelLaunch> &out);
       // (entity_scatter.hip)

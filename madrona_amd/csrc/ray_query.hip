@@ -74,21 +74,29 @@ int computeRays(mwhip_exec *exec, uint64_t handle, bool wait)
     return finishQueued(exec, queueRays(exec, *rays), wait);
 }
 
-// what create refuses about a source of `item_bytes` per record
 int checkRaySource(const char *name, const mwhip_ray_source &source, uint32_t item_bytes)
+{
+    return checkItemSource("rays_create", name, source, item_bytes);
+}
+
+}
+
+// what a create refuses about a source of `item_bytes` per record (box queries
+// take the same sources: box_query.hip)
+MWHIP_RT int checkItemSource(const char *who, const char *name, const mwhip_ray_source &source,
+                             uint32_t item_bytes)
 {
     if (((uint64_t)source.src & 3ull) != 0ull || source.record_bytes % 4u != 0u ||
             source.first_byte % 4u != 0u) {
-        return fail(-2, "rays_create: %s: src %p, record_bytes %u and first_byte %u must be "
-                    "multiples of 4", name, source.src, source.record_bytes, source.first_byte);
+        return fail(-2, "%s: %s: src %p, record_bytes %u and first_byte %u must be "
+                    "multiples of 4", who, name, source.src, source.record_bytes,
+                    source.first_byte);
     }
     if ((uint64_t)source.first_byte + item_bytes > (uint64_t)source.record_bytes) {
-        return fail(-2, "rays_create: %s: %u bytes from byte %u do not fit a record of %u bytes",
+        return fail(-2, "%s: %s: %u bytes from byte %u do not fit a record of %u bytes", who,
                     name, item_bytes, source.first_byte, source.record_bytes);
     }
     return 0;
-}
-
 }
 
 // Tail stage: the ONE launch that recomputes every step ray query inside a step

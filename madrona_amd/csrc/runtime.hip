@@ -687,6 +687,7 @@ extern "C" void mwhip_destroy(mwhip_exec *exec)
     exec->gathers.clear();
     exec->scatters.clear();
     exec->rays.clear();
+    exec->boxes.clear();
     for (void *p : exec->allocations) {
         (void)hipFree(p);
     }

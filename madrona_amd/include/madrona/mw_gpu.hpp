@@ -177,7 +177,8 @@ friend class MWCudaExecutor;
 namespace detail {
 
 // What MWHipSnapshot, MWHipDigest, MWHipWorldView, MWHipWorldWrite,
-// MWHipWorldReduce, MWHipEntityGather, MWHipEntityScatter and MWHipRayQuery share: the move-only handle
+// MWHipWorldReduce, MWHipEntityGather, MWHipEntityScatter, MWHipRayQuery and
+// MWHipBoxQuery share: the move-only handle
 // of an object that belongs to an executor (mwhip_<kind>_create / _destroy,
 // include/mwhip.h).  Kind: { name, destroy(exec, handle) }.
 template <typename Kind>
@@ -261,6 +262,10 @@ struct EntityScatterKind {
 struct RayQueryKind {
     static constexpr const char *name = "ray query";
     static void destroy(mwhip_exec *exec, uint64_t handle) { mwhip_rays_destroy(exec, handle); }
+};
+struct BoxQueryKind {
+    static constexpr const char *name = "box query";
+    static void destroy(mwhip_exec *exec, uint64_t handle) { mwhip_boxes_destroy(exec, handle); }
 };
 
 }
@@ -684,6 +689,107 @@ private:
 
     uint64_t num_fans_;
     uint64_t num_rays_;
+    int32_t gpu_id_;
+
+friend class MWCudaExecutor;
+};
+
+// B = F x G boxes, F bundles of G boxes that share a world and a centre, tested
+// through the worlds' broadphase BVHs by one kernel of the simulator's code
+// object: per box int32 status (MWHIP_BOXES_OK, _SKIPPED, _BAD_WORLD, _BAD_BOX),
+// int32 count (how many entities PhysicsSystem::findEntitiesWithinAABB reports,
+// not capped) and the first maxHits() of them as Entity handles in report
+// order, Entity::none() behind them.  mwhip_boxes_*, include/mwhip.h, is the
+// exact definition: pMin = centre + lo, pMax = centre + hi; which inputs are
+// owned buffers and which the caller's sources; that a box sees the tree as the
+// last broadphase pass left it and the poses as they are now.  Needs a
+// simulator that sets up a broadphase.  An extension of this backend.  Belongs
+// to the executor that made it and must not outlive it, nor its sources.
+class MWHipBoxQuery : public detail::ExecObject<detail::BoxQueryKind> {
+public:
+    MWHipBoxQuery() : num_bundles_(0), num_boxes_(0), max_hits_(0), gpu_id_(0) {}
+
+    // waits for the executor's stream
+    void compute() { req(mwhip_boxes_compute(exec_, handle_), "compute"); }
+    // queued on the executor's stream behind the replays queued so far
+    void computeAsync() { req(mwhip_boxes_compute_async(exec_, handle_), "computeAsync"); }
+
+    // inputs the query owns: int32 [numBundles()] (no world source, no
+    // bundles_per_world), float [numBundles()][3] (no centre source), float
+    // [numBoxes()][3] twice
+    py::Tensor worldsTensor() const
+    {
+        return tensor(MWHIP_BOXES_BUF_WORLD, py::TensorElementType::Int32, num_bundles_, 0, 0,
+                      "worldsTensor");
+    }
+    py::Tensor centresTensor() const
+    {
+        return tensor(MWHIP_BOXES_BUF_CENTRE, py::TensorElementType::Float32, num_bundles_, 3,
+                      0, "centresTensor");
+    }
+    py::Tensor loTensor() const
+    {
+        return tensor(MWHIP_BOXES_BUF_LO, py::TensorElementType::Float32, num_boxes_, 3, 0,
+                      "loTensor");
+    }
+    py::Tensor hiTensor() const
+    {
+        return tensor(MWHIP_BOXES_BUF_HI, py::TensorElementType::Float32, num_boxes_, 3, 0,
+                      "hiTensor");
+    }
+
+    // outputs: int32 [numBoxes()] twice, int32 [numBoxes()][maxHits()][2]
+    // (gen, id)
+    py::Tensor statusTensor() const
+    {
+        return tensor(MWHIP_BOXES_BUF_STATUS, py::TensorElementType::Int32, num_boxes_, 0, 0,
+                      "statusTensor");
+    }
+    py::Tensor countsTensor() const
+    {
+        return tensor(MWHIP_BOXES_BUF_COUNT, py::TensorElementType::Int32, num_boxes_, 0, 0,
+                      "countsTensor");
+    }
+    py::Tensor hitsTensor() const
+    {
+        return tensor(MWHIP_BOXES_BUF_HITS, py::TensorElementType::Int32, num_boxes_,
+                      (int64_t)max_hits_, 2, "hitsTensor");
+    }
+
+    // the hits as the source of an entity gather or scatter: numBoxes() x
+    // maxHits() handles
+    mwhip_gather_source handleSource() const
+    {
+        void *ptr = mwhip_boxes_buffer(exec_, handle_, MWHIP_BOXES_BUF_HITS, nullptr);
+        req(ptr != nullptr ? 0 : -1, "handleSource");
+        return mwhip_gather_source { ptr, num_boxes_ * max_hits_, 8u, 0u, 1u, 0u };
+    }
+
+    uint64_t numBundles() const { return num_bundles_; }
+    uint64_t numBoxes() const { return num_boxes_; }
+    uint64_t maxHits() const { return max_hits_; }
+
+private:
+    MWHipBoxQuery(mwhip_exec *exec, uint64_t boxes, uint64_t num_bundles, uint64_t num_boxes,
+                  uint64_t max_hits, int32_t gpu_id)
+        : ExecObject(exec, boxes), num_bundles_(num_bundles), num_boxes_(num_boxes),
+          max_hits_(max_hits), gpu_id_(gpu_id)
+    {}
+
+    py::Tensor tensor(uint32_t which, py::TensorElementType type, uint64_t rows,
+                      int64_t inner, int64_t innermost, const char *what) const
+    {
+        void *ptr = mwhip_boxes_buffer(exec_, handle_, which, nullptr);
+        req(ptr != nullptr ? 0 : -1, what);
+        const int64_t dims[3] = { (int64_t)rows, inner, innermost };
+        return py::Tensor(ptr, type,
+                          Span<const int64_t>(dims, innermost != 0 ? 3 : inner != 0 ? 2 : 1),
+                          Optional<int>::make((int)gpu_id_));
+    }
+
+    uint64_t num_bundles_;
+    uint64_t num_boxes_;
+    uint64_t max_hits_;
     int32_t gpu_id_;
 
 friend class MWCudaExecutor;
@@ -1194,6 +1300,29 @@ public:
     {
         req(mwhip_set_step_rays(exec_, rays != nullptr ? rays->handle() : 0, on ? 1 : 0),
             "setStepRays");
+    }
+
+    // desc.num_bundles bundles of desc.boxes_per_bundle boxes through the
+    // worlds' broadphase BVHs, up to desc.max_hits entities listed per box (see
+    // MWHipBoxQuery and mwhip_boxes_desc)
+    MWHipBoxQuery makeBoxQuery(const mwhip_boxes_desc &desc)
+    {
+        uint64_t boxes = 0;
+        req(mwhip_boxes_create(exec_, &desc, &boxes), "makeBoxQuery");
+        return MWHipBoxQuery(exec_, boxes, desc.num_bundles,
+                             (uint64_t)desc.num_bundles * desc.boxes_per_bundle, desc.max_hits,
+                             gpu_id_);
+    }
+
+    // on: every replay of a step graph recomputes `boxes` directly behind its
+    // step ray queries (hence behind its step views, whose slabs and counts it
+    // may read) and in front of its step gathers (which may read the hits), its
+    // pack node and its output rings (up to MWHIP_MAX_STEP_BOXES queries, one
+    // launch for all); off: no longer
+    void setStepBoxes(const MWHipBoxQuery *boxes, bool on)
+    {
+        req(mwhip_set_step_boxes(exec_, boxes != nullptr ? boxes->handle() : 0, on ? 1 : 0),
+            "setStepBoxes");
     }
 
     // Device-resident rings (extensions of this backend, include/mwhip.h).

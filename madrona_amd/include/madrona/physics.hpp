@@ -194,6 +194,15 @@ template <int LANES = 64, typename Fn>
 MADRONA_DEVICE inline Entity findFirstEntityWithinAABBWave(Context &ctx,
                                                            math::AABB aabb,
                                                            Fn &&accept);
+// checkEntityAABBOverlap(ctx, boxes[b], e) for every b < num_boxes whose bit is
+// set in `candidates`, at once (bit b of the result): what does not depend on
+// the query box is computed once.  The bits of num_boxes separate calls.
+template <int MAX_BOXES>
+MADRONA_DEVICE inline uint32_t checkEntityAABBsOverlap(Context &ctx,
+                                                       const math::AABB *boxes,
+                                                       int32_t num_boxes,
+                                                       uint32_t candidates,
+                                                       Entity e);
 #endif
 
 MADRONA_HD inline bool checkEntityAABBOverlap(Context &ctx, math::AABB aabb,

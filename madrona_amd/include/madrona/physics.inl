@@ -1759,6 +1759,8 @@ bvhUpdateKernel(EcsState *S, void *, uint32_t, uint32_t)
 
 // the ray queries' kernel (mwhip_rays_*): rayQueryKernel
 #include <madrona/phys_impl/ray_query.inl>
+// the box queries' kernel (mwhip_boxes_*): boxQueryKernel
+#include <madrona/phys_impl/box_query.inl>
 }
 #endif // __HIPCC__
 
@@ -2497,10 +2499,19 @@ MADRONA_HOST_API inline TaskGraphNodeID setupBroadphaseTasks(
 #else
     auto ray_stub = []() -> const void * { return nullptr; };
 #endif
+#if defined(__HIPCC__)
+    [[maybe_unused]] auto box_stub = [] __host__ () -> const void * {
+        return (const void *)&kernels::boxQueryKernel;
+    };
+#else
+    auto box_stub = []() -> const void * { return nullptr; };
+#endif
 #if MADRONA_ON_HOST
-    // a simulator with a broadphase has ray queries (mwhip_rays_create): the
-    // kernel is in this code object, the runtime launches it
+    // a simulator with a broadphase has ray queries (mwhip_rays_create) and box
+    // queries (mwhip_boxes_create): the kernels are in this code object, the
+    // runtime launches them
     mwhip::check(mwhip_set_ray_kernel(builder.exec(), ray_stub()), "set_ray_kernel");
+    mwhip::check(mwhip_set_box_kernel(builder.exec(), box_stub()), "set_box_kernel");
 #endif
 
     const bool carried = inputs == BroadphaseInputs::CarriedOver;

@@ -149,6 +149,14 @@ class RaysDesc(C.Structure):
                 ("world", RaySource), ("count", RaySource), ("origin", RaySource)]
 
 
+class BoxesDesc(C.Structure):
+    """mwhip_boxes_desc (include/mwhip.h)."""
+    _fields_ = [("num_bundles", C.c_uint32), ("boxes_per_bundle", C.c_uint32),
+                ("max_hits", C.c_uint32), ("bundles_per_world", C.c_uint32),
+                ("flags", C.c_uint32), ("pad_", C.c_uint32),
+                ("world", RaySource), ("count", RaySource), ("centre", RaySource)]
+
+
 class SortStats(C.Structure):
     """mwhip_sort_counters (include/mwhip.h)"""
     _fields_ = [(name, C.c_uint64) for name in
@@ -325,6 +333,19 @@ def runtime_lib() -> C.CDLL:
     lib.mwhip_set_step_rays.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
     lib.mwhip_set_ray_kernel.restype = C.c_int
     lib.mwhip_set_ray_kernel.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mwhip_boxes_create.restype = C.c_int
+    lib.mwhip_boxes_create.argtypes = [C.c_void_p, C.POINTER(BoxesDesc), C.POINTER(C.c_uint64)]
+    lib.mwhip_boxes_destroy.restype = None
+    lib.mwhip_boxes_destroy.argtypes = [C.c_void_p, C.c_uint64]
+    for fn in (lib.mwhip_boxes_compute, lib.mwhip_boxes_compute_async):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_uint64]
+    lib.mwhip_boxes_buffer.restype = C.c_void_p
+    lib.mwhip_boxes_buffer.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
+    lib.mwhip_set_step_boxes.restype = C.c_int
+    lib.mwhip_set_step_boxes.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
+    lib.mwhip_set_box_kernel.restype = C.c_int
+    lib.mwhip_set_box_kernel.argtypes = [C.c_void_p, C.c_void_p]
     return lib
 
 
@@ -346,7 +367,7 @@ class _Checked:
 
 
 class _ExecObject(_Checked):
-    """What Snapshot, StateDigest, WorldView, WorldWrite, WorldReduce, EntityGather, EntityScatter and RayQuery are: something a simulator's
+    """What Snapshot, StateDigest, WorldView, WorldWrite, WorldReduce, EntityGather, EntityScatter, RayQuery and BoxQuery are: something a simulator's
     executor owns, named by `handle` there, kept in one of the simulator's
     lists (`_list`) while it is open.  close() frees it and takes it off the
     list (a snapshot too, which used to stay on it until the simulator closed); Simulator.close() frees the executor and orphans
@@ -1424,7 +1445,7 @@ class RayQuery(_ExecObject):
              "status": 7}
 
     @staticmethod
-    def _source(what: str, source, item_bytes: int):
+    def _source(what: str, source, item_bytes: int, who: str = "ray_query()"):
         """(the tensor to keep alive or None, RaySource) of None, a device
         tensor whose rows are the records, or (ptr, record_bytes, first_byte)"""
         if source is None:
@@ -1435,14 +1456,14 @@ class RayQuery(_ExecObject):
         import torch
 
         if not isinstance(source, torch.Tensor) or not source.is_cuda:
-            raise TypeError(f"ray_query(): {what} is a torch tensor on the device or a "
+            raise TypeError(f"{who}: {what} is a torch tensor on the device or a "
                             "(ptr, record_bytes, first_byte) tuple")
         if source.element_size() != 4 or not source.is_contiguous() or source.dim() < 1:
-            raise TypeError(f"ray_query(): the {what} tensor must be contiguous with 4-byte "
+            raise TypeError(f"{who}: the {what} tensor must be contiguous with 4-byte "
                             f"items, not {source.dtype} {tuple(source.shape)}")
         record = item_bytes if source.dim() == 1 else int(source.shape[-1]) * 4
         if record < item_bytes:
-            raise TypeError(f"ray_query(): rows of {record} bytes are too short for {what}")
+            raise TypeError(f"{who}: rows of {record} bytes are too short for {what}")
         return source, RaySource(source.data_ptr(), record, 0)
 
     def __init__(self, sim: "Simulator", fans: int, rays_per_fan: int, world=None, origin=None,
@@ -1553,6 +1574,153 @@ class RayQuery(_ExecObject):
         self._every_step = bool(on)
 
 
+class BoxQuery(_ExecObject):
+    """B = bundles x boxes_per_bundle boxes tested through the worlds' broadphase
+    BVHs by one kernel: per box the whole list of the entities
+    PhysicsSystem::findEntitiesWithinAABB reports, in the order it reports them
+    (mwhip_boxes_*, include/mwhip.h; madrona_amd/box_ref.py is the exact
+    definition).  The boxes of a bundle share a world and a centre: box b = f *
+    G + g is pMin = centre[f] + lo[b], pMax = centre[f] + hi[b] in float32.
+    Inputs: worlds() int32 [F], centres() float32 [F, 3] (each owned unless a
+    source was given -- a device tensor or (ptr, record_bytes, first_byte),
+    read when the kernel runs and kept in place while the query exists;
+    bundles_per_world > 0 replaces worlds() by world = f // bundles_per_world,
+    and `count`, an int32 per world such as a view's counts, then SKIPS bundles
+    f % bundles_per_world >= count[world]), lo() and hi() float32 [B, 3].  All
+    owned inputs are zero at creation: empty boxes, and with owned centres lo
+    and hi are absolute corners.  Outputs, rewritten in full by every compute:
+    status() int32 [B] (OK 0, SKIPPED -1, BAD_WORLD -2, BAD_BOX -3), counts()
+    int32 [B] (not capped by max_hits, 0 unless OK), hits() int32 [B, K, 2]
+    (gen, id): the first min(count, K) entities, -1, -1 behind them.  All are
+    zero-copy torch tensors over the device buffers; what torch writes into the
+    inputs on its own stream must have landed before a compute or a step reads
+    it (torch.cuda.synchronize()).  A world whose tree no broadphase pass has
+    built yet (before its first step) gives OK with count 0.  A box sees the
+    tree as the last broadphase pass of the step left it and the poses as they
+    are now.  handle_source() is what entity_gather() / entity_scatter() take
+    to go from hits to cells.  packed=True maps a box to a lane through plain
+    findEntitiesWithinAABB instead of a chunk of a bundle to a group of 32
+    lanes; same words.  compute() waits for the executor's stream,
+    compute_async() queues behind the replays queued so far; every_step() makes
+    every replay of a step graph recompute the query behind its step views and
+    ray queries and in front of its step gathers and output rings.  HIP backend
+    only."""
+
+    _kind, _destroy, _list = "box query", "mwhip_boxes_destroy", "_box_queries"
+    OK, SKIPPED, BAD_WORLD, BAD_BOX = 0, -1, -2, -3
+    PACKED = 1
+    _BUFS = {"world": 0, "centre": 1, "lo": 2, "hi": 3, "status": 4, "count": 5, "hits": 6}
+
+    def __init__(self, sim: "Simulator", bundles: int, boxes_per_bundle: int, max_hits: int,
+                 world=None, centre=None, bundles_per_world: int = 0, count=None,
+                 packed: bool = False):
+        self._sim = sim
+        self.num_bundles, self.boxes_per_bundle = int(bundles), int(boxes_per_bundle)
+        self.max_hits = int(max_hits)
+        self.num_boxes = self.num_bundles * self.boxes_per_bundle
+        self.bundles_per_world = int(bundles_per_world)
+        self.packed = bool(packed)
+        self._rt = runtime_lib()
+        self._exec = sim.hip_exec()
+        self._tensors = {}
+        self._every_step = False
+        self.handle = 0
+        desc = BoxesDesc(self.num_bundles, self.boxes_per_bundle, self.max_hits,
+                         self.bundles_per_world, self.PACKED if self.packed else 0, 0)
+        source = lambda what, src, nbytes: RayQuery._source(what, src, nbytes, "box_query()")
+        keep_w, desc.world = source("world", world, 4)
+        keep_c, desc.count = source("count", count, 4)
+        keep_o, desc.centre = source("centre", centre, 12)
+        self._sources = (keep_w, keep_c, keep_o)    # (stay where they are)
+        handle = C.c_uint64(0)
+        self._check(self._rt.mwhip_boxes_create(self._exec, C.byref(desc), C.byref(handle)),
+                    "mwhip_boxes_create")
+        self.handle = int(handle.value)
+        self._owned = {"world": world is None and self.bundles_per_world == 0,
+                       "centre": centre is None}
+
+    def _orphan(self) -> None:
+        super()._orphan()
+        self._tensors = {}
+        self._sources = ()
+
+    _wrap = WorldView._wrap
+
+    def buffer_ptr(self, name: str) -> int:
+        """Device address of owned buffer `name`: world, centre, lo, hi, status,
+        count or hits."""
+        handle = self._live()
+        nbytes = C.c_uint64(0)
+        ptr = self._rt.mwhip_boxes_buffer(self._exec, handle, self._BUFS[name], C.byref(nbytes))
+        if not ptr:
+            raise RuntimeError(f"mwhip_boxes_buffer({name}): "
+                               f"{self._rt.mwhip_last_error().decode()}")
+        return int(ptr)
+
+    def _tensor(self, name, dtype, shape):
+        self._live()
+        if not self._owned.get(name, True):
+            raise RuntimeError(f"this box query owns no {name} buffer: " + (
+                "bundles_per_world gives each bundle its world" if name == "world"
+                and self.bundles_per_world else f"a {name} source was given"))
+        if name not in self._tensors:
+            self._wrap(name, self.buffer_ptr(name), dtype, shape)
+        return self._tensors[name]
+
+    def worlds(self):
+        """int32 [F] (owned: no world source and no bundles_per_world)"""
+        return self._tensor("world", np.int32, (self.num_bundles,))
+
+    def centres(self):
+        """float32 [F, 3] (owned: no centre source)"""
+        return self._tensor("centre", np.float32, (self.num_bundles, 3))
+
+    def lo(self):
+        """float32 [B, 3]: pMin = centre + lo"""
+        return self._tensor("lo", np.float32, (self.num_boxes, 3))
+
+    def hi(self):
+        """float32 [B, 3]: pMax = centre + hi"""
+        return self._tensor("hi", np.float32, (self.num_boxes, 3))
+
+    def status(self):
+        """int32 [B]: OK 0, SKIPPED -1, BAD_WORLD -2, BAD_BOX -3"""
+        return self._tensor("status", np.int32, (self.num_boxes,))
+
+    def counts(self):
+        """int32 [B]: the entities the box holds, not capped by max_hits"""
+        return self._tensor("count", np.int32, (self.num_boxes,))
+
+    def hits(self):
+        """int32 [B, K, 2] (gen, id), -1, -1 behind the first min(count, K)"""
+        return self._tensor("hits", np.int32, (self.num_boxes, self.max_hits, 2))
+
+    def handle_source(self):
+        """The hits as a source of Simulator.entity_gather() / entity_scatter():
+        (ptr, num_records, record_bytes, first_byte, handles_per_record)."""
+        return (self.buffer_ptr("hits"), self.num_boxes * self.max_hits, 8, 0, 1)
+
+    def compute(self) -> "BoxQuery":
+        """Rewrites every output; waits for the executor's stream."""
+        self._check(self._rt.mwhip_boxes_compute(self._exec, self._live()),
+                    "mwhip_boxes_compute")
+        return self
+
+    def compute_async(self) -> None:
+        self._check(self._rt.mwhip_boxes_compute_async(self._exec, self._live()),
+                    "mwhip_boxes_compute_async")
+
+    def every_step(self, on: bool = True) -> None:
+        """Every replay of a step graph recomputes this query (waits for the
+        stream and rebuilds the launch graphs); on=False turns it off again."""
+        handle = self._live()
+        if not on and not self._every_step:
+            return
+        self._check(self._rt.mwhip_set_step_boxes(self._exec, handle, 1 if on else 0),
+                    "mwhip_set_step_boxes")
+        self._every_step = bool(on)
+
+
 class Simulator:
     """One simulator instance behind the C API (either backend)."""
 
@@ -1585,6 +1753,7 @@ class Simulator:
         self._gathers: List["EntityGather"] = []
         self._scatters: List["EntityScatter"] = []
         self._ray_queries: List["RayQuery"] = []
+        self._box_queries: List["BoxQuery"] = []
         self._tensor_info: Dict[str, Tuple[int, np.dtype, Tuple[int, ...], bool]] = {}
         for i in range(self.lib.sim_num_tensors(self.handle)):
             info = SimTensorInfo()
@@ -1603,11 +1772,11 @@ class Simulator:
         if self.handle:
             # sim_destroy frees the executor and with it its snapshots, digests,
             # world views, world writes, world reduces, entity gathers,
-            # entity scatters and ray queries, and
+            # entity scatters, ray queries and box queries, and
             # forgets its output rings (the trajectories keep their tensors)
             for open_ones in (self._snapshots, self._trajectories, self._digests, self._views,
                               self._writes, self._reduces, self._gathers, self._scatters,
-                              self._ray_queries):
+                              self._ray_queries, self._box_queries):
                 for obj in open_ones:
                     obj._orphan()
                 open_ones.clear()
@@ -1855,6 +2024,26 @@ class Simulator:
             raise RuntimeError(f"ray queries need the HIP backend, this is {self.backend!r}")
         query = RayQuery(self, fans, rays_per_fan, world, origin, fans_per_world, count)
         self._ray_queries.append(query)
+        return query
+
+    def box_query(self, bundles: int, boxes_per_bundle: int, max_hits: int, world=None,
+                  centre=None, bundles_per_world: int = 0, count=None,
+                  packed: bool = False) -> "BoxQuery":
+        """A BoxQuery of `bundles` bundles of `boxes_per_bundle` boxes through
+        the worlds' broadphase BVHs, up to `max_hits` entities listed per box
+        (HIP backend, a simulator with a broadphase).  `world` (int32 per
+        bundle), `centre` (3 floats per bundle) and `count` (int32 per world,
+        with bundles_per_world) are device tensors whose rows are the records
+        or (ptr, record_bytes, first_byte); None: world and centre are buffers
+        the query owns (worlds(), centres()).  bundles_per_world > 0: world = f
+        // bundles_per_world, the shape of a world view's slab.  packed: a box
+        per lane instead of a chunk of a bundle per group of 32 lanes (same
+        words).  Simulator.close() frees what is left open."""
+        if self.backend != "hip":
+            raise RuntimeError(f"box queries need the HIP backend, this is {self.backend!r}")
+        query = BoxQuery(self, bundles, boxes_per_bundle, max_hits, world, centre,
+                         bundles_per_world, count, packed)
+        self._box_queries.append(query)
         return query
 
     def record(self, names: List[str], steps: int, on_render: bool = False) -> "Trajectory":

@@ -13,8 +13,9 @@
 // A query owns a device-resident plan and ONE allocation with its owned inputs
 // (world and centre unless a source was given; lo and hi always) and its outputs
 // (status, count, hits), 256-byte aligned each.  Sources are read on the device
-// when the kernel runs, as a ray query's.
-#include "exec_internal.hpp"
+// when the kernel runs, as a ray query's.  What the two share is in
+// tree_query.hpp.
+#include "tree_query.hpp"
 
 namespace {
 
@@ -23,22 +24,10 @@ constexpr uint32_t kBoxWaves = kBoxThreads / 64u;
 
 }
 
-struct mwhip_boxes_rec {
-    uint64_t handle = 0;
+struct mwhip_boxes_rec : TreeQueryRec<mwhip_box_plan, MWHIP_BOXES_NUM_BUFS> {
     uint32_t numBundles = 0;
     uint32_t numBoxes = 0;
     uint32_t maxHits = 0;
-    uint32_t items = 0;         // wavefront work items
-    char *bufs[MWHIP_BOXES_NUM_BUFS] = {};      // into bufDev; null: not owned
-    uint64_t bytes[MWHIP_BOXES_NUM_BUFS] = {};
-    mwhip_box_plan *planDev = nullptr;
-    char *bufDev = nullptr;
-
-    ~mwhip_boxes_rec()
-    {
-        if (planDev != nullptr) (void)hipFree(planDev);
-        if (bufDev != nullptr) (void)hipFree(bufDev);
-    }
 };
 
 namespace {
@@ -53,28 +42,18 @@ mwhip_boxes_rec *findBoxes(mwhip_exec *exec, uint64_t handle)
 // workgroups per CU at a time: DESIGN.md §35)
 dim3 boxGrid(mwhip_exec *exec, uint32_t items)
 {
-    const uint32_t blocks = (items + kBoxWaves - 1u) / kBoxWaves;
-    return dim3(std::max(std::min(blocks, std::max(exec->numCUs, 1u) * 8u), 1u), 1, 1);
+    return waveGrid(exec, items, kBoxWaves, 8u);
 }
 
 int queueBoxes(mwhip_exec *exec, mwhip_boxes_rec &boxes)
 {
-    mwhip_box_args args {};
-    args.num_plans = 1;
-    args.items[0] = boxes.items;
-    args.plans[0] = boxes.planDev;
-    void *argv[] = { &args };
-    HIPCHK(hipLaunchKernel(exec->boxKernel, boxGrid(exec, boxes.items), dim3(kBoxThreads), argv,
-                           0, exec->stream));
-    return 0;
+    return queueBatch(exec, exec->boxKernel, boxGrid(exec, boxes.items), kBoxThreads,
+                      singleBatch<mwhip_box_args>(boxes));
 }
 
 int computeBoxes(mwhip_exec *exec, uint64_t handle, bool wait)
 {
-    mwhip_boxes_rec *boxes = findBoxes(exec, handle);
-    if (boxes == nullptr) return unknownObject("box query", handle);
-    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
-    return finishQueued(exec, queueBoxes(exec, *boxes), wait);
+    return computeObject(exec, findBoxes(exec, handle), "box query", handle, wait, queueBoxes);
 }
 
 }
@@ -90,34 +69,18 @@ MWHIP_RT int stepBoxesStage(mwhip_exec *exec, const LaunchGraph &lg,
 {
     if (lg.isRender || exec->boxKernel == nullptr) return 0;
     mwhip_box_args args {};
-    uint32_t items = 0;
     double bytes = 0;
-    for (uint64_t handle : exec->extras.stepBoxes) {
-        mwhip_boxes_rec *boxes = findBoxes(exec, handle);
-        if (boxes == nullptr || args.num_plans >= MWHIP_MAX_STEP_BOXES) continue;
-        args.items[args.num_plans] = boxes->items;
-        args.plans[args.num_plans] = boxes->planDev;
-        args.num_plans += 1;
-        items += boxes->items;
-        // written: status, count and every hit slot; read: lo, hi, and per
-        // bundle world and centre (the trees' and the bodies' bytes depend on
-        // the boxes and are not counted)
-        bytes += (double)boxes->numBoxes * (8.0 + 8.0 * (double)boxes->maxHits + 24.0) +
-            (double)boxes->numBundles * 16.0;
-    }
+    const uint32_t items = collectStepBatch(
+        exec->extras.stepBoxes, exec->boxes, args, [&](const mwhip_boxes_rec &boxes) {
+            // written: status, count and every hit slot; read: lo, hi, and per
+            // bundle world and centre (the trees' and the bodies' bytes depend
+            // on the boxes and are not counted)
+            bytes += (double)boxes.numBoxes * (8.0 + 8.0 * (double)boxes.maxHits + 24.0) +
+                (double)boxes.numBundles * 16.0;
+        });
     if (args.num_plans == 0) return 0;
-
-    KernelLaunch k;
-    static_assert(sizeof(mwhip_box_args) <= sizeof(k.argStorage));
-    k.fn = exec->boxKernel;
-    k.grid = boxGrid(exec, items);
-    k.block = dim3(kBoxThreads, 1, 1);
-    k.setArgs(args);
-    k.name = "boxes";
-    k.role = "boxes";
-    k.kind = MWHIP_NODE_RECYCLE;
-    k.fixedBytes = bytes;
-    out.push_back(k);
+    out.push_back(stageLaunch(exec->boxKernel, boxGrid(exec, items), kBoxThreads, args, "boxes",
+                              "boxes", bytes));
     return 0;
 }
 
@@ -157,19 +120,12 @@ extern "C" int mwhip_boxes_create(mwhip_exec *exec, const mwhip_boxes_desc *desc
     const bool by_rule = desc->bundles_per_world != 0u;
     const bool own_world = !by_rule && desc->world.src == nullptr;
     const bool own_centre = desc->centre.src == nullptr;
-    int rc = 0;
-    if (!by_rule && !own_world) rc = checkItemSource("boxes_create", "world", desc->world, 4u);
-    if (rc == 0 && desc->count.src != nullptr) {
-        if (!by_rule) {
-            return fail(-2, "boxes_create: a count source needs bundles_per_world > 0");
-        }
-        rc = checkItemSource("boxes_create", "count", desc->count, 4u);
-    }
-    if (rc == 0 && !own_centre) rc = checkItemSource("boxes_create", "centre", desc->centre, 12u);
+    const int rc = checkGroupSources("boxes_create", by_rule, "bundles_per_world", desc->world,
+                                     desc->count, "centre", desc->centre);
     if (rc != 0) return rc;
 
     HIPCHK(hipSetDevice(exec->cfg.gpu_id));
-    std::unique_ptr<mwhip_boxes_rec> boxes(new mwhip_boxes_rec {});
+    std::unique_ptr<mwhip_boxes_rec> boxes(new mwhip_boxes_rec());
     const uint32_t F = desc->num_bundles, G = desc->boxes_per_bundle, K = desc->max_hits;
     const uint32_t B = (uint32_t)num_boxes;
     boxes->numBundles = F;
@@ -189,20 +145,9 @@ extern "C" int mwhip_boxes_create(mwhip_exec *exec, const mwhip_boxes_desc *desc
     boxes->bytes[MWHIP_BOXES_BUF_STATUS] = (uint64_t)B * 4ull;
     boxes->bytes[MWHIP_BOXES_BUF_COUNT] = (uint64_t)B * 4ull;
     boxes->bytes[MWHIP_BOXES_BUF_HITS] = (uint64_t)B * K * 8ull;
-    uint64_t offsets[MWHIP_BOXES_NUM_BUFS];
     uint64_t total = 0;
-    for (uint32_t b = 0; b < MWHIP_BOXES_NUM_BUFS; b++) {
-        offsets[b] = total;
-        total += (boxes->bytes[b] + 255ull) & ~255ull;
-    }
-
-    bool ok = hipMalloc((void **)&boxes->bufDev, total) == hipSuccess &&
-        hipMalloc((void **)&boxes->planDev, sizeof(mwhip_box_plan)) == hipSuccess &&
-        hipMemset(boxes->bufDev, 0, total) == hipSuccess;
+    bool ok = allocQueryBuffers(*boxes, &total);
     if (ok) {
-        for (uint32_t b = 0; b < MWHIP_BOXES_NUM_BUFS; b++) {
-            if (boxes->bytes[b] != 0ull) boxes->bufs[b] = boxes->bufDev + offsets[b];
-        }
         // the outputs as a compute leaves a query whose boxes met nothing
         ok = hipMemset(boxes->bufs[MWHIP_BOXES_BUF_HITS], 0xFF,
                        boxes->bytes[MWHIP_BOXES_BUF_HITS]) == hipSuccess;
@@ -210,24 +155,13 @@ extern "C" int mwhip_boxes_create(mwhip_exec *exec, const mwhip_boxes_desc *desc
     if (ok) {
         mwhip_box_plan plan {};
         plan.state = exec->stateDev;
-        if (own_world) {
-            plan.world_src = boxes->bufs[MWHIP_BOXES_BUF_WORLD];
-            plan.world_stride = 4u;
-        } else if (!by_rule) {
-            plan.world_src = (const char *)desc->world.src + desc->world.first_byte;
-            plan.world_stride = desc->world.record_bytes;
+        if (!by_rule) {
+            resolveItemSource(own_world, boxes->bufs[MWHIP_BOXES_BUF_WORLD], 4u, desc->world,
+                              &plan.world_src, &plan.world_stride);
         }
-        if (desc->count.src != nullptr) {
-            plan.count_src = (const char *)desc->count.src + desc->count.first_byte;
-            plan.count_stride = desc->count.record_bytes;
-        }
-        if (own_centre) {
-            plan.centre_src = boxes->bufs[MWHIP_BOXES_BUF_CENTRE];
-            plan.centre_stride = 12u;
-        } else {
-            plan.centre_src = (const char *)desc->centre.src + desc->centre.first_byte;
-            plan.centre_stride = desc->centre.record_bytes;
-        }
+        resolveItemSource(false, nullptr, 0u, desc->count, &plan.count_src, &plan.count_stride);
+        resolveItemSource(own_centre, boxes->bufs[MWHIP_BOXES_BUF_CENTRE], 12u, desc->centre,
+                          &plan.centre_src, &plan.centre_stride);
         plan.lo = (const float *)boxes->bufs[MWHIP_BOXES_BUF_LO];
         plan.hi = (const float *)boxes->bufs[MWHIP_BOXES_BUF_HI];
         plan.status = (int32_t *)boxes->bufs[MWHIP_BOXES_BUF_STATUS];
@@ -253,34 +187,14 @@ extern "C" int mwhip_set_step_boxes(mwhip_exec *exec, uint64_t boxes, int on)
 {
     carryStale(exec);
     if (findBoxes(exec, boxes) == nullptr) return unknownObject("box query", boxes);
-    const std::vector<uint64_t> &step_boxes = exec->extras.stepBoxes;
-    const bool is_on = std::find(step_boxes.begin(), step_boxes.end(), boxes) != step_boxes.end();
-    if (is_on == (on != 0)) return 0;
-    if (on != 0 && step_boxes.size() >= MWHIP_MAX_STEP_BOXES) {
-        return fail(-2, "set_step_boxes: %u step box queries are set already (at most %u)",
-                    (uint32_t)step_boxes.size(), (uint32_t)MWHIP_MAX_STEP_BOXES);
-    }
-    return changeReplayExtras(exec, [boxes, on](ReplayExtras &extras) {
-        std::vector<uint64_t> &set = extras.stepBoxes;
-        if (on != 0) {
-            set.push_back(boxes);
-        } else {
-            set.erase(std::find(set.begin(), set.end(), boxes));
-        }
-        return 0;
-    });
+    return toggleStepSet(exec, &ReplayExtras::stepBoxes, boxes, on, MWHIP_MAX_STEP_BOXES,
+                         "set_step_boxes", "step box queries");
 }
 
 extern "C" void mwhip_boxes_destroy(mwhip_exec *exec, uint64_t handle)
 {
     carryStale(exec);
-    if (findBoxes(exec, handle) == nullptr) return;
-    (void)hipSetDevice(exec->cfg.gpu_id);
-    // (the step graphs must stop naming its buffers before they go; if they
-    // could not be rebuilt without it, it stays until mwhip_destroy)
-    if (mwhip_set_step_boxes(exec, handle, 0) != 0) return;
-    (void)hipStreamSynchronize(exec->stream);
-    exec->boxes.erase(handle);
+    destroyStepObject(exec, &mwhip_exec::boxes, handle, &mwhip_set_step_boxes);
 }
 
 extern "C" int mwhip_boxes_compute(mwhip_exec *exec, uint64_t handle)
@@ -298,20 +212,6 @@ extern "C" int mwhip_boxes_compute_async(mwhip_exec *exec, uint64_t handle)
 extern "C" void *mwhip_boxes_buffer(mwhip_exec *exec, uint64_t handle, uint32_t which,
                                     uint64_t *bytes_out)
 {
-    mwhip_boxes_rec *boxes = findBoxes(exec, handle);
-    if (boxes == nullptr) {
-        (void)unknownObject("box query", handle);
-        return nullptr;
-    }
-    if (which >= MWHIP_BOXES_NUM_BUFS) {
-        (void)fail(-2, "boxes_buffer: buffer %u of %u", which, (uint32_t)MWHIP_BOXES_NUM_BUFS);
-        return nullptr;
-    }
-    if (boxes->bufs[which] == nullptr) {
-        (void)fail(-2, "boxes_buffer: buffer %u is not owned (a source or bundles_per_world was "
-                   "given)", which);
-        return nullptr;
-    }
-    if (bytes_out != nullptr) *bytes_out = boxes->bytes[which];
-    return boxes->bufs[which];
+    return queryBuffer(findBoxes(exec, handle), "box query", handle, "boxes_buffer",
+                       "bundles_per_world", which, bytes_out);
 }

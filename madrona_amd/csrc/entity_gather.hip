@@ -61,11 +61,7 @@ struct GatherPlan {
 };
 
 // by value in the kernel-argument segment, like ViewArgs
-struct GatherArgs {
-    uint32_t numGathers;
-    uint32_t items[MWHIP_MAX_STEP_GATHERS];     // wavefront work items of each gather
-    const GatherPlan *plans[MWHIP_MAX_STEP_GATHERS];
-};
+using GatherArgs = madrona::mwhip::PlanBatch<GatherPlan, MWHIP_MAX_STEP_GATHERS>;
 
 using madrona::mwhip::HandleSource;
 using madrona::mwhip::Resolved;
@@ -143,27 +139,12 @@ entityGatherKernel(GatherArgs args)
 {
     const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    uint32_t total = 0;
-#pragma unroll
-    for (uint32_t g = 0; g < MWHIP_MAX_STEP_GATHERS; g++) {
-        if (g < args.numGathers) total += args.items[g];
-    }
+    const uint32_t total = madrona::mwhip::batchItems(args);
     for (uint32_t item = blockIdx.x * kGatherWaves + wave; item < total;
          item += gridDim.x * kGatherWaves) {
-        // the gather this item belongs to (constant indices: the arguments
-        // stay in scalar registers)
-        const GatherPlan *plan = nullptr;
-        uint32_t rel = item;
-#pragma unroll
-        for (uint32_t g = 0; g < MWHIP_MAX_STEP_GATHERS; g++) {
-            if (plan == nullptr && g < args.numGathers) {
-                if (rel < args.items[g]) {
-                    plan = args.plans[g];
-                } else {
-                    rel -= args.items[g];
-                }
-            }
-        }
+        // the gather this item belongs to
+        uint32_t rel;
+        const GatherPlan *plan = madrona::mwhip::planOfItem(args, item, &rel);
         if (plan != nullptr) {
             gatherWave(plan, rel, lane);
         }
@@ -203,28 +184,18 @@ mwhip_gather_rec *findGather(mwhip_exec *exec, uint64_t handle)
 
 dim3 gatherGrid(mwhip_exec *exec, uint32_t items)
 {
-    const uint32_t blocks = (items + kGatherWaves - 1u) / kGatherWaves;
-    return dim3(std::max(std::min(blocks, std::max(exec->numCUs, 1u) * 16u), 1u), 1, 1);
+    return waveGrid(exec, items, kGatherWaves, 16u);
 }
 
 int queueGather(mwhip_exec *exec, mwhip_gather_rec &gather)
 {
-    GatherArgs args {};
-    args.numGathers = 1;
-    args.items[0] = gather.items;
-    args.plans[0] = gather.planDev;
-    hipLaunchKernelGGL(entityGatherKernel, gatherGrid(exec, gather.items), dim3(kGatherThreads),
-                       0, exec->stream, args);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return queueBatch(exec, (const void *)&entityGatherKernel, gatherGrid(exec, gather.items),
+                      kGatherThreads, singleBatch<GatherArgs>(gather));
 }
 
 int computeGather(mwhip_exec *exec, uint64_t handle, bool wait)
 {
-    mwhip_gather_rec *gather = findGather(exec, handle);
-    if (gather == nullptr) return unknownObject("gather", handle);
-    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
-    return finishQueued(exec, queueGather(exec, *gather), wait);
+    return computeObject(exec, findGather(exec, handle), "gather", handle, wait, queueGather);
 }
 
 // Bytes the step gathers' last run read: per handle the handle itself, and for
@@ -259,32 +230,16 @@ MWHIP_RT int stepGatherStage(mwhip_exec *exec, const LaunchGraph &lg,
 {
     if (lg.isRender) return 0;
     GatherArgs args {};
-    uint32_t items = 0;
     double written = 0;
-    for (uint64_t handle : exec->extras.stepGathers) {
-        mwhip_gather_rec *gather = findGather(exec, handle);
-        if (gather == nullptr || args.numGathers >= MWHIP_MAX_STEP_GATHERS) continue;
-        args.items[args.numGathers] = gather->items;
-        args.plans[args.numGathers] = gather->planDev;
-        args.numGathers += 1;
-        items += gather->items;
-        written += (double)gather->numHandles * ((double)gather->rowBytes + 8.0);
-    }
-    if (args.numGathers == 0) return 0;
-
-    KernelLaunch k;
-    static_assert(sizeof(GatherArgs) <= sizeof(k.argStorage));
-    k.fn = (const void *)&entityGatherKernel;
-    k.grid = gatherGrid(exec, items);
-    k.block = dim3(kGatherThreads, 1, 1);
-    k.setArgs(args);
-    k.name = "gather";
-    k.role = "gather";
-    k.kind = MWHIP_NODE_RECYCLE;
-    k.fixedBytes = written;
-    // what the step gathers read: from the archetypes they just left
-    k.measuredBytes = &stepGatherReadBytes;
-    out.push_back(k);
+    const uint32_t items = collectStepBatch(
+        exec->extras.stepGathers, exec->gathers, args, [&](const mwhip_gather_rec &gather) {
+            written += (double)gather.numHandles * ((double)gather.rowBytes + 8.0);
+        });
+    if (args.num_plans == 0) return 0;
+    // (what the step gathers read: from the archetypes they just left)
+    out.push_back(stageLaunch((const void *)&entityGatherKernel, gatherGrid(exec, items),
+                              kGatherThreads, args, "gather", "gather", written,
+                              &stepGatherReadBytes));
     return 0;
 }
 
@@ -412,35 +367,14 @@ extern "C" int mwhip_set_step_gather(mwhip_exec *exec, uint64_t gather, int on)
 {
     carryStale(exec);
     if (findGather(exec, gather) == nullptr) return unknownObject("gather", gather);
-    const std::vector<uint64_t> &step_gathers = exec->extras.stepGathers;
-    const bool is_on =
-        std::find(step_gathers.begin(), step_gathers.end(), gather) != step_gathers.end();
-    if (is_on == (on != 0)) return 0;
-    if (on != 0 && step_gathers.size() >= MWHIP_MAX_STEP_GATHERS) {
-        return fail(-2, "set_step_gather: %u step gathers are set already (at most %u)",
-                    (uint32_t)step_gathers.size(), (uint32_t)MWHIP_MAX_STEP_GATHERS);
-    }
-    return changeReplayExtras(exec, [gather, on](ReplayExtras &extras) {
-        std::vector<uint64_t> &gathers = extras.stepGathers;
-        if (on != 0) {
-            gathers.push_back(gather);
-        } else {
-            gathers.erase(std::find(gathers.begin(), gathers.end(), gather));
-        }
-        return 0;
-    });
+    return toggleStepSet(exec, &ReplayExtras::stepGathers, gather, on, MWHIP_MAX_STEP_GATHERS,
+                         "set_step_gather", "step gathers");
 }
 
 extern "C" void mwhip_gather_destroy(mwhip_exec *exec, uint64_t handle)
 {
     carryStale(exec);
-    if (findGather(exec, handle) == nullptr) return;
-    (void)hipSetDevice(exec->cfg.gpu_id);
-    // (the step graphs must stop naming its buffers before they go; if they
-    // could not be rebuilt without it, it stays until mwhip_destroy)
-    if (mwhip_set_step_gather(exec, handle, 0) != 0) return;
-    (void)hipStreamSynchronize(exec->stream);
-    exec->gathers.erase(handle);
+    destroyStepObject(exec, &mwhip_exec::gathers, handle, &mwhip_set_step_gather);
 }
 
 extern "C" int mwhip_gather_compute(mwhip_exec *exec, uint64_t handle)

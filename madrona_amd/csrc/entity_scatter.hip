@@ -89,11 +89,7 @@ struct ScatterPlan {
 };
 
 // by value in the kernel-argument segment, like GatherArgs
-struct ScatterArgs {
-    uint32_t numScatters;
-    uint32_t items[MWHIP_MAX_STEP_SCATTERS];    // wavefront work items of each scatter
-    const ScatterPlan *plans[MWHIP_MAX_STEP_SCATTERS];
-};
+using ScatterArgs = madrona::mwhip::PlanBatch<ScatterPlan, MWHIP_MAX_STEP_SCATTERS>;
 
 struct ScatterZeroArgs {
     uint32_t numScatters;
@@ -229,45 +225,16 @@ __device__ inline void writeWave(const ScatterPlan *plan, uint32_t item, uint32_
     }
 }
 
-// The scatter work item `item` belongs to and its number there (constant
-// indices: the arguments stay in scalar registers).
-__device__ inline const ScatterPlan *planOf(const ScatterArgs &args, uint32_t item, uint32_t *rel)
-{
-    const ScatterPlan *plan = nullptr;
-    *rel = item;
-#pragma unroll
-    for (uint32_t g = 0; g < MWHIP_MAX_STEP_SCATTERS; g++) {
-        if (plan == nullptr && g < args.numScatters) {
-            if (*rel < args.items[g]) {
-                plan = args.plans[g];
-            } else {
-                *rel -= args.items[g];
-            }
-        }
-    }
-    return plan;
-}
-
-__device__ inline uint32_t totalItems(const ScatterArgs &args)
-{
-    uint32_t total = 0;
-#pragma unroll
-    for (uint32_t g = 0; g < MWHIP_MAX_STEP_SCATTERS; g++) {
-        if (g < args.numScatters) total += args.items[g];
-    }
-    return total;
-}
-
 __global__ void __launch_bounds__(kScatterThreads)
 scatterClaimKernel(ScatterArgs args)
 {
     const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t total = totalItems(args);
+    const uint32_t total = madrona::mwhip::batchItems(args);
     for (uint32_t item = blockIdx.x * kScatterWaves + wave; item < total;
          item += gridDim.x * kScatterWaves) {
         uint32_t rel;
-        const ScatterPlan *plan = planOf(args, item, &rel);
+        const ScatterPlan *plan = madrona::mwhip::planOfItem(args, item, &rel);
         if (plan != nullptr) claimWave(plan, rel, lane);
     }
 }
@@ -277,11 +244,11 @@ scatterWriteKernel(ScatterArgs args)
 {
     const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t total = totalItems(args);
+    const uint32_t total = madrona::mwhip::batchItems(args);
     for (uint32_t item = blockIdx.x * kScatterWaves + wave; item < total;
          item += gridDim.x * kScatterWaves) {
         uint32_t rel;
-        const ScatterPlan *plan = planOf(args, item, &rel);
+        const ScatterPlan *plan = madrona::mwhip::planOfItem(args, item, &rel);
         if (plan != nullptr) writeWave(plan, rel, lane);
     }
 }
@@ -325,8 +292,7 @@ mwhip_scatter_rec *findScatter(mwhip_exec *exec, uint64_t handle)
 
 dim3 scatterGrid(mwhip_exec *exec, uint32_t items)
 {
-    const uint32_t blocks = (items + kScatterWaves - 1u) / kScatterWaves;
-    return dim3(std::max(std::min(blocks, std::max(exec->numCUs, 1u) * 16u), 1u), 1, 1);
+    return waveGrid(exec, items, kScatterWaves, 16u);
 }
 
 dim3 zeroGrid(mwhip_exec *exec, uint64_t vecs)
@@ -336,60 +302,48 @@ dim3 zeroGrid(mwhip_exec *exec, uint64_t vecs)
                     std::min<uint64_t>(blocks, std::max(exec->numCUs, 1u) * 16u), 1u), 1, 1);
 }
 
-// The three launches for `scatters` (1 .. MWHIP_MAX_STEP_SCATTERS of them).
+// What the three launches need of the scatters in `args` (1 ..
+// MWHIP_MAX_STEP_SCATTERS of them) besides that batch.
 struct ScatterLaunches {
     ScatterZeroArgs zero {};
     ScatterArgs args {};
-    dim3 zeroGrid;
-    dim3 grid;
+    uint64_t vecs = 0;          // of the largest claim table
     double claimBytes = 0;      // of the claim tables
     double perHandleBytes = 0;  // N of every scatter
-};
 
-ScatterLaunches scatterLaunches(mwhip_exec *exec, const std::vector<mwhip_scatter_rec *> &scatters)
-{
-    ScatterLaunches out;
-    uint32_t items = 0;
-    uint64_t vecs = 0;
-    for (mwhip_scatter_rec *scatter : scatters) {
-        const uint32_t g = out.args.numScatters;
-        out.args.items[g] = scatter->items;
-        out.args.plans[g] = scatter->planDev;
-        out.args.numScatters += 1;
-        out.zero.vecs[g] = scatter->slots / 2u;     // 2 * slots words of 4 bytes
-        out.zero.tables[g] = scatter->claimDev;
-        out.zero.numScatters += 1;
-        items += scatter->items;
-        vecs = std::max<uint64_t>(vecs, scatter->slots / 2u);
-        out.claimBytes += (double)scatter->slots * 8.0;
-        out.perHandleBytes += (double)scatter->numHandles;
+    // (behind the batch, which just took it)
+    void take(const mwhip_scatter_rec &scatter)
+    {
+        const uint32_t g = zero.numScatters;
+        zero.vecs[g] = scatter.slots / 2u;      // 2 * slots words of 4 bytes
+        zero.tables[g] = scatter.claimDev;
+        zero.numScatters += 1;
+        vecs = std::max<uint64_t>(vecs, scatter.slots / 2u);
+        claimBytes += (double)scatter.slots * 8.0;
+        perHandleBytes += (double)scatter.numHandles;
     }
-    out.zeroGrid = zeroGrid(exec, vecs);
-    out.grid = scatterGrid(exec, items);
-    return out;
-}
+};
 
 int queueScatter(mwhip_exec *exec, mwhip_scatter_rec &scatter)
 {
-    const ScatterLaunches l = scatterLaunches(exec, { &scatter });
-    hipLaunchKernelGGL(scatterZeroKernel, l.zeroGrid, dim3(kScatterThreads), 0, exec->stream,
-                       l.zero);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(scatterClaimKernel, l.grid, dim3(kScatterThreads), 0, exec->stream,
-                       l.args);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(scatterWriteKernel, l.grid, dim3(kScatterThreads), 0, exec->stream,
-                       l.args);
-    HIPCHK(hipGetLastError());
-    return 0;
+    ScatterLaunches l;
+    l.args = singleBatch<ScatterArgs>(scatter);
+    l.take(scatter);
+    const dim3 grid = scatterGrid(exec, scatter.items);
+    int rc = queueBatch(exec, (const void *)&scatterZeroKernel, zeroGrid(exec, l.vecs),
+                        kScatterThreads, l.zero);
+    if (rc == 0) {
+        rc = queueBatch(exec, (const void *)&scatterClaimKernel, grid, kScatterThreads, l.args);
+    }
+    if (rc == 0) {
+        rc = queueBatch(exec, (const void *)&scatterWriteKernel, grid, kScatterThreads, l.args);
+    }
+    return rc;
 }
 
 int applyScatter(mwhip_exec *exec, uint64_t handle, bool wait)
 {
-    mwhip_scatter_rec *scatter = findScatter(exec, handle);
-    if (scatter == nullptr) return unknownObject("scatter", handle);
-    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
-    return finishQueued(exec, queueScatter(exec, *scatter), wait);
+    return computeObject(exec, findScatter(exec, handle), "scatter", handle, wait, queueScatter);
 }
 
 // What the step scatters' last run left: handles that named an entity and
@@ -446,53 +400,23 @@ MWHIP_RT int stepScatterStage(mwhip_exec *exec, const LaunchGraph &lg,
                               std::vector<KernelLaunch> &out)
 {
     if (lg.isRender) return 0;
-    std::vector<mwhip_scatter_rec *> scatters;
-    for (uint64_t handle : exec->extras.stepScatters) {
-        mwhip_scatter_rec *scatter = findScatter(exec, handle);
-        if (scatter == nullptr || scatters.size() >= MWHIP_MAX_STEP_SCATTERS) continue;
-        scatters.push_back(scatter);
-    }
-    if (scatters.empty()) return 0;
-    const ScatterLaunches l = scatterLaunches(exec, scatters);
+    ScatterLaunches l;
+    const uint32_t items = collectStepBatch(
+        exec->extras.stepScatters, exec->scatters, l.args,
+        [&](const mwhip_scatter_rec &scatter) { l.take(scatter); });
+    if (l.args.num_plans == 0) return 0;
+    const dim3 grid = scatterGrid(exec, items);
 
-    KernelLaunch zero;
-    static_assert(sizeof(ScatterZeroArgs) <= sizeof(zero.argStorage));
-    static_assert(sizeof(ScatterArgs) <= sizeof(zero.argStorage));
-    zero.fn = (const void *)&scatterZeroKernel;
-    zero.grid = l.zeroGrid;
-    zero.block = dim3(kScatterThreads, 1, 1);
-    zero.setArgs(l.zero);
-    zero.name = "scatter";
-    zero.role = "scatter.zero";
-    zero.kind = MWHIP_NODE_RECYCLE;
-    zero.fixedBytes = l.claimBytes;
-    out.push_back(zero);
-
-    KernelLaunch claim;
-    claim.fn = (const void *)&scatterClaimKernel;
-    claim.grid = l.grid;
-    claim.block = dim3(kScatterThreads, 1, 1);
-    claim.setArgs(l.args);
-    claim.name = "scatter";
-    claim.role = "scatter.claim";
-    claim.kind = MWHIP_NODE_RECYCLE;
+    out.push_back(stageLaunch((const void *)&scatterZeroKernel, zeroGrid(exec, l.vecs),
+                              kScatterThreads, l.zero, "scatter", "scatter.zero", l.claimBytes));
     // per handle: the handle and select read, archetype and world written
-    claim.fixedBytes = l.perHandleBytes * (8.0 + 4.0 + 8.0);
-    claim.measuredBytes = &stepScatterClaimBytes;
-    out.push_back(claim);
-
-    KernelLaunch write;
-    write.fn = (const void *)&scatterWriteKernel;
-    write.grid = l.grid;
-    write.block = dim3(kScatterThreads, 1, 1);
-    write.setArgs(l.args);
-    write.name = "scatter";
-    write.role = "scatter.write";
-    write.kind = MWHIP_NODE_RECYCLE;
+    out.push_back(stageLaunch((const void *)&scatterClaimKernel, grid, kScatterThreads, l.args,
+                              "scatter", "scatter.claim", l.perHandleBytes * (8.0 + 4.0 + 8.0),
+                              &stepScatterClaimBytes));
     // per handle: the handle and select read, written written
-    write.fixedBytes = l.perHandleBytes * (8.0 + 4.0 + 4.0);
-    write.measuredBytes = &stepScatterWriteBytes;
-    out.push_back(write);
+    out.push_back(stageLaunch((const void *)&scatterWriteKernel, grid, kScatterThreads, l.args,
+                              "scatter", "scatter.write", l.perHandleBytes * (8.0 + 4.0 + 4.0),
+                              &stepScatterWriteBytes));
     return 0;
 }
 
@@ -596,18 +520,10 @@ extern "C" int mwhip_set_step_scatter(mwhip_exec *exec, uint64_t scatter, int on
     carryStale(exec);
     mwhip_scatter_rec *rec = findScatter(exec, scatter);
     if (rec == nullptr) return unknownObject("scatter", scatter);
-    const std::vector<uint64_t> &step_scatters = exec->extras.stepScatters;
-    const bool is_on =
-        std::find(step_scatters.begin(), step_scatters.end(), scatter) != step_scatters.end();
-    if (is_on == (on != 0)) return 0;
-    if (on != 0 && step_scatters.size() >= MWHIP_MAX_STEP_SCATTERS) {
-        return fail(-2, "set_step_scatter: %u step scatters are set already (at most %u)",
-                    (uint32_t)step_scatters.size(), (uint32_t)MWHIP_MAX_STEP_SCATTERS);
-    }
-    if (on != 0) {
-        // (two step scatters run in the same launches, each with a claim table
-        // of its own: on one component they could store to one cell)
-        for (uint64_t other_handle : step_scatters) {
+    // (two step scatters run in the same launches, each with a claim table of
+    // its own: on one component they could store to one cell)
+    const auto disjoint = [exec, rec, scatter] {
+        for (uint64_t other_handle : exec->extras.stepScatters) {
             mwhip_scatter_rec *other = findScatter(exec, other_handle);
             if (other == nullptr) continue;
             for (uint32_t component : rec->components) {
@@ -620,28 +536,16 @@ extern "C" int mwhip_set_step_scatter(mwhip_exec *exec, uint64_t scatter, int on
                 }
             }
         }
-    }
-    return changeReplayExtras(exec, [scatter, on](ReplayExtras &extras) {
-        std::vector<uint64_t> &scatters = extras.stepScatters;
-        if (on != 0) {
-            scatters.push_back(scatter);
-        } else {
-            scatters.erase(std::find(scatters.begin(), scatters.end(), scatter));
-        }
         return 0;
-    });
+    };
+    return toggleStepSet(exec, &ReplayExtras::stepScatters, scatter, on, MWHIP_MAX_STEP_SCATTERS,
+                         "set_step_scatter", "step scatters", disjoint);
 }
 
 extern "C" void mwhip_scatter_destroy(mwhip_exec *exec, uint64_t handle)
 {
     carryStale(exec);
-    if (findScatter(exec, handle) == nullptr) return;
-    (void)hipSetDevice(exec->cfg.gpu_id);
-    // (the step graphs must stop naming its buffers before they go; if they
-    // could not be rebuilt without it, it stays until mwhip_destroy)
-    if (mwhip_set_step_scatter(exec, handle, 0) != 0) return;
-    (void)hipStreamSynchronize(exec->stream);
-    exec->scatters.erase(handle);
+    destroyStepObject(exec, &mwhip_exec::scatters, handle, &mwhip_set_step_scatter);
 }
 
 extern "C" int mwhip_scatter_apply(mwhip_exec *exec, uint64_t handle)

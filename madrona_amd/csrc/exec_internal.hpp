@@ -10,7 +10,10 @@
 // entity_scatter.hip: cells written into those entities; ray_query.hip: rays
 // cast through the worlds' broadphase BVHs by the simulator's kernel;
 // box_query.hip: boxes tested through the same BVHs by its second kernel).
-// Not installed.
+// exec_objects.hpp (included in front of mwhip_exec) holds what every executor
+// object shares, step_batch.hpp (included at the end) what the step-batched ones
+// share; tree_query.hpp, which ray_query.hip and box_query.hip include, what
+// those two share.  Not installed.
 #pragma once
 #include "runtime_internal.hpp"
 #include <madrona/tracing.hpp>
@@ -543,11 +546,6 @@ MWHIP_RT int checkHandleRequest(mwhip_exec *exec, const char *what,
 MWHIP_RT int stepRaysStage(mwhip_exec *exec, const LaunchGraph &lg,
                            std::vector<KernelLaunch> &out);
       // (ray_query.hip)
-// what `who` (rays_create, boxes_create) refuses about a source of `item_bytes`
-// per record
-MWHIP_RT int checkItemSource(const char *who, const char *name, const mwhip_ray_source &source,
-                             uint32_t item_bytes);
-      // (ray_query.hip)
 MWHIP_RT int stepBoxesStage(mwhip_exec *exec, const LaunchGraph &lg,
                             std::vector<KernelLaunch> &out);
       // (box_query.hip)
@@ -590,3 +588,6 @@ inline int changeReplayExtras(mwhip_exec *exec, Change &&change)
     if (rc != 0) exec->extras = before;
     return rc;
 }
+
+// (needs mwhip_exec, ReplayExtras and changeReplayExtras from above)
+#include "step_batch.hpp"

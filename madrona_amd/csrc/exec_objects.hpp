@@ -3,7 +3,9 @@
 // (world_reduce.hip), entity gathers (entity_gather.hip), entity scatters
 // (entity_scatter.hip), ray queries (ray_query.hip) and box queries
 // (box_query.hip) share on the host
-// (DESIGN.md §24).  An executor object
+// (what the last seven share as step-batched objects is in
+// step_batch.hpp, what the last two share besides in tree_query.hpp).  An
+// executor object
 // is a record with device memory of its own, made by mwhip_<kind>_create, named
 // by a handle, used through mwhip_<kind>_* and freed by mwhip_<kind>_destroy or
 // with its executor.  Host code only.  Not a header to include on its own:

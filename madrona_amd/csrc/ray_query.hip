@@ -12,8 +12,9 @@
 // A query owns a device-resident plan and ONE allocation with its owned inputs
 // (world and origin unless a source was given; direction and t_max always) and
 // its outputs (hit_t, hit, normal, status), 256-byte aligned each.  Sources are
-// read on the device when the kernel runs, as a gather's.
-#include "exec_internal.hpp"
+// read on the device when the kernel runs, as a gather's.  What a box query has
+// too is in tree_query.hpp.
+#include "tree_query.hpp"
 
 namespace {
 
@@ -22,22 +23,10 @@ constexpr uint32_t kRayWaves = kRayThreads / 64u;
 
 }
 
-struct mwhip_rays_rec {
-    uint64_t handle = 0;
+struct mwhip_rays_rec : TreeQueryRec<mwhip_ray_plan, MWHIP_RAYS_NUM_BUFS> {
     uint32_t numFans = 0;
     uint32_t raysPerFan = 0;
     uint32_t numRays = 0;
-    uint32_t items = 0;         // wavefront work items
-    char *bufs[MWHIP_RAYS_NUM_BUFS] = {};       // into bufDev; null: not owned
-    uint64_t bytes[MWHIP_RAYS_NUM_BUFS] = {};
-    mwhip_ray_plan *planDev = nullptr;
-    char *bufDev = nullptr;
-
-    ~mwhip_rays_rec()
-    {
-        if (planDev != nullptr) (void)hipFree(planDev);
-        if (bufDev != nullptr) (void)hipFree(bufDev);
-    }
 };
 
 namespace {
@@ -50,53 +39,20 @@ mwhip_rays_rec *findRays(mwhip_exec *exec, uint64_t handle)
 // (four workgroups of 39 KB of LDS fit a CU; wavefronts stride over the items)
 dim3 rayGrid(mwhip_exec *exec, uint32_t items)
 {
-    const uint32_t blocks = (items + kRayWaves - 1u) / kRayWaves;
-    return dim3(std::max(std::min(blocks, std::max(exec->numCUs, 1u) * 8u), 1u), 1, 1);
+    return waveGrid(exec, items, kRayWaves, 8u);
 }
 
 int queueRays(mwhip_exec *exec, mwhip_rays_rec &rays)
 {
-    mwhip_ray_args args {};
-    args.num_plans = 1;
-    args.items[0] = rays.items;
-    args.plans[0] = rays.planDev;
-    void *argv[] = { &args };
-    HIPCHK(hipLaunchKernel(exec->rayKernel, rayGrid(exec, rays.items), dim3(kRayThreads), argv,
-                           0, exec->stream));
-    return 0;
+    return queueBatch(exec, exec->rayKernel, rayGrid(exec, rays.items), kRayThreads,
+                      singleBatch<mwhip_ray_args>(rays));
 }
 
 int computeRays(mwhip_exec *exec, uint64_t handle, bool wait)
 {
-    mwhip_rays_rec *rays = findRays(exec, handle);
-    if (rays == nullptr) return unknownObject("ray query", handle);
-    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
-    return finishQueued(exec, queueRays(exec, *rays), wait);
+    return computeObject(exec, findRays(exec, handle), "ray query", handle, wait, queueRays);
 }
 
-int checkRaySource(const char *name, const mwhip_ray_source &source, uint32_t item_bytes)
-{
-    return checkItemSource("rays_create", name, source, item_bytes);
-}
-
-}
-
-// what a create refuses about a source of `item_bytes` per record (box queries
-// take the same sources: box_query.hip)
-MWHIP_RT int checkItemSource(const char *who, const char *name, const mwhip_ray_source &source,
-                             uint32_t item_bytes)
-{
-    if (((uint64_t)source.src & 3ull) != 0ull || source.record_bytes % 4u != 0u ||
-            source.first_byte % 4u != 0u) {
-        return fail(-2, "%s: %s: src %p, record_bytes %u and first_byte %u must be "
-                    "multiples of 4", who, name, source.src, source.record_bytes,
-                    source.first_byte);
-    }
-    if ((uint64_t)source.first_byte + item_bytes > (uint64_t)source.record_bytes) {
-        return fail(-2, "%s: %s: %u bytes from byte %u do not fit a record of %u bytes", who,
-                    name, item_bytes, source.first_byte, source.record_bytes);
-    }
-    return 0;
 }
 
 // Tail stage: the ONE launch that recomputes every step ray query inside a step
@@ -108,32 +64,16 @@ MWHIP_RT int stepRaysStage(mwhip_exec *exec, const LaunchGraph &lg,
 {
     if (lg.isRender || exec->rayKernel == nullptr) return 0;
     mwhip_ray_args args {};
-    uint32_t items = 0;
     double bytes = 0;
-    for (uint64_t handle : exec->extras.stepRays) {
-        mwhip_rays_rec *rays = findRays(exec, handle);
-        if (rays == nullptr || args.num_plans >= MWHIP_MAX_STEP_RAYS) continue;
-        args.items[args.num_plans] = rays->items;
-        args.plans[args.num_plans] = rays->planDev;
-        args.num_plans += 1;
-        items += rays->items;
-        // written: hit_t, hit, normal, status; read: direction, t_max, and per
-        // fan world and origin (the trees' bytes depend on the rays)
-        bytes += (double)rays->numRays * (28.0 + 16.0) + (double)rays->numFans * 16.0;
-    }
+    const uint32_t items = collectStepBatch(
+        exec->extras.stepRays, exec->rays, args, [&](const mwhip_rays_rec &rays) {
+            // written: hit_t, hit, normal, status; read: direction, t_max, and
+            // per fan world and origin (the trees' bytes depend on the rays)
+            bytes += (double)rays.numRays * (28.0 + 16.0) + (double)rays.numFans * 16.0;
+        });
     if (args.num_plans == 0) return 0;
-
-    KernelLaunch k;
-    static_assert(sizeof(mwhip_ray_args) <= sizeof(k.argStorage));
-    k.fn = exec->rayKernel;
-    k.grid = rayGrid(exec, items);
-    k.block = dim3(kRayThreads, 1, 1);
-    k.setArgs(args);
-    k.name = "rays";
-    k.role = "rays";
-    k.kind = MWHIP_NODE_RECYCLE;
-    k.fixedBytes = bytes;
-    out.push_back(k);
+    out.push_back(stageLaunch(exec->rayKernel, rayGrid(exec, items), kRayThreads, args, "rays",
+                              "rays", bytes));
     return 0;
 }
 
@@ -168,19 +108,12 @@ extern "C" int mwhip_rays_create(mwhip_exec *exec, const mwhip_rays_desc *desc,
     const bool by_rule = desc->fans_per_world != 0u;
     const bool own_world = !by_rule && desc->world.src == nullptr;
     const bool own_origin = desc->origin.src == nullptr;
-    int rc = 0;
-    if (!by_rule && !own_world) rc = checkRaySource("world", desc->world, 4u);
-    if (rc == 0 && desc->count.src != nullptr) {
-        if (!by_rule) {
-            return fail(-2, "rays_create: a count source needs fans_per_world > 0");
-        }
-        rc = checkRaySource("count", desc->count, 4u);
-    }
-    if (rc == 0 && !own_origin) rc = checkRaySource("origin", desc->origin, 12u);
+    const int rc = checkGroupSources("rays_create", by_rule, "fans_per_world", desc->world,
+                                     desc->count, "origin", desc->origin);
     if (rc != 0) return rc;
 
     HIPCHK(hipSetDevice(exec->cfg.gpu_id));
-    std::unique_ptr<mwhip_rays_rec> rays(new mwhip_rays_rec {});
+    std::unique_ptr<mwhip_rays_rec> rays(new mwhip_rays_rec());
     const uint32_t F = desc->num_fans, R = desc->rays_per_fan, N = F * R;
     rays->numFans = F;
     rays->raysPerFan = R;
@@ -199,20 +132,9 @@ extern "C" int mwhip_rays_create(mwhip_exec *exec, const mwhip_rays_desc *desc,
     rays->bytes[MWHIP_RAYS_BUF_HIT] = (uint64_t)N * 8ull;
     rays->bytes[MWHIP_RAYS_BUF_NORMAL] = (uint64_t)N * 12ull;
     rays->bytes[MWHIP_RAYS_BUF_STATUS] = (uint64_t)N * 4ull;
-    uint64_t offsets[MWHIP_RAYS_NUM_BUFS];
     uint64_t total = 0;
-    for (uint32_t b = 0; b < MWHIP_RAYS_NUM_BUFS; b++) {
-        offsets[b] = total;
-        total += (rays->bytes[b] + 255ull) & ~255ull;
-    }
-
-    bool ok = hipMalloc((void **)&rays->bufDev, total) == hipSuccess &&
-        hipMalloc((void **)&rays->planDev, sizeof(mwhip_ray_plan)) == hipSuccess &&
-        hipMemset(rays->bufDev, 0, total) == hipSuccess;
+    bool ok = allocQueryBuffers(*rays, &total);
     if (ok) {
-        for (uint32_t b = 0; b < MWHIP_RAYS_NUM_BUFS; b++) {
-            if (rays->bytes[b] != 0ull) rays->bufs[b] = rays->bufDev + offsets[b];
-        }
         // t_max starts at +inf; the outputs as a compute leaves a query that
         // met nothing
         ok = hipMemsetD32((hipDeviceptr_t)rays->bufs[MWHIP_RAYS_BUF_T_MAX], 0x7F800000,
@@ -222,24 +144,13 @@ extern "C" int mwhip_rays_create(mwhip_exec *exec, const mwhip_rays_desc *desc,
     if (ok) {
         mwhip_ray_plan plan {};
         plan.state = exec->stateDev;
-        if (own_world) {
-            plan.world_src = rays->bufs[MWHIP_RAYS_BUF_WORLD];
-            plan.world_stride = 4u;
-        } else if (!by_rule) {
-            plan.world_src = (const char *)desc->world.src + desc->world.first_byte;
-            plan.world_stride = desc->world.record_bytes;
+        if (!by_rule) {
+            resolveItemSource(own_world, rays->bufs[MWHIP_RAYS_BUF_WORLD], 4u, desc->world,
+                              &plan.world_src, &plan.world_stride);
         }
-        if (desc->count.src != nullptr) {
-            plan.count_src = (const char *)desc->count.src + desc->count.first_byte;
-            plan.count_stride = desc->count.record_bytes;
-        }
-        if (own_origin) {
-            plan.origin_src = rays->bufs[MWHIP_RAYS_BUF_ORIGIN];
-            plan.origin_stride = 12u;
-        } else {
-            plan.origin_src = (const char *)desc->origin.src + desc->origin.first_byte;
-            plan.origin_stride = desc->origin.record_bytes;
-        }
+        resolveItemSource(false, nullptr, 0u, desc->count, &plan.count_src, &plan.count_stride);
+        resolveItemSource(own_origin, rays->bufs[MWHIP_RAYS_BUF_ORIGIN], 12u, desc->origin,
+                          &plan.origin_src, &plan.origin_stride);
         plan.dir = (const float *)rays->bufs[MWHIP_RAYS_BUF_DIR];
         plan.t_max = (const float *)rays->bufs[MWHIP_RAYS_BUF_T_MAX];
         plan.hit_t = (float *)rays->bufs[MWHIP_RAYS_BUF_HIT_T];
@@ -264,34 +175,14 @@ extern "C" int mwhip_set_step_rays(mwhip_exec *exec, uint64_t rays, int on)
 {
     carryStale(exec);
     if (findRays(exec, rays) == nullptr) return unknownObject("ray query", rays);
-    const std::vector<uint64_t> &step_rays = exec->extras.stepRays;
-    const bool is_on = std::find(step_rays.begin(), step_rays.end(), rays) != step_rays.end();
-    if (is_on == (on != 0)) return 0;
-    if (on != 0 && step_rays.size() >= MWHIP_MAX_STEP_RAYS) {
-        return fail(-2, "set_step_rays: %u step ray queries are set already (at most %u)",
-                    (uint32_t)step_rays.size(), (uint32_t)MWHIP_MAX_STEP_RAYS);
-    }
-    return changeReplayExtras(exec, [rays, on](ReplayExtras &extras) {
-        std::vector<uint64_t> &set = extras.stepRays;
-        if (on != 0) {
-            set.push_back(rays);
-        } else {
-            set.erase(std::find(set.begin(), set.end(), rays));
-        }
-        return 0;
-    });
+    return toggleStepSet(exec, &ReplayExtras::stepRays, rays, on, MWHIP_MAX_STEP_RAYS,
+                         "set_step_rays", "step ray queries");
 }
 
 extern "C" void mwhip_rays_destroy(mwhip_exec *exec, uint64_t handle)
 {
     carryStale(exec);
-    if (findRays(exec, handle) == nullptr) return;
-    (void)hipSetDevice(exec->cfg.gpu_id);
-    // (the step graphs must stop naming its buffers before they go; if they
-    // could not be rebuilt without it, it stays until mwhip_destroy)
-    if (mwhip_set_step_rays(exec, handle, 0) != 0) return;
-    (void)hipStreamSynchronize(exec->stream);
-    exec->rays.erase(handle);
+    destroyStepObject(exec, &mwhip_exec::rays, handle, &mwhip_set_step_rays);
 }
 
 extern "C" int mwhip_rays_compute(mwhip_exec *exec, uint64_t handle)
@@ -309,20 +200,6 @@ extern "C" int mwhip_rays_compute_async(mwhip_exec *exec, uint64_t handle)
 extern "C" void *mwhip_rays_buffer(mwhip_exec *exec, uint64_t handle, uint32_t which,
                                    uint64_t *bytes_out)
 {
-    mwhip_rays_rec *rays = findRays(exec, handle);
-    if (rays == nullptr) {
-        (void)unknownObject("ray query", handle);
-        return nullptr;
-    }
-    if (which >= MWHIP_RAYS_NUM_BUFS) {
-        (void)fail(-2, "rays_buffer: buffer %u of %u", which, (uint32_t)MWHIP_RAYS_NUM_BUFS);
-        return nullptr;
-    }
-    if (rays->bufs[which] == nullptr) {
-        (void)fail(-2, "rays_buffer: buffer %u is not owned (a source or fans_per_world was "
-                   "given)", which);
-        return nullptr;
-    }
-    if (bytes_out != nullptr) *bytes_out = rays->bytes[which];
-    return rays->bufs[which];
+    return queryBuffer(findRays(exec, handle), "ray query", handle, "rays_buffer",
+                       "fans_per_world", which, bytes_out);
 }

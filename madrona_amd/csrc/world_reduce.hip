@@ -94,11 +94,7 @@ struct ReduceTermInfo {
 };
 
 // by value in the kernel-argument segment, like ViewArgs
-struct ReduceArgs {
-    uint32_t numReduces;
-    uint32_t items[MWHIP_MAX_STEP_REDUCES];     // wavefront work items of each reduce
-    const ReducePlan *plans[MWHIP_MAX_STEP_REDUCES];
-};
+using ReduceArgs = madrona::mwhip::PlanBatch<ReducePlan, MWHIP_MAX_STEP_REDUCES>;
 
 using madrona::mwhip::GlobalU32;
 using madrona::mwhip::GlobalU8;
@@ -324,7 +320,7 @@ worldReduceKernel(ReduceArgs args)
     uint32_t total = 0;
 #pragma unroll
     for (uint32_t v = 0; v < MWHIP_MAX_STEP_REDUCES; v++) {
-        if (v < args.numReduces) total += args.items[v];
+        if (v < args.num_plans) total += args.items[v];
     }
     for (uint32_t item = blockIdx.x * kReduceWaves + wave; item < total;
          item += gridDim.x * kReduceWaves) {
@@ -334,7 +330,7 @@ worldReduceKernel(ReduceArgs args)
         uint32_t rel = item;
 #pragma unroll
         for (uint32_t v = 0; v < MWHIP_MAX_STEP_REDUCES; v++) {
-            if (plan == nullptr && v < args.numReduces) {
+            if (plan == nullptr && v < args.num_plans) {
                 if (rel < args.items[v]) {
                     plan = args.plans[v];
                 } else {
@@ -382,28 +378,18 @@ mwhip_reduce_rec *findReduce(mwhip_exec *exec, uint64_t handle)
 
 dim3 reduceGrid(mwhip_exec *exec, uint32_t items)
 {
-    const uint32_t blocks = (items + kReduceWaves - 1u) / kReduceWaves;
-    return dim3(std::max(std::min(blocks, std::max(exec->numCUs, 1u) * 16u), 1u), 1, 1);
+    return waveGrid(exec, items, kReduceWaves, 16u);
 }
 
 int queueReduce(mwhip_exec *exec, mwhip_reduce_rec &reduce)
 {
-    ReduceArgs args {};
-    args.numReduces = 1;
-    args.items[0] = reduce.items;
-    args.plans[0] = reduce.planDev;
-    hipLaunchKernelGGL(worldReduceKernel, reduceGrid(exec, reduce.items), dim3(kReduceThreads),
-                       0, exec->stream, args);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return queueBatch(exec, (const void *)&worldReduceKernel, reduceGrid(exec, reduce.items),
+                      kReduceThreads, singleBatch<ReduceArgs>(reduce));
 }
 
 int computeReduce(mwhip_exec *exec, uint64_t handle, bool wait)
 {
-    mwhip_reduce_rec *reduce = findReduce(exec, handle);
-    if (reduce == nullptr) return unknownObject("reduce", handle);
-    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
-    return finishQueued(exec, queueReduce(exec, *reduce), wait);
+    return computeObject(exec, findReduce(exec, handle), "reduce", handle, wait, queueReduce);
 }
 
 // Bytes the step reduces' last run read: per row counted its WorldID cell and
@@ -466,32 +452,16 @@ MWHIP_RT int stepReduceStage(mwhip_exec *exec, const LaunchGraph &lg,
 {
     if (lg.isRender) return 0;
     ReduceArgs args {};
-    uint32_t items = 0;
     double written = 0;
-    for (uint64_t handle : exec->extras.stepReduces) {
-        mwhip_reduce_rec *reduce = findReduce(exec, handle);
-        if (reduce == nullptr || args.numReduces >= MWHIP_MAX_STEP_REDUCES) continue;
-        args.items[args.numReduces] = reduce->items;
-        args.plans[args.numReduces] = reduce->planDev;
-        args.numReduces += 1;
-        items += reduce->items;
-        written += (double)reduce->numWorlds * (4.0 * reduce->numElems + 8.0);
-    }
-    if (args.numReduces == 0) return 0;
-
-    KernelLaunch k;
-    static_assert(sizeof(ReduceArgs) <= sizeof(k.argStorage));
-    k.fn = (const void *)&worldReduceKernel;
-    k.grid = reduceGrid(exec, items);
-    k.block = dim3(kReduceThreads, 1, 1);
-    k.setArgs(args);
-    k.name = "reduce";
-    k.role = "reduce";
-    k.kind = MWHIP_NODE_RECYCLE;
-    k.fixedBytes = written;
-    // what the step reduces read: from the counts they just left
-    k.measuredBytes = &stepReduceReadBytes;
-    out.push_back(k);
+    const uint32_t items = collectStepBatch(
+        exec->extras.stepReduces, exec->reduces, args, [&](const mwhip_reduce_rec &reduce) {
+            written += (double)reduce.numWorlds * (4.0 * reduce.numElems + 8.0);
+        });
+    if (args.num_plans == 0) return 0;
+    // (what the step reduces read: from the counts they just left)
+    out.push_back(stageLaunch((const void *)&worldReduceKernel, reduceGrid(exec, items),
+                              kReduceThreads, args, "reduce", "reduce", written,
+                              &stepReduceReadBytes));
     return 0;
 }
 
@@ -652,35 +622,14 @@ extern "C" int mwhip_set_step_reduce(mwhip_exec *exec, uint64_t reduce, int on)
 {
     carryStale(exec);
     if (findReduce(exec, reduce) == nullptr) return unknownObject("reduce", reduce);
-    const std::vector<uint64_t> &step_reduces = exec->extras.stepReduces;
-    const bool is_on =
-        std::find(step_reduces.begin(), step_reduces.end(), reduce) != step_reduces.end();
-    if (is_on == (on != 0)) return 0;
-    if (on != 0 && step_reduces.size() >= MWHIP_MAX_STEP_REDUCES) {
-        return fail(-2, "set_step_reduce: %u step reduces are set already (at most %u)",
-                    (uint32_t)step_reduces.size(), (uint32_t)MWHIP_MAX_STEP_REDUCES);
-    }
-    return changeReplayExtras(exec, [reduce, on](ReplayExtras &extras) {
-        std::vector<uint64_t> &reduces = extras.stepReduces;
-        if (on != 0) {
-            reduces.push_back(reduce);
-        } else {
-            reduces.erase(std::find(reduces.begin(), reduces.end(), reduce));
-        }
-        return 0;
-    });
+    return toggleStepSet(exec, &ReplayExtras::stepReduces, reduce, on, MWHIP_MAX_STEP_REDUCES,
+                         "set_step_reduce", "step reduces");
 }
 
 extern "C" void mwhip_reduce_destroy(mwhip_exec *exec, uint64_t handle)
 {
     carryStale(exec);
-    if (findReduce(exec, handle) == nullptr) return;
-    (void)hipSetDevice(exec->cfg.gpu_id);
-    // (the step graphs must stop naming its buffers before they go; if they
-    // could not be rebuilt without it, it stays until mwhip_destroy)
-    if (mwhip_set_step_reduce(exec, handle, 0) != 0) return;
-    (void)hipStreamSynchronize(exec->stream);
-    exec->reduces.erase(handle);
+    destroyStepObject(exec, &mwhip_exec::reduces, handle, &mwhip_set_step_reduce);
 }
 
 extern "C" int mwhip_reduce_compute(mwhip_exec *exec, uint64_t handle)

@@ -61,11 +61,7 @@ struct ViewPlan {
 };
 
 // by value in the kernel-argument segment, like OutputRingArgs
-struct ViewArgs {
-    uint32_t numViews;
-    uint32_t items[MWHIP_MAX_STEP_VIEWS];       // wavefront work items of each view
-    const ViewPlan *plans[MWHIP_MAX_STEP_VIEWS];
-};
+using ViewArgs = madrona::mwhip::PlanBatch<ViewPlan, MWHIP_MAX_STEP_VIEWS>;
 
 using madrona::mwhip::CopyU4;
 using madrona::mwhip::GlobalU4;
@@ -178,27 +174,12 @@ worldViewKernel(ViewArgs args)
 {
     const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    uint32_t total = 0;
-#pragma unroll
-    for (uint32_t v = 0; v < MWHIP_MAX_STEP_VIEWS; v++) {
-        if (v < args.numViews) total += args.items[v];
-    }
+    const uint32_t total = madrona::mwhip::batchItems(args);
     for (uint32_t item = blockIdx.x * kViewWaves + wave; item < total;
          item += gridDim.x * kViewWaves) {
-        // the view this item belongs to (constant indices: the arguments stay
-        // in scalar registers)
-        const ViewPlan *plan = nullptr;
-        uint32_t rel = item;
-#pragma unroll
-        for (uint32_t v = 0; v < MWHIP_MAX_STEP_VIEWS; v++) {
-            if (plan == nullptr && v < args.numViews) {
-                if (rel < args.items[v]) {
-                    plan = args.plans[v];
-                } else {
-                    rel -= args.items[v];
-                }
-            }
-        }
+        // the view this item belongs to
+        uint32_t rel;
+        const ViewPlan *plan = madrona::mwhip::planOfItem(args, item, &rel);
         if (plan != nullptr) {
             viewWave(plan, rel, lane);
         }
@@ -238,28 +219,18 @@ mwhip_view_rec *findView(mwhip_exec *exec, uint64_t handle)
 
 dim3 viewGrid(mwhip_exec *exec, uint32_t items)
 {
-    const uint32_t blocks = (items + kViewWaves - 1u) / kViewWaves;
-    return dim3(std::max(std::min(blocks, std::max(exec->numCUs, 1u) * 16u), 1u), 1, 1);
+    return waveGrid(exec, items, kViewWaves, 16u);
 }
 
 int queueView(mwhip_exec *exec, mwhip_view_rec &view)
 {
-    ViewArgs args {};
-    args.numViews = 1;
-    args.items[0] = view.items;
-    args.plans[0] = view.planDev;
-    hipLaunchKernelGGL(worldViewKernel, viewGrid(exec, view.items), dim3(kViewThreads), 0,
-                       exec->stream, args);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return queueBatch(exec, (const void *)&worldViewKernel, viewGrid(exec, view.items),
+                      kViewThreads, singleBatch<ViewArgs>(view));
 }
 
 int computeView(mwhip_exec *exec, uint64_t handle, bool wait)
 {
-    mwhip_view_rec *view = findView(exec, handle);
-    if (view == nullptr) return unknownObject("view", handle);
-    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
-    return finishQueued(exec, queueView(exec, *view), wait);
+    return computeObject(exec, findView(exec, handle), "view", handle, wait, queueView);
 }
 
 // Bytes the step views' last run read: the listed cells of the rows it copied
@@ -291,32 +262,15 @@ MWHIP_RT int stepViewStage(mwhip_exec *exec, const LaunchGraph &lg,
 {
     if (lg.isRender) return 0;
     ViewArgs args {};
-    uint32_t items = 0;
     double written = 0;
-    for (uint64_t handle : exec->extras.stepViews) {
-        mwhip_view_rec *view = findView(exec, handle);
-        if (view == nullptr || args.numViews >= MWHIP_MAX_STEP_VIEWS) continue;
-        args.items[args.numViews] = view->items;
-        args.plans[args.numViews] = view->planDev;
-        args.numViews += 1;
-        items += view->items;
-        written += (double)view->numWorlds * ((double)view->maxRows * view->rowBytes + 4.0);
-    }
-    if (args.numViews == 0) return 0;
-
-    KernelLaunch k;
-    static_assert(sizeof(ViewArgs) <= sizeof(k.argStorage));
-    k.fn = (const void *)&worldViewKernel;
-    k.grid = viewGrid(exec, items);
-    k.block = dim3(kViewThreads, 1, 1);
-    k.setArgs(args);
-    k.name = "view";
-    k.role = "view";
-    k.kind = MWHIP_NODE_RECYCLE;
-    k.fixedBytes = written;
-    // what the step views read: from the counts they just left
-    k.measuredBytes = &stepViewReadBytes;
-    out.push_back(k);
+    const uint32_t items = collectStepBatch(
+        exec->extras.stepViews, exec->views, args, [&](const mwhip_view_rec &view) {
+            written += (double)view.numWorlds * ((double)view.maxRows * view.rowBytes + 4.0);
+        });
+    if (args.num_plans == 0) return 0;
+    // (what the step views read: from the counts they just left)
+    out.push_back(stageLaunch((const void *)&worldViewKernel, viewGrid(exec, items), kViewThreads,
+                              args, "view", "view", written, &stepViewReadBytes));
     return 0;
 }
 
@@ -401,34 +355,14 @@ extern "C" int mwhip_set_step_view(mwhip_exec *exec, uint64_t view, int on)
 {
     carryStale(exec);
     if (findView(exec, view) == nullptr) return unknownObject("view", view);
-    const std::vector<uint64_t> &step_views = exec->extras.stepViews;
-    const bool is_on = std::find(step_views.begin(), step_views.end(), view) != step_views.end();
-    if (is_on == (on != 0)) return 0;
-    if (on != 0 && step_views.size() >= MWHIP_MAX_STEP_VIEWS) {
-        return fail(-2, "set_step_view: %u step views are set already (at most %u)",
-                    (uint32_t)step_views.size(), (uint32_t)MWHIP_MAX_STEP_VIEWS);
-    }
-    return changeReplayExtras(exec, [view, on](ReplayExtras &extras) {
-        std::vector<uint64_t> &views = extras.stepViews;
-        if (on != 0) {
-            views.push_back(view);
-        } else {
-            views.erase(std::find(views.begin(), views.end(), view));
-        }
-        return 0;
-    });
+    return toggleStepSet(exec, &ReplayExtras::stepViews, view, on, MWHIP_MAX_STEP_VIEWS,
+                         "set_step_view", "step views");
 }
 
 extern "C" void mwhip_view_destroy(mwhip_exec *exec, uint64_t handle)
 {
     carryStale(exec);
-    if (findView(exec, handle) == nullptr) return;
-    (void)hipSetDevice(exec->cfg.gpu_id);
-    // (the step graphs must stop naming its buffers before they go; if they
-    // could not be rebuilt without it, it stays until mwhip_destroy)
-    if (mwhip_set_step_view(exec, handle, 0) != 0) return;
-    (void)hipStreamSynchronize(exec->stream);
-    exec->views.erase(handle);
+    destroyStepObject(exec, &mwhip_exec::views, handle, &mwhip_set_step_view);
 }
 
 extern "C" int mwhip_view_compute(mwhip_exec *exec, uint64_t handle)

@@ -72,11 +72,7 @@ struct WritePlan {
 };
 
 // by value in the kernel-argument segment, like ViewArgs
-struct WriteArgs {
-    uint32_t numWrites;
-    uint32_t items[MWHIP_MAX_STEP_WRITES];      // wavefront work items of each write
-    const WritePlan *plans[MWHIP_MAX_STEP_WRITES];
-};
+using WriteArgs = madrona::mwhip::PlanBatch<WritePlan, MWHIP_MAX_STEP_WRITES>;
 
 using madrona::mwhip::cellCopy;
 using madrona::mwhip::teamCopy;
@@ -182,27 +178,12 @@ worldWriteKernel(WriteArgs args)
 {
     const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    uint32_t total = 0;
-#pragma unroll
-    for (uint32_t v = 0; v < MWHIP_MAX_STEP_WRITES; v++) {
-        if (v < args.numWrites) total += args.items[v];
-    }
+    const uint32_t total = madrona::mwhip::batchItems(args);
     for (uint32_t item = blockIdx.x * kWriteWaves + wave; item < total;
          item += gridDim.x * kWriteWaves) {
-        // the write this item belongs to (constant indices: the arguments stay
-        // in scalar registers)
-        const WritePlan *plan = nullptr;
-        uint32_t rel = item;
-#pragma unroll
-        for (uint32_t v = 0; v < MWHIP_MAX_STEP_WRITES; v++) {
-            if (plan == nullptr && v < args.numWrites) {
-                if (rel < args.items[v]) {
-                    plan = args.plans[v];
-                } else {
-                    rel -= args.items[v];
-                }
-            }
-        }
+        // the write this item belongs to
+        uint32_t rel;
+        const WritePlan *plan = madrona::mwhip::planOfItem(args, item, &rel);
         if (plan != nullptr) {
             writeWave(plan, rel, lane);
         }
@@ -243,28 +224,18 @@ mwhip_write_rec *findWrite(mwhip_exec *exec, uint64_t handle)
 
 dim3 writeGrid(mwhip_exec *exec, uint32_t items)
 {
-    const uint32_t blocks = (items + kWriteWaves - 1u) / kWriteWaves;
-    return dim3(std::max(std::min(blocks, std::max(exec->numCUs, 1u) * 16u), 1u), 1, 1);
+    return waveGrid(exec, items, kWriteWaves, 16u);
 }
 
 int queueWrite(mwhip_exec *exec, mwhip_write_rec &write)
 {
-    WriteArgs args {};
-    args.numWrites = 1;
-    args.items[0] = write.items;
-    args.plans[0] = write.planDev;
-    hipLaunchKernelGGL(worldWriteKernel, writeGrid(exec, write.items), dim3(kWriteThreads), 0,
-                       exec->stream, args);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return queueBatch(exec, (const void *)&worldWriteKernel, writeGrid(exec, write.items),
+                      kWriteThreads, singleBatch<WriteArgs>(write));
 }
 
 int applyWrite(mwhip_exec *exec, uint64_t handle, bool wait)
 {
-    mwhip_write_rec *write = findWrite(exec, handle);
-    if (write == nullptr) return unknownObject("write", handle);
-    HIPCHK(hipSetDevice(exec->cfg.gpu_id));
-    return finishQueued(exec, queueWrite(exec, *write), wait);
+    return computeObject(exec, findWrite(exec, handle), "write", handle, wait, queueWrite);
 }
 
 // Bytes the step writes' last run moved: the listed cells of the rows it wrote,
@@ -303,29 +274,12 @@ MWHIP_RT int stepWriteStage(mwhip_exec *exec, const LaunchGraph &lg,
 {
     if (lg.isRender) return 0;
     WriteArgs args {};
-    uint32_t items = 0;
-    for (uint64_t handle : exec->extras.stepWrites) {
-        mwhip_write_rec *write = findWrite(exec, handle);
-        if (write == nullptr || args.numWrites >= MWHIP_MAX_STEP_WRITES) continue;
-        args.items[args.numWrites] = write->items;
-        args.plans[args.numWrites] = write->planDev;
-        args.numWrites += 1;
-        items += write->items;
-    }
-    if (args.numWrites == 0) return 0;
-
-    KernelLaunch k;
-    static_assert(sizeof(WriteArgs) <= sizeof(k.argStorage));
-    k.fn = (const void *)&worldWriteKernel;
-    k.grid = writeGrid(exec, items);
-    k.block = dim3(kWriteThreads, 1, 1);
-    k.setArgs(args);
-    k.name = "write";
-    k.role = "write";
-    k.kind = MWHIP_NODE_RECYCLE;
-    // what the step writes moved: from take and the counts they just left
-    k.measuredBytes = &stepWriteBytes;
-    out.push_back(k);
+    const uint32_t items = collectStepBatch(exec->extras.stepWrites, exec->writes, args,
+                                            [](const mwhip_write_rec &) {});
+    if (args.num_plans == 0) return 0;
+    // (what the step writes moved: from take and the counts they just left)
+    out.push_back(stageLaunch((const void *)&worldWriteKernel, writeGrid(exec, items),
+                              kWriteThreads, args, "write", "write", 0.0, &stepWriteBytes));
     return 0;
 }
 
@@ -425,35 +379,14 @@ extern "C" int mwhip_set_step_write(mwhip_exec *exec, uint64_t write, int on)
 {
     carryStale(exec);
     if (findWrite(exec, write) == nullptr) return unknownObject("write", write);
-    const std::vector<uint64_t> &step_writes = exec->extras.stepWrites;
-    const bool is_on =
-        std::find(step_writes.begin(), step_writes.end(), write) != step_writes.end();
-    if (is_on == (on != 0)) return 0;
-    if (on != 0 && step_writes.size() >= MWHIP_MAX_STEP_WRITES) {
-        return fail(-2, "set_step_write: %u step writes are set already (at most %u)",
-                    (uint32_t)step_writes.size(), (uint32_t)MWHIP_MAX_STEP_WRITES);
-    }
-    return changeReplayExtras(exec, [write, on](ReplayExtras &extras) {
-        std::vector<uint64_t> &writes = extras.stepWrites;
-        if (on != 0) {
-            writes.push_back(write);
-        } else {
-            writes.erase(std::find(writes.begin(), writes.end(), write));
-        }
-        return 0;
-    });
+    return toggleStepSet(exec, &ReplayExtras::stepWrites, write, on, MWHIP_MAX_STEP_WRITES,
+                         "set_step_write", "step writes");
 }
 
 extern "C" void mwhip_write_destroy(mwhip_exec *exec, uint64_t handle)
 {
     carryStale(exec);
-    if (findWrite(exec, handle) == nullptr) return;
-    (void)hipSetDevice(exec->cfg.gpu_id);
-    // (the step graphs must stop naming its buffers before they go; if they
-    // could not be rebuilt without it, it stays until mwhip_destroy)
-    if (mwhip_set_step_write(exec, handle, 0) != 0) return;
-    (void)hipStreamSynchronize(exec->stream);
-    exec->writes.erase(handle);
+    destroyStepObject(exec, &mwhip_exec::writes, handle, &mwhip_set_step_write);
 }
 
 extern "C" int mwhip_write_apply(mwhip_exec *exec, uint64_t handle)

@@ -39,6 +39,8 @@
 
 namespace boxq {
 
+using treeq::finiteBits;
+
 struct BundleHead {
     int32_t status;
     int32_t world;
@@ -49,33 +51,13 @@ struct BundleHead {
 __device__ inline BundleHead readBundle(const mwhip_box_plan *plan, const EcsState *S,
                                         uint32_t bundle)
 {
-    BundleHead head { MWHIP_BOXES_OK, 0, 0.f, 0.f, 0.f };
-    const uint32_t bundles_per_world = plan->bundles_per_world;
-    if (bundles_per_world != 0u) {
-        head.world = (int32_t)(bundle / bundles_per_world);
-    } else {
-        head.world = *(const int32_t *)(plan->world_src +
-                                        (uint64_t)bundle * plan->world_stride);
-    }
-    if (head.world < 0 || head.world >= S->numWorlds) {
-        head.status = MWHIP_BOXES_BAD_WORLD;
-    } else if (plan->count_src != nullptr && bundles_per_world != 0u &&
-               (int32_t)(bundle % bundles_per_world) >=
-                   *(const int32_t *)(plan->count_src +
-                                      (uint64_t)(uint32_t)head.world * plan->count_stride)) {
-        head.status = MWHIP_BOXES_SKIPPED;
-    } else {
-        const float *c = (const float *)(plan->centre_src +
-                                         (uint64_t)bundle * plan->centre_stride);
-        head.cx = c[0];
-        head.cy = c[1];
-        head.cz = c[2];
-        if (!rayq::finiteBits(head.cx) || !rayq::finiteBits(head.cy) ||
-                !rayq::finiteBits(head.cz)) {
-            head.status = MWHIP_BOXES_BAD_BOX;
-        }
-    }
-    return head;
+    const treeq::GroupHead head = treeq::readGroupHead(
+        plan->world_src, plan->world_stride, plan->count_src, plan->count_stride,
+        plan->centre_src, plan->centre_stride, plan->bundles_per_world, bundle, S);
+    const int32_t status = head.code == treeq::HeadCode::BadWorld ? MWHIP_BOXES_BAD_WORLD :
+        head.code == treeq::HeadCode::Skipped ? MWHIP_BOXES_SKIPPED :
+        head.code == treeq::HeadCode::BadPoint ? MWHIP_BOXES_BAD_BOX : MWHIP_BOXES_OK;
+    return BundleHead { status, head.world, head.x, head.y, head.z };
 }
 
 // box `box` of a bundle whose head passed: OK or BAD_BOX
@@ -93,8 +75,8 @@ __device__ inline int32_t readBox(const mwhip_box_plan *plan, uint32_t box, floa
     for (int a = 0; a < 3; a++) {
         p_min[a] = c[a] + l[a];
         p_max[a] = c[a] + h[a];
-        ok = ok && rayq::finiteBits(l[a]) && rayq::finiteBits(h[a]) &&
-            rayq::finiteBits(p_min[a]) && rayq::finiteBits(p_max[a]) && p_min[a] <= p_max[a];
+        ok = ok && finiteBits(l[a]) && finiteBits(h[a]) && finiteBits(p_min[a]) &&
+            finiteBits(p_max[a]) && p_min[a] <= p_max[a];
     }
     out->pMin = math::Vector3 { p_min[0], p_min[1], p_min[2] };
     out->pMax = math::Vector3 { p_max[0], p_max[1], p_max[2] };

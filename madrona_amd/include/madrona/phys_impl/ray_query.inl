@@ -32,7 +32,9 @@
 // no spin-waits, no workgroup barrier (the groups only use wave barriers), no
 // workgroup waits for another; plain vector stores.
 
-namespace rayq {
+// what ray queries and box queries (box_query.inl, included behind this file)
+// share on the device
+namespace treeq {
 
 __device__ inline bool finiteBits(float v)
 {
@@ -43,6 +45,56 @@ __device__ inline bool nanBits(float v)
 {
     return (__builtin_bit_cast(uint32_t, v) & 0x7FFFFFFFu) > 0x7F800000u;
 }
+
+enum class HeadCode : int32_t { Ok, BadWorld, Skipped, BadPoint };
+
+struct GroupHead {
+    HeadCode code;
+    int32_t world;
+    float x, y, z;
+};
+
+// World, count and point (a fan's origin, a bundle's centre) of group `group`,
+// read and checked in that order by ONE lane; nothing behind a check that
+// failed is read.  groups_per_world > 0: world = group / groups_per_world, and
+// with a count source the groups at or past their world's count are skipped.
+__device__ inline GroupHead readGroupHead(const char *world_src, uint32_t world_stride,
+                                          const char *count_src, uint32_t count_stride,
+                                          const char *point_src, uint32_t point_stride,
+                                          uint32_t groups_per_world, uint32_t group,
+                                          const EcsState *S)
+{
+    GroupHead head { HeadCode::Ok, 0, 0.f, 0.f, 0.f };
+    if (groups_per_world != 0u) {
+        head.world = (int32_t)(group / groups_per_world);
+    } else {
+        head.world = *(const int32_t *)(world_src + (uint64_t)group * world_stride);
+    }
+    if (head.world < 0 || head.world >= S->numWorlds) {
+        head.code = HeadCode::BadWorld;
+    } else if (count_src != nullptr && groups_per_world != 0u &&
+               (int32_t)(group % groups_per_world) >=
+                   *(const int32_t *)(count_src +
+                                      (uint64_t)(uint32_t)head.world * count_stride)) {
+        head.code = HeadCode::Skipped;
+    } else {
+        const float *p = (const float *)(point_src + (uint64_t)group * point_stride);
+        head.x = p[0];
+        head.y = p[1];
+        head.z = p[2];
+        if (!finiteBits(head.x) || !finiteBits(head.y) || !finiteBits(head.z)) {
+            head.code = HeadCode::BadPoint;
+        }
+    }
+    return head;
+}
+
+}
+
+namespace rayq {
+
+using treeq::finiteBits;
+using treeq::nanBits;
 
 // one wavefront: groups 2 * item and 2 * item + 1 of one query
 __device__ inline void rayWave(const mwhip_ray_plan *plan, uint32_t item, uint32_t lane,
@@ -87,29 +139,16 @@ __device__ inline void rayWave(const mwhip_ray_plan *plan, uint32_t item, uint32
     int32_t world = 0;
     float ox = 0.f, oy = 0.f, oz = 0.f;
     if (valid && lane == leader) {
-        if (fans_per_world != 0u) {
-            world = (int32_t)(fan / fans_per_world);
-        } else {
-            world = *(const int32_t *)(plan->world_src +
-                                       (uint64_t)fan * plan->world_stride);
-        }
-        if (world < 0 || world >= S->numWorlds) {
-            status = MWHIP_RAYS_BAD_WORLD;
-        } else if (plan->count_src != nullptr && fans_per_world != 0u &&
-                   (int32_t)(fan % fans_per_world) >=
-                       *(const int32_t *)(plan->count_src +
-                                          (uint64_t)(uint32_t)world * plan->count_stride)) {
-            status = MWHIP_RAYS_SKIPPED;
-        } else {
-            const float *o = (const float *)(plan->origin_src +
-                                             (uint64_t)fan * plan->origin_stride);
-            ox = o[0];
-            oy = o[1];
-            oz = o[2];
-            if (!finiteBits(ox) || !finiteBits(oy) || !finiteBits(oz)) {
-                status = MWHIP_RAYS_BAD_RAY;
-            }
-        }
+        const treeq::GroupHead head = treeq::readGroupHead(
+            plan->world_src, plan->world_stride, plan->count_src, plan->count_stride,
+            plan->origin_src, plan->origin_stride, fans_per_world, fan, S);
+        status = head.code == treeq::HeadCode::BadWorld ? MWHIP_RAYS_BAD_WORLD :
+            head.code == treeq::HeadCode::Skipped ? MWHIP_RAYS_SKIPPED :
+            head.code == treeq::HeadCode::BadPoint ? MWHIP_RAYS_BAD_RAY : MWHIP_RAYS_MISS;
+        world = head.world;
+        ox = head.x;
+        oy = head.y;
+        oz = head.z;
     }
     // (every lane of the wavefront takes part in the cross-lane reads)
     status = __shfl(status, (int)leader, 64);

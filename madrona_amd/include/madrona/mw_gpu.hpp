@@ -27,7 +27,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <cstdint>
+#include <initializer_list>
 #include <vector>
 
 // Defined by MADRONA_BUILD_MWGPU_ENTRY in the simulator's device TU.
@@ -180,13 +180,14 @@ namespace detail {
 // MWHipWorldReduce, MWHipEntityGather, MWHipEntityScatter, MWHipRayQuery and
 // MWHipBoxQuery share: the move-only handle
 // of an object that belongs to an executor (mwhip_<kind>_create / _destroy,
-// include/mwhip.h).  Kind: { name, destroy(exec, handle) }.
+// include/mwhip.h), the device its buffers are on, and how one of those
+// buffers becomes a py::Tensor.  Kind: { name, destroy(exec, handle) }.
 template <typename Kind>
 class ExecObject {
 public:
-    ExecObject() : exec_(nullptr), handle_(0) {}
+    ExecObject() : exec_(nullptr), handle_(0), gpu_id_(0) {}
     ExecObject(const ExecObject &) = delete;
-    ExecObject(ExecObject &&o) : exec_(o.exec_), handle_(o.handle_)
+    ExecObject(ExecObject &&o) : exec_(o.exec_), handle_(o.handle_), gpu_id_(o.gpu_id_)
     {
         o.exec_ = nullptr;
         o.handle_ = 0;
@@ -207,6 +208,7 @@ public:
             }
             exec_ = o.exec_;
             handle_ = o.handle_;
+            gpu_id_ = o.gpu_id_;
             o.exec_ = nullptr;
             o.handle_ = 0;
         }
@@ -216,7 +218,9 @@ public:
     uint64_t handle() const { return handle_; }
 
 protected:
-    ExecObject(mwhip_exec *exec, uint64_t handle) : exec_(exec), handle_(handle) {}
+    ExecObject(mwhip_exec *exec, uint64_t handle, int32_t gpu_id)
+        : exec_(exec), handle_(handle), gpu_id_(gpu_id)
+    {}
 
     static void req(int rc, const char *what)
     {
@@ -227,8 +231,28 @@ protected:
         }
     }
 
+    using Elem = py::TensorElementType;
+
+    // one of the object's device buffers (nullptr: the runtime refused, and
+    // member `what` fails) as a tensor of up to three dimensions
+    py::Tensor tensor(void *ptr, Elem type, std::initializer_list<uint64_t> dims,
+                      const char *what) const
+    {
+        req(ptr != nullptr ? 0 : -1, what);
+        int64_t shape[3] = {};
+        CountT n = 0;
+        for (uint64_t d : dims) {
+            shape[n++] = (int64_t)d;
+        }
+        return py::Tensor(ptr, type, Span<const int64_t>(shape, n),
+                          Optional<int>::make((int)gpu_id_));
+    }
+
+    uint64_t numWorlds() const { return mwhip_num_worlds(exec_); }
+
     mwhip_exec *exec_;
     uint64_t handle_;
+    int32_t gpu_id_;
 };
 
 struct SnapshotKind {
@@ -294,7 +318,9 @@ public:
     uint64_t numBytes() const { return mwhip_snapshot_bytes(exec_, handle_); }
 
 private:
-    MWHipSnapshot(mwhip_exec *exec, uint64_t snapshot) : ExecObject(exec, snapshot) {}
+    MWHipSnapshot(mwhip_exec *exec, uint64_t snapshot, int32_t gpu_id)
+        : ExecObject(exec, snapshot, gpu_id)
+    {}
 
 friend class MWCudaExecutor;
 };
@@ -331,7 +357,9 @@ public:
     }
 
 private:
-    MWHipDigest(mwhip_exec *exec, uint64_t digest) : ExecObject(exec, digest) {}
+    MWHipDigest(mwhip_exec *exec, uint64_t digest, int32_t gpu_id)
+        : ExecObject(exec, digest, gpu_id)
+    {}
 
 friend class MWCudaExecutor;
 };
@@ -344,7 +372,7 @@ friend class MWCudaExecutor;
 // that made it and must not outlive it.
 class MWHipWorldView : public detail::ExecObject<detail::WorldViewKind> {
 public:
-    MWHipWorldView() : max_rows_(0), gpu_id_(0) {}
+    MWHipWorldView() : max_rows_(0) {}
 
     // waits for the executor's stream
     void compute() { req(mwhip_view_compute(exec_, handle_), "compute"); }
@@ -358,32 +386,24 @@ public:
         uint64_t bytes = 0;
         uint32_t cell = 0;
         void *ptr = mwhip_view_buffer(exec_, handle_, column, &bytes, &cell);
-        req(ptr != nullptr ? 0 : -1, "columnTensor");
-        const int64_t dims[3] = { (int64_t)mwhip_num_worlds(exec_), (int64_t)max_rows_,
-                                  (int64_t)cell };
-        return py::Tensor(ptr, py::TensorElementType::UInt8, Span<const int64_t>(dims, 3),
-                          Optional<int>::make((int)gpu_id_));
+        return tensor(ptr, Elem::UInt8, { numWorlds(), max_rows_, cell }, "columnTensor");
     }
 
     // int32 [worlds]: each world's rows in the table (may exceed maxRows())
     py::Tensor countsTensor() const
     {
-        void *ptr = mwhip_view_counts(exec_, handle_);
-        req(ptr != nullptr ? 0 : -1, "countsTensor");
-        const int64_t dims[1] = { (int64_t)mwhip_num_worlds(exec_) };
-        return py::Tensor(ptr, py::TensorElementType::Int32, Span<const int64_t>(dims, 1),
-                          Optional<int>::make((int)gpu_id_));
+        return tensor(mwhip_view_counts(exec_, handle_), Elem::Int32,
+                      { numWorlds() }, "countsTensor");
     }
 
     uint32_t maxRows() const { return max_rows_; }
 
 private:
     MWHipWorldView(mwhip_exec *exec, uint64_t view, uint32_t max_rows, int32_t gpu_id)
-        : ExecObject(exec, view), max_rows_(max_rows), gpu_id_(gpu_id)
+        : ExecObject(exec, view, gpu_id), max_rows_(max_rows)
     {}
 
     uint32_t max_rows_;
-    int32_t gpu_id_;
 
 friend class MWCudaExecutor;
 };
@@ -402,7 +422,7 @@ friend class MWCudaExecutor;
 // it and must not outlive it.
 class MWHipWorldWrite : public detail::ExecObject<detail::WorldWriteKind> {
 public:
-    MWHipWorldWrite() : max_rows_(0), gpu_id_(0) {}
+    MWHipWorldWrite() : max_rows_(0) {}
 
     // waits for the executor's stream
     void apply() { req(mwhip_write_apply(exec_, handle_), "apply"); }
@@ -416,42 +436,30 @@ public:
         uint64_t bytes = 0;
         uint32_t cell = 0;
         void *ptr = mwhip_write_buffer(exec_, handle_, column, &bytes, &cell);
-        req(ptr != nullptr ? 0 : -1, "columnTensor");
-        const int64_t dims[3] = { (int64_t)mwhip_num_worlds(exec_), (int64_t)max_rows_,
-                                  (int64_t)cell };
-        return py::Tensor(ptr, py::TensorElementType::UInt8, Span<const int64_t>(dims, 3),
-                          Optional<int>::make((int)gpu_id_));
+        return tensor(ptr, Elem::UInt8, { numWorlds(), max_rows_, cell }, "columnTensor");
     }
 
     // int32 [worlds], in: the leading rows of each world to write
     py::Tensor takeTensor() const
     {
-        return perWorld(mwhip_write_take(exec_, handle_), "takeTensor");
+        return tensor(mwhip_write_take(exec_, handle_), Elem::Int32, { numWorlds() }, "takeTensor");
     }
 
     // int32 [worlds], out: each world's rows in the table (may exceed maxRows())
     py::Tensor countsTensor() const
     {
-        return perWorld(mwhip_write_counts(exec_, handle_), "countsTensor");
+        return tensor(mwhip_write_counts(exec_, handle_), Elem::Int32,
+                      { numWorlds() }, "countsTensor");
     }
 
     uint32_t maxRows() const { return max_rows_; }
 
 private:
     MWHipWorldWrite(mwhip_exec *exec, uint64_t write, uint32_t max_rows, int32_t gpu_id)
-        : ExecObject(exec, write), max_rows_(max_rows), gpu_id_(gpu_id)
+        : ExecObject(exec, write, gpu_id), max_rows_(max_rows)
     {}
 
-    py::Tensor perWorld(void *ptr, const char *what) const
-    {
-        req(ptr != nullptr ? 0 : -1, what);
-        const int64_t dims[1] = { (int64_t)mwhip_num_worlds(exec_) };
-        return py::Tensor(ptr, py::TensorElementType::Int32, Span<const int64_t>(dims, 1),
-                          Optional<int>::make((int)gpu_id_));
-    }
-
     uint32_t max_rows_;
-    int32_t gpu_id_;
 
 friend class MWCudaExecutor;
 };
@@ -467,7 +475,7 @@ friend class MWCudaExecutor;
 // executor that made it and must not outlive it.
 class MWHipWorldReduce : public detail::ExecObject<detail::WorldReduceKind> {
 public:
-    MWHipWorldReduce() : num_terms_(0), gpu_id_(0), is_float_ {} {}
+    MWHipWorldReduce() : num_terms_(0), is_float_ {} {}
 
     // waits for the executor's stream
     void compute() { req(mwhip_reduce_compute(exec_, handle_), "compute"); }
@@ -483,23 +491,22 @@ public:
         uint64_t bytes = 0;
         uint32_t elems = 0;
         void *ptr = mwhip_reduce_buffer(exec_, handle_, term, &bytes, &elems);
-        req(ptr != nullptr ? 0 : -1, "termTensor");
-        const int64_t dims[2] = { (int64_t)mwhip_num_worlds(exec_), (int64_t)elems };
-        return py::Tensor(ptr, is_float_[term] ? py::TensorElementType::Float32 :
-                          py::TensorElementType::Int32, Span<const int64_t>(dims, 2),
-                          Optional<int>::make((int)gpu_id_));
+        return tensor(ptr, is_float_[term] ? Elem::Float32 : Elem::Int32,
+                      { numWorlds(), elems }, "termTensor");
     }
 
     // int32 [worlds]: each world's rows in the table
     py::Tensor countsTensor() const
     {
-        return perWorld(mwhip_reduce_counts(exec_, handle_), "countsTensor");
+        return tensor(mwhip_reduce_counts(exec_, handle_), Elem::Int32,
+                      { numWorlds() }, "countsTensor");
     }
 
     // int32 [worlds]: 1 where an alarm term tripped, else 0
     py::Tensor alarmTensor() const
     {
-        return perWorld(mwhip_reduce_alarm(exec_, handle_), "alarmTensor");
+        return tensor(mwhip_reduce_alarm(exec_, handle_), Elem::Int32,
+                      { numWorlds() }, "alarmTensor");
     }
 
     uint32_t numTerms() const { return num_terms_; }
@@ -507,7 +514,7 @@ public:
 private:
     MWHipWorldReduce(mwhip_exec *exec, uint64_t reduce, const mwhip_reduce_term *terms,
                      uint32_t n, int32_t gpu_id)
-        : ExecObject(exec, reduce), num_terms_(n), gpu_id_(gpu_id), is_float_ {}
+        : ExecObject(exec, reduce, gpu_id), num_terms_(n), is_float_ {}
     {
         for (uint32_t i = 0; i < n && i < MWHIP_REDUCE_MAX_TERMS; i++) {
             is_float_[i] = terms[i].dtype == MWHIP_REDUCE_F32 &&
@@ -515,16 +522,7 @@ private:
         }
     }
 
-    py::Tensor perWorld(void *ptr, const char *what) const
-    {
-        req(ptr != nullptr ? 0 : -1, what);
-        const int64_t dims[1] = { (int64_t)mwhip_num_worlds(exec_) };
-        return py::Tensor(ptr, py::TensorElementType::Int32, Span<const int64_t>(dims, 1),
-                          Optional<int>::make((int)gpu_id_));
-    }
-
     uint32_t num_terms_;
-    int32_t gpu_id_;
     bool is_float_[MWHIP_REDUCE_MAX_TERMS];
 
 friend class MWCudaExecutor;
@@ -541,7 +539,7 @@ friend class MWCudaExecutor;
 // Belongs to the executor that made it and must not outlive it, nor its source.
 class MWHipEntityGather : public detail::ExecObject<detail::EntityGatherKind> {
 public:
-    MWHipEntityGather() : num_handles_(0), gpu_id_(0) {}
+    MWHipEntityGather() : num_handles_(0) {}
 
     // waits for the executor's stream
     void compute() { req(mwhip_gather_compute(exec_, handle_), "compute"); }
@@ -555,41 +553,31 @@ public:
         uint64_t bytes = 0;
         uint32_t cell = 0;
         void *ptr = mwhip_gather_buffer(exec_, handle_, column, &bytes, &cell);
-        req(ptr != nullptr ? 0 : -1, "columnTensor");
-        const int64_t dims[2] = { (int64_t)num_handles_, (int64_t)cell };
-        return py::Tensor(ptr, py::TensorElementType::UInt8, Span<const int64_t>(dims, 2),
-                          Optional<int>::make((int)gpu_id_));
+        return tensor(ptr, Elem::UInt8, { num_handles_, cell }, "columnTensor");
     }
 
     // int32 [numHandles()]: the archetype of the entity each handle names, -1: none
     py::Tensor archetypesTensor() const
     {
-        return perHandle(mwhip_gather_archetypes(exec_, handle_), "archetypesTensor");
+        return tensor(mwhip_gather_archetypes(exec_, handle_), Elem::Int32,
+                      { num_handles_ }, "archetypesTensor");
     }
 
     // int32 [numHandles()]: the world that entity is in, -1: none
     py::Tensor worldsTensor() const
     {
-        return perHandle(mwhip_gather_worlds(exec_, handle_), "worldsTensor");
+        return tensor(mwhip_gather_worlds(exec_, handle_), Elem::Int32,
+                      { num_handles_ }, "worldsTensor");
     }
 
     uint64_t numHandles() const { return num_handles_; }
 
 private:
     MWHipEntityGather(mwhip_exec *exec, uint64_t gather, uint64_t num_handles, int32_t gpu_id)
-        : ExecObject(exec, gather), num_handles_(num_handles), gpu_id_(gpu_id)
+        : ExecObject(exec, gather, gpu_id), num_handles_(num_handles)
     {}
 
-    py::Tensor perHandle(void *ptr, const char *what) const
-    {
-        req(ptr != nullptr ? 0 : -1, what);
-        const int64_t dims[1] = { (int64_t)num_handles_ };
-        return py::Tensor(ptr, py::TensorElementType::Int32, Span<const int64_t>(dims, 1),
-                          Optional<int>::make((int)gpu_id_));
-    }
-
     uint64_t num_handles_;
-    int32_t gpu_id_;
 
 friend class MWCudaExecutor;
 };
@@ -606,7 +594,7 @@ friend class MWCudaExecutor;
 // Belongs to the executor that made it and must not outlive it, nor its sources.
 class MWHipRayQuery : public detail::ExecObject<detail::RayQueryKind> {
 public:
-    MWHipRayQuery() : num_fans_(0), num_rays_(0), gpu_id_(0) {}
+    MWHipRayQuery() : num_fans_(0), num_rays_(0) {}
 
     // waits for the executor's stream
     void compute() { req(mwhip_rays_compute(exec_, handle_), "compute"); }
@@ -618,52 +606,47 @@ public:
     // [numRays()][3], float [numRays()]
     py::Tensor worldsTensor() const
     {
-        return tensor(MWHIP_RAYS_BUF_WORLD, py::TensorElementType::Int32, num_fans_, 0,
-                      "worldsTensor");
+        return tensor(buffer(MWHIP_RAYS_BUF_WORLD), Elem::Int32, { num_fans_ }, "worldsTensor");
     }
     py::Tensor originsTensor() const
     {
-        return tensor(MWHIP_RAYS_BUF_ORIGIN, py::TensorElementType::Float32, num_fans_, 3,
-                      "originsTensor");
+        return tensor(buffer(MWHIP_RAYS_BUF_ORIGIN), Elem::Float32,
+                      { num_fans_, 3 }, "originsTensor");
     }
     py::Tensor directionsTensor() const
     {
-        return tensor(MWHIP_RAYS_BUF_DIR, py::TensorElementType::Float32, num_rays_, 3,
-                      "directionsTensor");
+        return tensor(buffer(MWHIP_RAYS_BUF_DIR), Elem::Float32,
+                      { num_rays_, 3 }, "directionsTensor");
     }
     py::Tensor tMaxTensor() const
     {
-        return tensor(MWHIP_RAYS_BUF_T_MAX, py::TensorElementType::Float32, num_rays_, 0,
-                      "tMaxTensor");
+        return tensor(buffer(MWHIP_RAYS_BUF_T_MAX), Elem::Float32, { num_rays_ }, "tMaxTensor");
     }
 
     // outputs: float [numRays()], int32 [numRays()][2] (gen, id), float
     // [numRays()][3], int32 [numRays()]
     py::Tensor hitTTensor() const
     {
-        return tensor(MWHIP_RAYS_BUF_HIT_T, py::TensorElementType::Float32, num_rays_, 0,
-                      "hitTTensor");
+        return tensor(buffer(MWHIP_RAYS_BUF_HIT_T), Elem::Float32, { num_rays_ }, "hitTTensor");
     }
     py::Tensor hitsTensor() const
     {
-        return tensor(MWHIP_RAYS_BUF_HIT, py::TensorElementType::Int32, num_rays_, 2,
-                      "hitsTensor");
+        return tensor(buffer(MWHIP_RAYS_BUF_HIT), Elem::Int32, { num_rays_, 2 }, "hitsTensor");
     }
     py::Tensor normalsTensor() const
     {
-        return tensor(MWHIP_RAYS_BUF_NORMAL, py::TensorElementType::Float32, num_rays_, 3,
-                      "normalsTensor");
+        return tensor(buffer(MWHIP_RAYS_BUF_NORMAL), Elem::Float32,
+                      { num_rays_, 3 }, "normalsTensor");
     }
     py::Tensor statusTensor() const
     {
-        return tensor(MWHIP_RAYS_BUF_STATUS, py::TensorElementType::Int32, num_rays_, 0,
-                      "statusTensor");
+        return tensor(buffer(MWHIP_RAYS_BUF_STATUS), Elem::Int32, { num_rays_ }, "statusTensor");
     }
 
     // the hits as the source of an entity gather or scatter
     mwhip_gather_source handleSource() const
     {
-        void *ptr = mwhip_rays_buffer(exec_, handle_, MWHIP_RAYS_BUF_HIT, nullptr);
+        void *ptr = buffer(MWHIP_RAYS_BUF_HIT);
         req(ptr != nullptr ? 0 : -1, "handleSource");
         return mwhip_gather_source { ptr, num_rays_, 8u, 0u, 1u, 0u };
     }
@@ -674,22 +657,16 @@ public:
 private:
     MWHipRayQuery(mwhip_exec *exec, uint64_t rays, uint64_t num_fans, uint64_t num_rays,
                   int32_t gpu_id)
-        : ExecObject(exec, rays), num_fans_(num_fans), num_rays_(num_rays), gpu_id_(gpu_id)
+        : ExecObject(exec, rays, gpu_id), num_fans_(num_fans), num_rays_(num_rays)
     {}
 
-    py::Tensor tensor(uint32_t which, py::TensorElementType type, uint64_t rows,
-                      int64_t inner, const char *what) const
+    void *buffer(uint32_t which) const
     {
-        void *ptr = mwhip_rays_buffer(exec_, handle_, which, nullptr);
-        req(ptr != nullptr ? 0 : -1, what);
-        const int64_t dims[2] = { (int64_t)rows, inner };
-        return py::Tensor(ptr, type, Span<const int64_t>(dims, inner != 0 ? 2 : 1),
-                          Optional<int>::make((int)gpu_id_));
+        return mwhip_rays_buffer(exec_, handle_, which, nullptr);
     }
 
     uint64_t num_fans_;
     uint64_t num_rays_;
-    int32_t gpu_id_;
 
 friend class MWCudaExecutor;
 };
@@ -707,7 +684,7 @@ friend class MWCudaExecutor;
 // to the executor that made it and must not outlive it, nor its sources.
 class MWHipBoxQuery : public detail::ExecObject<detail::BoxQueryKind> {
 public:
-    MWHipBoxQuery() : num_bundles_(0), num_boxes_(0), max_hits_(0), gpu_id_(0) {}
+    MWHipBoxQuery() : num_bundles_(0), num_boxes_(0), max_hits_(0) {}
 
     // waits for the executor's stream
     void compute() { req(mwhip_boxes_compute(exec_, handle_), "compute"); }
@@ -719,48 +696,43 @@ public:
     // [numBoxes()][3] twice
     py::Tensor worldsTensor() const
     {
-        return tensor(MWHIP_BOXES_BUF_WORLD, py::TensorElementType::Int32, num_bundles_, 0, 0,
-                      "worldsTensor");
+        return tensor(buffer(MWHIP_BOXES_BUF_WORLD), Elem::Int32, { num_bundles_ }, "worldsTensor");
     }
     py::Tensor centresTensor() const
     {
-        return tensor(MWHIP_BOXES_BUF_CENTRE, py::TensorElementType::Float32, num_bundles_, 3,
-                      0, "centresTensor");
+        return tensor(buffer(MWHIP_BOXES_BUF_CENTRE), Elem::Float32,
+                      { num_bundles_, 3 }, "centresTensor");
     }
     py::Tensor loTensor() const
     {
-        return tensor(MWHIP_BOXES_BUF_LO, py::TensorElementType::Float32, num_boxes_, 3, 0,
-                      "loTensor");
+        return tensor(buffer(MWHIP_BOXES_BUF_LO), Elem::Float32, { num_boxes_, 3 }, "loTensor");
     }
     py::Tensor hiTensor() const
     {
-        return tensor(MWHIP_BOXES_BUF_HI, py::TensorElementType::Float32, num_boxes_, 3, 0,
-                      "hiTensor");
+        return tensor(buffer(MWHIP_BOXES_BUF_HI), Elem::Float32, { num_boxes_, 3 }, "hiTensor");
     }
 
     // outputs: int32 [numBoxes()] twice, int32 [numBoxes()][maxHits()][2]
     // (gen, id)
     py::Tensor statusTensor() const
     {
-        return tensor(MWHIP_BOXES_BUF_STATUS, py::TensorElementType::Int32, num_boxes_, 0, 0,
-                      "statusTensor");
+        return tensor(buffer(MWHIP_BOXES_BUF_STATUS), Elem::Int32, { num_boxes_ }, "statusTensor");
     }
     py::Tensor countsTensor() const
     {
-        return tensor(MWHIP_BOXES_BUF_COUNT, py::TensorElementType::Int32, num_boxes_, 0, 0,
-                      "countsTensor");
+        return tensor(buffer(MWHIP_BOXES_BUF_COUNT), Elem::Int32, { num_boxes_ }, "countsTensor");
     }
     py::Tensor hitsTensor() const
     {
-        return tensor(MWHIP_BOXES_BUF_HITS, py::TensorElementType::Int32, num_boxes_,
-                      (int64_t)max_hits_, 2, "hitsTensor");
+        return tensor(buffer(MWHIP_BOXES_BUF_HITS), Elem::Int32,
+                      { num_boxes_, max_hits_, 2 }, "hitsTensor");
     }
 
     // the hits as the source of an entity gather or scatter: numBoxes() x
     // maxHits() handles
     mwhip_gather_source handleSource() const
     {
-        void *ptr = mwhip_boxes_buffer(exec_, handle_, MWHIP_BOXES_BUF_HITS, nullptr);
+        void *ptr = buffer(MWHIP_BOXES_BUF_HITS);
         req(ptr != nullptr ? 0 : -1, "handleSource");
         return mwhip_gather_source { ptr, num_boxes_ * max_hits_, 8u, 0u, 1u, 0u };
     }
@@ -772,25 +744,18 @@ public:
 private:
     MWHipBoxQuery(mwhip_exec *exec, uint64_t boxes, uint64_t num_bundles, uint64_t num_boxes,
                   uint64_t max_hits, int32_t gpu_id)
-        : ExecObject(exec, boxes), num_bundles_(num_bundles), num_boxes_(num_boxes),
-          max_hits_(max_hits), gpu_id_(gpu_id)
+        : ExecObject(exec, boxes, gpu_id), num_bundles_(num_bundles), num_boxes_(num_boxes),
+          max_hits_(max_hits)
     {}
 
-    py::Tensor tensor(uint32_t which, py::TensorElementType type, uint64_t rows,
-                      int64_t inner, int64_t innermost, const char *what) const
+    void *buffer(uint32_t which) const
     {
-        void *ptr = mwhip_boxes_buffer(exec_, handle_, which, nullptr);
-        req(ptr != nullptr ? 0 : -1, what);
-        const int64_t dims[3] = { (int64_t)rows, inner, innermost };
-        return py::Tensor(ptr, type,
-                          Span<const int64_t>(dims, innermost != 0 ? 3 : inner != 0 ? 2 : 1),
-                          Optional<int>::make((int)gpu_id_));
+        return mwhip_boxes_buffer(exec_, handle_, which, nullptr);
     }
 
     uint64_t num_bundles_;
     uint64_t num_boxes_;
     uint64_t max_hits_;
-    int32_t gpu_id_;
 
 friend class MWCudaExecutor;
 };
@@ -808,7 +773,7 @@ friend class MWCudaExecutor;
 // nor its source.
 class MWHipEntityScatter : public detail::ExecObject<detail::EntityScatterKind> {
 public:
-    MWHipEntityScatter() : num_handles_(0), gpu_id_(0) {}
+    MWHipEntityScatter() : num_handles_(0) {}
 
     // waits for the executor's stream
     void apply() { req(mwhip_scatter_apply(exec_, handle_), "apply"); }
@@ -822,53 +787,45 @@ public:
         uint64_t bytes = 0;
         uint32_t cell = 0;
         void *ptr = mwhip_scatter_buffer(exec_, handle_, column, &bytes, &cell);
-        req(ptr != nullptr ? 0 : -1, "columnTensor");
-        const int64_t dims[2] = { (int64_t)num_handles_, (int64_t)cell };
-        return py::Tensor(ptr, py::TensorElementType::UInt8, Span<const int64_t>(dims, 2),
-                          Optional<int>::make((int)gpu_id_));
+        return tensor(ptr, Elem::UInt8, { num_handles_, cell }, "columnTensor");
     }
 
     // int32 [numHandles()]: non-zero where handle i's cells are to be stored (input)
     py::Tensor selectTensor() const
     {
-        return perHandle(mwhip_scatter_select(exec_, handle_), "selectTensor");
+        return tensor(mwhip_scatter_select(exec_, handle_), Elem::Int32,
+                      { num_handles_ }, "selectTensor");
     }
 
     // int32 [numHandles()]: the archetype of the entity each handle names, -1: none
     py::Tensor archetypesTensor() const
     {
-        return perHandle(mwhip_scatter_archetypes(exec_, handle_), "archetypesTensor");
+        return tensor(mwhip_scatter_archetypes(exec_, handle_), Elem::Int32,
+                      { num_handles_ }, "archetypesTensor");
     }
 
     // int32 [numHandles()]: the world that entity is in, -1: none
     py::Tensor worldsTensor() const
     {
-        return perHandle(mwhip_scatter_worlds(exec_, handle_), "worldsTensor");
+        return tensor(mwhip_scatter_worlds(exec_, handle_), Elem::Int32,
+                      { num_handles_ }, "worldsTensor");
     }
 
     // int32 [numHandles()]: 1 where the last apply stored handle i's cells
     py::Tensor writtenTensor() const
     {
-        return perHandle(mwhip_scatter_written(exec_, handle_), "writtenTensor");
+        return tensor(mwhip_scatter_written(exec_, handle_), Elem::Int32,
+                      { num_handles_ }, "writtenTensor");
     }
 
     uint64_t numHandles() const { return num_handles_; }
 
 private:
     MWHipEntityScatter(mwhip_exec *exec, uint64_t scatter, uint64_t num_handles, int32_t gpu_id)
-        : ExecObject(exec, scatter), num_handles_(num_handles), gpu_id_(gpu_id)
+        : ExecObject(exec, scatter, gpu_id), num_handles_(num_handles)
     {}
 
-    py::Tensor perHandle(void *ptr, const char *what) const
-    {
-        req(ptr != nullptr ? 0 : -1, what);
-        const int64_t dims[1] = { (int64_t)num_handles_ };
-        return py::Tensor(ptr, py::TensorElementType::Int32, Span<const int64_t>(dims, 1),
-                          Optional<int>::make((int)gpu_id_));
-    }
-
     uint64_t num_handles_;
-    int32_t gpu_id_;
 
 friend class MWCudaExecutor;
 };
@@ -1159,7 +1116,7 @@ public:
     {
         uint64_t snapshot = 0;
         req(mwhip_snapshot_create(exec_, &snapshot), "makeSnapshot");
-        return MWHipSnapshot(exec_, snapshot);
+        return MWHipSnapshot(exec_, snapshot, gpu_id_);
     }
 
     // a digest of the listed columns of this executor's worlds (see MWHipDigest)
@@ -1168,15 +1125,14 @@ public:
         uint64_t digest = 0;
         req(mwhip_digest_create(exec_, (const mwhip_digest_column *)columns.data(),
             (uint32_t)columns.size(), &digest), "makeDigest");
-        return MWHipDigest(exec_, digest);
+        return MWHipDigest(exec_, digest, gpu_id_);
     }
 
     // every replay of a step graph recomputes `digest` behind its task-graph
     // nodes and before its pack node and output rings; nullptr: none
     void setStepDigest(const MWHipDigest *digest)
     {
-        req(mwhip_set_step_digest(exec_, digest != nullptr ? digest->handle() : 0),
-            "setStepDigest");
+        setStep(mwhip_set_step_digest, digest, "setStepDigest");
     }
 
     // a padded per-world view of `components` of archetype `archetype`'s table,
@@ -1195,8 +1151,7 @@ public:
     // MWHIP_MAX_STEP_VIEWS views, one launch for all); off: no longer
     void setStepView(const MWHipWorldView *view, bool on)
     {
-        req(mwhip_set_step_view(exec_, view != nullptr ? view->handle() : 0, on ? 1 : 0),
-            "setStepView");
+        setStep(mwhip_set_step_view, view, "setStepView", on ? 1 : 0);
     }
 
     // tensors to scatter into `components` of archetype `archetype`'s table
@@ -1215,8 +1170,7 @@ public:
     // writes, one launch for all); off: no longer
     void setStepWrite(const MWHipWorldWrite *write, bool on)
     {
-        req(mwhip_set_step_write(exec_, write != nullptr ? write->handle() : 0, on ? 1 : 0),
-            "setStepWrite");
+        setStep(mwhip_set_step_write, write, "setStepWrite", on ? 1 : 0);
     }
 
     // per-world reductions of archetype `archetype`'s table, one per term (see
@@ -1234,8 +1188,7 @@ public:
     // MWHIP_MAX_STEP_REDUCES reduces, one launch for all); off: no longer
     void setStepReduce(const MWHipWorldReduce *reduce, bool on)
     {
-        req(mwhip_set_step_reduce(exec_, reduce != nullptr ? reduce->handle() : 0, on ? 1 : 0),
-            "setStepReduce");
+        setStep(mwhip_set_step_reduce, reduce, "setStepReduce", on ? 1 : 0);
     }
 
     // the cells of `components` (component ids) of the entities the handles of
@@ -1256,8 +1209,7 @@ public:
     // off: no longer
     void setStepGather(const MWHipEntityGather *gather, bool on)
     {
-        req(mwhip_set_step_gather(exec_, gather != nullptr ? gather->handle() : 0, on ? 1 : 0),
-            "setStepGather");
+        setStep(mwhip_set_step_gather, gather, "setStepGather", on ? 1 : 0);
     }
 
     // cells of `components` (component ids; neither Entity nor WorldID) written
@@ -1278,8 +1230,7 @@ public:
     // components, three launches for all); off: no longer
     void setStepScatter(const MWHipEntityScatter *scatter, bool on)
     {
-        req(mwhip_set_step_scatter(exec_, scatter != nullptr ? scatter->handle() : 0,
-                                   on ? 1 : 0), "setStepScatter");
+        setStep(mwhip_set_step_scatter, scatter, "setStepScatter", on ? 1 : 0);
     }
 
     // desc.num_fans fans of desc.rays_per_fan rays through the worlds'
@@ -1298,8 +1249,7 @@ public:
     // MWHIP_MAX_STEP_RAYS queries, one launch for all); off: no longer
     void setStepRays(const MWHipRayQuery *rays, bool on)
     {
-        req(mwhip_set_step_rays(exec_, rays != nullptr ? rays->handle() : 0, on ? 1 : 0),
-            "setStepRays");
+        setStep(mwhip_set_step_rays, rays, "setStepRays", on ? 1 : 0);
     }
 
     // desc.num_bundles bundles of desc.boxes_per_bundle boxes through the
@@ -1321,8 +1271,7 @@ public:
     // launch for all); off: no longer
     void setStepBoxes(const MWHipBoxQuery *boxes, bool on)
     {
-        req(mwhip_set_step_boxes(exec_, boxes != nullptr ? boxes->handle() : 0, on ? 1 : 0),
-            "setStepBoxes");
+        setStep(mwhip_set_step_boxes, boxes, "setStepBoxes", on ? 1 : 0);
     }
 
     // Device-resident rings (extensions of this backend, include/mwhip.h).
@@ -1368,6 +1317,15 @@ private:
                     mwhip_last_error());
             abort();
         }
+    }
+
+    // mwhip_set_step_<kind>(exec, the handle of obj or 0, on...): the digest's
+    // takes no `on`
+    template <typename Obj, typename... On>
+    void setStep(int (*set)(mwhip_exec *, uint64_t, On...), const Obj *obj, const char *what,
+                 On... on)
+    {
+        req(set(exec_, obj != nullptr ? obj->handle() : 0, on...), what);
     }
 
     mwhip_exec *exec_;

@@ -96,6 +96,11 @@ def _bind(lib: C.CDLL) -> None:
     lib.sim_hip_render_graph.argtypes = [C.c_void_p]
     lib.sim_hip_step_graph.restype = C.c_uint64
     lib.sim_hip_step_graph.argtypes = [C.c_void_p]
+    # (a simulator library built before the accessor was added does not have it:
+    # a reference-backend library an earlier build left behind still loads)
+    if hasattr(lib, "sim_hip_cxx_exec"):
+        lib.sim_hip_cxx_exec.restype = C.c_void_p
+        lib.sim_hip_cxx_exec.argtypes = [C.c_void_p]
     # (a simulator library built before state digests does not have it)
     if hasattr(lib, "sim_hip_column_ids"):
         lib.sim_hip_column_ids.restype = C.c_int
@@ -179,8 +184,40 @@ def _torch_runtime_first() -> None:
         pass
 
 
+_U32P, _U64P = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+_OBJECT = [C.c_void_p, C.c_uint64]      # (the executor, the object's handle)
+
+# The executor objects of include/mwhip.h by the stem of their calls: the verbs
+# (mwhip_<stem>_<verb> and ..._<verb>_async) and the getters of further
+# per-object device pointers (mwhip_<stem>_<getter>).  Each has
+# mwhip_<stem>_destroy, and each but the snapshot mwhip_set_step_<stem>.
+_KINDS = {
+    "snapshot": (("save", "restore"), ()),
+    "digest": (("compute",), ()),
+    "view": (("compute",), ("counts",)),
+    "write": (("apply",), ("take", "counts")),
+    "reduce": (("compute",), ("counts", "alarm")),
+    "gather": (("compute",), ("archetypes", "worlds")),
+    "scatter": (("apply",), ("select", "archetypes", "worlds", "written")),
+    "rays": (("compute",), ()),
+    "boxes": (("compute",), ()),
+}
+
+_runtime = None
+
+
+def _declare(lib: C.CDLL, name: str, restype, argtypes) -> None:
+    fn = getattr(lib, name)
+    fn.restype = restype
+    fn.argtypes = argtypes
+
+
 def runtime_lib() -> C.CDLL:
-    """libmadrona_hip.so (the C ABI of include/mwhip.h)."""
+    """libmadrona_hip.so (the C ABI of include/mwhip.h), opened and declared
+    by the first call."""
+    global _runtime
+    if _runtime is not None:
+        return _runtime
     _torch_runtime_first()
     lib = C.CDLL(os.path.join(HIP_BUILD_DIR, "libmadrona_hip.so"), mode=C.RTLD_GLOBAL)
     lib.mwhip_profile.restype = C.c_int32
@@ -213,140 +250,55 @@ def runtime_lib() -> C.CDLL:
     lib.mwhip_pack_rows.restype = C.c_int
     lib.mwhip_pack_rows.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p),
                                     C.POINTER(C.c_uint32), C.c_uint32, C.c_void_p]
-    lib.mwhip_snapshot_create.restype = C.c_int
-    lib.mwhip_snapshot_create.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-    lib.mwhip_snapshot_destroy.restype = None
-    lib.mwhip_snapshot_destroy.argtypes = [C.c_void_p, C.c_uint64]
-    for fn in (lib.mwhip_snapshot_save, lib.mwhip_snapshot_restore,
-               lib.mwhip_snapshot_save_async, lib.mwhip_snapshot_restore_async):
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_uint64]
-    lib.mwhip_snapshot_bytes.restype = C.c_uint64
-    lib.mwhip_snapshot_bytes.argtypes = [C.c_void_p, C.c_uint64]
-    lib.mwhip_digest_create.restype = C.c_int
-    lib.mwhip_digest_create.argtypes = [C.c_void_p, C.POINTER(DigestColumn), C.c_uint32,
-                                        C.POINTER(C.c_uint64)]
-    lib.mwhip_digest_destroy.restype = None
-    lib.mwhip_digest_destroy.argtypes = [C.c_void_p, C.c_uint64]
-    for fn in (lib.mwhip_digest_compute, lib.mwhip_digest_compute_async,
-               lib.mwhip_set_step_digest):
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_uint64]
-    lib.mwhip_digest_buffer.restype = C.c_void_p
-    lib.mwhip_digest_buffer.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32),
-                                        C.POINTER(C.c_uint32)]
-    lib.mwhip_digest_group.restype = C.c_int
-    lib.mwhip_digest_group.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32,
-                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    lib.mwhip_view_create.restype = C.c_int
-    lib.mwhip_view_create.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32),
-                                      C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
-    lib.mwhip_view_destroy.restype = None
-    lib.mwhip_view_destroy.argtypes = [C.c_void_p, C.c_uint64]
-    for fn in (lib.mwhip_view_compute, lib.mwhip_view_compute_async):
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_uint64]
-    lib.mwhip_view_buffer.restype = C.c_void_p
-    lib.mwhip_view_buffer.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32,
-                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
-    lib.mwhip_view_counts.restype = C.c_void_p
-    lib.mwhip_view_counts.argtypes = [C.c_void_p, C.c_uint64]
-    lib.mwhip_set_step_view.restype = C.c_int
-    lib.mwhip_set_step_view.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
-    lib.mwhip_write_create.restype = C.c_int
-    lib.mwhip_write_create.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32),
-                                       C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
-    lib.mwhip_write_destroy.restype = None
-    lib.mwhip_write_destroy.argtypes = [C.c_void_p, C.c_uint64]
-    for fn in (lib.mwhip_write_apply, lib.mwhip_write_apply_async):
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_uint64]
-    lib.mwhip_write_buffer.restype = C.c_void_p
-    lib.mwhip_write_buffer.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32,
-                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
-    for fn in (lib.mwhip_write_take, lib.mwhip_write_counts):
-        fn.restype = C.c_void_p
-        fn.argtypes = [C.c_void_p, C.c_uint64]
-    lib.mwhip_set_step_write.restype = C.c_int
-    lib.mwhip_set_step_write.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
-    lib.mwhip_reduce_create.restype = C.c_int
-    lib.mwhip_reduce_create.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(ReduceTerm),
-                                        C.c_uint32, C.POINTER(C.c_uint64)]
-    lib.mwhip_reduce_destroy.restype = None
-    lib.mwhip_reduce_destroy.argtypes = [C.c_void_p, C.c_uint64]
-    for fn in (lib.mwhip_reduce_compute, lib.mwhip_reduce_compute_async):
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_uint64]
-    lib.mwhip_reduce_buffer.restype = C.c_void_p
-    lib.mwhip_reduce_buffer.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32,
-                                        C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
-    for fn in (lib.mwhip_reduce_counts, lib.mwhip_reduce_alarm):
-        fn.restype = C.c_void_p
-        fn.argtypes = [C.c_void_p, C.c_uint64]
-    lib.mwhip_set_step_reduce.restype = C.c_int
-    lib.mwhip_set_step_reduce.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
-    lib.mwhip_gather_create.restype = C.c_int
-    lib.mwhip_gather_create.argtypes = [C.c_void_p, C.POINTER(GatherSource),
-                                        C.POINTER(C.c_uint32), C.c_uint32,
-                                        C.POINTER(C.c_uint64)]
-    lib.mwhip_gather_destroy.restype = None
-    lib.mwhip_gather_destroy.argtypes = [C.c_void_p, C.c_uint64]
-    for fn in (lib.mwhip_gather_compute, lib.mwhip_gather_compute_async):
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_uint64]
-    lib.mwhip_gather_buffer.restype = C.c_void_p
-    lib.mwhip_gather_buffer.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32,
-                                        C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
-    for fn in (lib.mwhip_gather_archetypes, lib.mwhip_gather_worlds):
-        fn.restype = C.c_void_p
-        fn.argtypes = [C.c_void_p, C.c_uint64]
-    lib.mwhip_set_step_gather.restype = C.c_int
-    lib.mwhip_set_step_gather.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
-    lib.mwhip_scatter_create.restype = C.c_int
-    lib.mwhip_scatter_create.argtypes = [C.c_void_p, C.POINTER(GatherSource),
-                                         C.POINTER(C.c_uint32), C.c_uint32,
-                                         C.POINTER(C.c_uint64)]
-    lib.mwhip_scatter_destroy.restype = None
-    lib.mwhip_scatter_destroy.argtypes = [C.c_void_p, C.c_uint64]
-    for fn in (lib.mwhip_scatter_apply, lib.mwhip_scatter_apply_async):
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_uint64]
-    lib.mwhip_scatter_buffer.restype = C.c_void_p
-    lib.mwhip_scatter_buffer.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32,
-                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
-    for fn in (lib.mwhip_scatter_select, lib.mwhip_scatter_archetypes,
-               lib.mwhip_scatter_worlds, lib.mwhip_scatter_written):
-        fn.restype = C.c_void_p
-        fn.argtypes = [C.c_void_p, C.c_uint64]
-    lib.mwhip_set_step_scatter.restype = C.c_int
-    lib.mwhip_set_step_scatter.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
-    lib.mwhip_rays_create.restype = C.c_int
-    lib.mwhip_rays_create.argtypes = [C.c_void_p, C.POINTER(RaysDesc), C.POINTER(C.c_uint64)]
-    lib.mwhip_rays_destroy.restype = None
-    lib.mwhip_rays_destroy.argtypes = [C.c_void_p, C.c_uint64]
-    for fn in (lib.mwhip_rays_compute, lib.mwhip_rays_compute_async):
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_uint64]
-    lib.mwhip_rays_buffer.restype = C.c_void_p
-    lib.mwhip_rays_buffer.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
-    lib.mwhip_set_step_rays.restype = C.c_int
-    lib.mwhip_set_step_rays.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
-    lib.mwhip_set_ray_kernel.restype = C.c_int
-    lib.mwhip_set_ray_kernel.argtypes = [C.c_void_p, C.c_void_p]
-    lib.mwhip_boxes_create.restype = C.c_int
-    lib.mwhip_boxes_create.argtypes = [C.c_void_p, C.POINTER(BoxesDesc), C.POINTER(C.c_uint64)]
-    lib.mwhip_boxes_destroy.restype = None
-    lib.mwhip_boxes_destroy.argtypes = [C.c_void_p, C.c_uint64]
-    for fn in (lib.mwhip_boxes_compute, lib.mwhip_boxes_compute_async):
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_uint64]
-    lib.mwhip_boxes_buffer.restype = C.c_void_p
-    lib.mwhip_boxes_buffer.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
-    lib.mwhip_set_step_boxes.restype = C.c_int
-    lib.mwhip_set_step_boxes.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
-    lib.mwhip_set_box_kernel.restype = C.c_int
-    lib.mwhip_set_box_kernel.argtypes = [C.c_void_p, C.c_void_p]
+    # what every kind has ...
+    for stem, (verbs, getters) in _KINDS.items():
+        _declare(lib, f"mwhip_{stem}_destroy", None, _OBJECT)
+        for verb in verbs:
+            _declare(lib, f"mwhip_{stem}_{verb}", C.c_int, _OBJECT)
+            _declare(lib, f"mwhip_{stem}_{verb}_async", C.c_int, _OBJECT)
+        for getter in getters:
+            _declare(lib, f"mwhip_{stem}_{getter}", C.c_void_p, _OBJECT)
+        if stem != "snapshot":
+            # (the executor has one step digest: set by its handle, unset by 0)
+            _declare(lib, f"mwhip_set_step_{stem}", C.c_int,
+                     _OBJECT if stem == "digest" else _OBJECT + [C.c_int])
+    # ... and what is a kind's own: how it is made and how its buffers are asked for
+    _declare(lib, "mwhip_snapshot_create", C.c_int, [C.c_void_p, _U64P])
+    _declare(lib, "mwhip_snapshot_bytes", C.c_uint64, _OBJECT)
+    _declare(lib, "mwhip_digest_create", C.c_int,
+             [C.c_void_p, C.POINTER(DigestColumn), C.c_uint32, _U64P])
+    _declare(lib, "mwhip_digest_buffer", C.c_void_p, _OBJECT + [_U32P, _U32P])
+    _declare(lib, "mwhip_digest_group", C.c_int, _OBJECT + [C.c_uint32, _U32P, _U32P])
+    for stem in ("view", "write"):
+        _declare(lib, f"mwhip_{stem}_create", C.c_int,
+                 [C.c_void_p, C.c_uint32, _U32P, C.c_uint32, C.c_uint32, _U64P])
+    _declare(lib, "mwhip_reduce_create", C.c_int,
+             [C.c_void_p, C.c_uint32, C.POINTER(ReduceTerm), C.c_uint32, _U64P])
+    for stem in ("gather", "scatter"):
+        _declare(lib, f"mwhip_{stem}_create", C.c_int,
+                 [C.c_void_p, C.POINTER(GatherSource), _U32P, C.c_uint32, _U64P])
+    for stem in ("view", "write", "reduce", "gather", "scatter"):
+        _declare(lib, f"mwhip_{stem}_buffer", C.c_void_p, _OBJECT + [C.c_uint32, _U64P, _U32P])
+    for stem, desc in (("rays", RaysDesc), ("boxes", BoxesDesc)):
+        _declare(lib, f"mwhip_{stem}_create", C.c_int, [C.c_void_p, C.POINTER(desc), _U64P])
+        _declare(lib, f"mwhip_{stem}_buffer", C.c_void_p, _OBJECT + [C.c_uint32, _U64P])
+    _declare(lib, "mwhip_set_ray_kernel", C.c_int, [C.c_void_p, C.c_void_p])
+    _declare(lib, "mwhip_set_box_kernel", C.c_int, [C.c_void_p, C.c_void_p])
+    _runtime = lib
     return lib
+
+
+def _verb(verb: str, returns_self: bool, doc: str = None):
+    """Method `verb` of an _ExecObject: mwhip_<stem>_<verb>(executor, handle),
+    checked.  (One frame per call: this is the path of a per-step call.)"""
+    def call(self):
+        handle = self._live()
+        fn, name = self._calls[verb]
+        self._check(fn(self._exec, handle), name)
+        return self if returns_self else None
+    call.__name__ = call.__qualname__ = verb
+    call.__doc__ = doc
+    return call
 
 
 class _Checked:
@@ -371,14 +323,46 @@ class _ExecObject(_Checked):
     executor owns, named by `handle` there, kept in one of the simulator's
     lists (`_list`) while it is open.  close() frees it and takes it off the
     list (a snapshot too, which used to stay on it until the simulator closed); Simulator.close() frees the executor and orphans
-    what is left: close() then does nothing, anything else raises."""
+    what is left: close() then does nothing, anything else raises.
+
+    A kind names its calls by `_stem` (a key of _KINDS) and says in __init__
+    what is its own: _open(sim), _create(what mwhip_<stem>_create takes between
+    the executor and the handle), then its buffers.  The rest is here: the
+    calls by their verb (_verb), the torch tensors over device buffers (_wrap,
+    _int32), which are made once and dropped with the object."""
 
     _kind = "object"    # in messages
-    _destroy = ""       # the runtime's destroy call
+    _stem = ""          # mwhip_<stem>_*
     _list = ""          # the simulator's list of the open ones
+    _lists: List[str] = []      # (every kind's, as the classes are defined)
     _sim = None
     _exec = 0
+    _calls: Dict[str, tuple] = {}
     handle = 0
+
+    def __init_subclass__(cls):
+        if "_list" in vars(cls):
+            _ExecObject._lists.append(cls._list)
+
+    def _open(self, sim: "Simulator") -> None:
+        self._sim = sim
+        self._rt = runtime_lib()
+        self._exec = sim.hip_exec()
+        self._tensors = {}
+        self._every_step = False
+        self.handle = 0
+        # (the runtime's functions are looked up here, once, not by every call)
+        names = {verb + tail: f"mwhip_{self._stem}_{verb}{tail}"
+                 for verb in _KINDS[self._stem][0] for tail in ("", "_async")}
+        if self._stem != "snapshot":
+            names["set_step"] = f"mwhip_set_step_{self._stem}"
+        self._calls = {verb: (getattr(self._rt, name), name) for verb, name in names.items()}
+
+    def _create(self, *args) -> None:
+        handle = C.c_uint64(0)
+        name = f"mwhip_{self._stem}_create"
+        self._check(getattr(self._rt, name)(self._exec, *args, C.byref(handle)), name)
+        self.handle = int(handle.value)
 
     def _live(self) -> int:
         # (the executor pointer dies with the simulator: never passed on then)
@@ -386,20 +370,143 @@ class _ExecObject(_Checked):
             raise RuntimeError(f"this {self._kind} is closed (or its simulator is)")
         return self.handle
 
+    def _pointer(self, getter: str) -> int:
+        """mwhip_<stem>_<getter>: a further device buffer of the object"""
+        return int(getattr(self._rt, f"mwhip_{self._stem}_{getter}")(
+            self._exec, self.handle) or 0)
+
+    def _wrap(self, key, ptr, dtype, shape):
+        if key not in self._tensors:
+            import torch
+
+            from .tensor import DeviceColumn
+            self._tensors[key] = torch.as_tensor(
+                DeviceColumn(ptr, dtype, shape),
+                device=torch.device("cuda", self._sim.gpu_id))
+        return self._tensors[key]
+
+    def _int32(self, name: str, ptr: int, n: int):
+        """torch int32 [n] over a device buffer (no copy)"""
+        self._live()
+        return self._wrap(("", name), ptr, np.int32, (n,))
+
     def _orphan(self) -> None:
         """Simulator.close(): the executor has freed (or is about to free) it."""
         self.handle = 0
         self._exec = 0
         self._sim = None
+        self._tensors = {}
 
     def close(self) -> None:
         if self._sim is not None:
             if self.handle:
-                getattr(self._rt, self._destroy)(self._exec, self.handle)
+                getattr(self._rt, f"mwhip_{self._stem}_destroy")(self._exec, self.handle)
             open_ones = getattr(self._sim, self._list)
             if self in open_ones:
                 open_ones.remove(self)
         self._orphan()
+
+
+class _StepObject(_ExecObject):
+    """An executor object that a step graph can carry: every_step()."""
+
+    def _step_args(self, handle: int, on: bool) -> tuple:
+        return handle, 1 if on else 0
+
+    def every_step(self, on: bool = True) -> None:
+        """Every replay of a step graph computes or applies this object (waits
+        for the stream and rebuilds the launch graphs); on=False turns it off
+        again."""
+        handle = self._live()
+        if not on and not self._every_step:
+            return
+        fn, name = self._calls["set_step"]
+        self._check(fn(self._exec, *self._step_args(handle, on)), name)
+        self._every_step = bool(on)
+        # (the rebuilt graphs are looked up by the same handles)
+
+
+class _Computed:
+    """The verbs of a _StepObject that is computed."""
+
+    compute = _verb("compute", True,
+                    "Rewrites every output in full; waits for the executor's stream.")
+    compute_async = _verb("compute_async", False)
+
+
+class _Applied:
+    """The verbs of a _StepObject that is applied."""
+
+    apply = _verb("apply", True, "Writes into the tables; waits for the executor's stream.")
+    apply_async = _verb("apply_async", False)
+
+
+class _Cells(_StepObject):
+    """A _StepObject with a device buffer of uint8 [*_shape(), cell_bytes] per
+    listed name (a column or a component): mwhip_<stem>_buffer."""
+
+    def _shape(self) -> tuple:
+        raise NotImplementedError
+
+    def _open_buffers(self, names) -> None:
+        buffer = getattr(self._rt, f"mwhip_{self._stem}_buffer")
+        self._buffers = {}
+        for p, name in enumerate(names):
+            nbytes, cell = C.c_uint64(0), C.c_uint32(0)
+            ptr = buffer(self._exec, self.handle, p, C.byref(nbytes), C.byref(cell))
+            assert ptr and nbytes.value == int(np.prod(self._shape())) * cell.value
+            self._buffers[name] = (int(ptr), int(cell.value))
+
+    def buffer_ptr(self, name: str) -> int:
+        """Device address of the [*shape, cell_bytes] bytes of `name`."""
+        self._live()
+        return self._buffers[name][0]
+
+    def cell_bytes(self, name: str) -> int:
+        return self._buffers[name][1]
+
+    def tensor(self, name: str, dtype=None):
+        """torch uint8 [*shape, cell_bytes] over the device buffer of `name` (no
+        copy), or, with a numpy dtype, [*shape, cell_bytes // itemsize] of that
+        type.  shape: worlds, max_rows of a view or a write; N of a gather or a
+        scatter."""
+        self._live()
+        ptr, cell = self._buffers[name]
+        dt = np.dtype(np.uint8 if dtype is None else dtype)
+        if cell % dt.itemsize != 0:
+            raise TypeError(f"{name}: cells of {cell} bytes do not hold whole {dt} items")
+        return self._wrap((name, dt.str), ptr, dt.type, (*self._shape(), cell // dt.itemsize))
+
+
+def _need_column_ids(sim: "Simulator") -> None:
+    if not hasattr(sim.lib, "sim_hip_column_ids"):
+        raise RuntimeError("this simulator library has no sim_hip_column_ids: rebuild it")
+
+
+def _column_ids(sim: "Simulator", idx: int, label=None) -> Tuple[int, int]:
+    """(archetype id, component id) of dump-list column idx; label: how a
+    message names the column"""
+    arch, comp = C.c_uint32(0), C.c_uint32(0)
+    if sim.lib.sim_hip_column_ids(sim.handle, idx, C.byref(arch), C.byref(comp)) != 0:
+        raise RuntimeError(f"sim_hip_column_ids({idx if label is None else label}) failed")
+    return int(arch.value), int(comp.value)
+
+
+def _table_columns(sim: "Simulator", table: str, who: str):
+    """(every dump-list column's name, those of `table`)"""
+    names = [c[0] for c in sim._columns]
+    of_table = [n for n in names if n.split(".", 1)[0] == table]
+    if not of_table:
+        raise KeyError(f"{who}: no table {table!r} in the dump list")
+    return names, of_table
+
+
+def _one_table(sim: "Simulator", names, columns) -> Tuple[int, List[int]]:
+    """(the archetype id, the component ids) of columns of one table"""
+    ids = [_column_ids(sim, names.index(name), name) for name in columns]
+    archetypes = {arch for arch, _ in ids}
+    assert len(archetypes) == 1, archetypes
+    return archetypes.pop(), [comp for _, comp in ids]
 
 
 class Snapshot(_ExecObject):
@@ -412,34 +519,16 @@ class Snapshot(_ExecObject):
     Not rewound: the executor's replay count (the input
     ring's slot position) and the rgb / depth outputs of the render pass."""
 
-    _kind, _destroy, _list = "snapshot", "mwhip_snapshot_destroy", "_snapshots"
+    _kind, _stem, _list = "snapshot", "snapshot", "_snapshots"
 
     def __init__(self, sim: "Simulator"):
-        self._rt = runtime_lib()
-        self._exec = sim.hip_exec()
+        self._open(sim)
         if not self._exec:
             raise RuntimeError("snapshots need the HIP backend")
-        handle = C.c_uint64(0)
-        self._check(self._rt.mwhip_snapshot_create(self._exec, C.byref(handle)),
-                    "mwhip_snapshot_create")
-        self.handle = int(handle.value)
-        self._sim = sim
+        self._create()
 
-    def save(self) -> None:
-        self._check(self._rt.mwhip_snapshot_save(self._exec, self._live()),
-                    "mwhip_snapshot_save")
-
-    def restore(self) -> None:
-        self._check(self._rt.mwhip_snapshot_restore(self._exec, self._live()),
-                    "mwhip_snapshot_restore")
-
-    def save_async(self) -> None:
-        self._check(self._rt.mwhip_snapshot_save_async(self._exec, self._live()),
-                    "mwhip_snapshot_save_async")
-
-    def restore_async(self) -> None:
-        self._check(self._rt.mwhip_snapshot_restore_async(self._exec, self._live()),
-                    "mwhip_snapshot_restore_async")
+    save, restore = _verb("save", False), _verb("restore", False)
+    save_async, restore_async = _verb("save_async", False), _verb("restore_async", False)
 
     @property
     def nbytes(self) -> int:
@@ -465,6 +554,8 @@ class Trajectory(_Checked):
     already records is refused (ValueError) rather than taken over.  close()
     removes the rings and lets the simulator forget the trajectory;
     Simulator.close() orphans what is left (the tensors stay valid)."""
+
+    _list = "_trajectories"     # the simulator's list of the open ones
 
     def __init__(self, sim: "Simulator", names: List[str], steps: int,
                  on_render: bool = False):
@@ -555,7 +646,7 @@ class Trajectory(_Checked):
             self._open_in = None
 
 
-class StateDigest(_ExecObject):
+class StateDigest(_Computed, _StepObject):
     """A 64-bit hash per world of a list of dump-list columns, one row of
     hashes per table the list names (madrona_amd/digest_ref.py is the exact
     definition; mwhip_digest_*, include/mwhip.h, computes it on the device).
@@ -572,7 +663,7 @@ class StateDigest(_ExecObject):
     `buffer_ptr` records the digest of every step).  close() frees it;
     Simulator.close() orphans what is left."""
 
-    _kind, _destroy, _list = "digest", "mwhip_digest_destroy", "_digests"
+    _kind, _stem, _list = "digest", "digest", "_digests"
 
     def __init__(self, sim: "Simulator", columns=None):
         names = [c[0] for c in sim._columns]
@@ -588,31 +679,18 @@ class StateDigest(_ExecObject):
             raise ValueError("digest(): no columns")
         if len(set(self._indices)) != len(self._indices):
             raise ValueError("digest(): a column is listed twice")
-        self._sim = sim
         self._tables = [names[i].split(".", 1)[0] for i in self._indices]
         self.num_worlds = sim.num_worlds
-        self.handle = 0
-        self._exec = 0
-        self._rt = None
-        self._tensor = None
-        self._every_step = False
         if sim.backend != "hip":
+            # (no executor and no runtime: _rt stays None)
+            self._sim = sim
             self.groups = [key for key, _, _ in digest_ref.plan_groups(self._tables)]
             return
-        if not hasattr(sim.lib, "sim_hip_column_ids"):
-            raise RuntimeError("this simulator library has no sim_hip_column_ids: rebuild it")
-        self._rt = runtime_lib()
-        self._exec = sim.hip_exec()
-        plan = (DigestColumn * len(self._indices))()
-        for p, idx in enumerate(self._indices):
-            arch, comp = C.c_uint32(0), C.c_uint32(0)
-            if sim.lib.sim_hip_column_ids(sim.handle, idx, C.byref(arch), C.byref(comp)) != 0:
-                raise RuntimeError(f"sim_hip_column_ids({idx}) failed")
-            plan[p] = DigestColumn(arch.value, comp.value)
-        handle = C.c_uint64(0)
-        self._check(self._rt.mwhip_digest_create(self._exec, plan, len(self._indices),
-                                                 C.byref(handle)), "mwhip_digest_create")
-        self.handle = int(handle.value)
+        _need_column_ids(sim)
+        self._open(sim)
+        plan = (DigestColumn * len(self._indices))(
+            *[DigestColumn(*_column_ids(sim, idx)) for idx in self._indices])
+        self._create(plan, len(self._indices))
         num_groups, num_worlds = C.c_uint32(0), C.c_uint32(0)
         self.buffer_ptr = int(self._rt.mwhip_digest_buffer(
             self._exec, self.handle, C.byref(num_groups), C.byref(num_worlds)) or 0)
@@ -633,10 +711,6 @@ class StateDigest(_ExecObject):
                                "this needs the HIP backend")
         return handle
 
-    def _orphan(self) -> None:
-        super()._orphan()
-        self._tensor = None
-
     def compute(self) -> np.ndarray:
         """uint64 [groups, worlds]; waits for the executor's stream."""
         if self._rt is None:
@@ -644,8 +718,7 @@ class StateDigest(_ExecObject):
             sim = self._sim
             return digest_ref.digest_of_dump(
                 self._tables, [sim.dump_column(i) for i in self._indices], self.num_worlds)
-        self._check(self._rt.mwhip_digest_compute(self._exec, self._live()),
-                    "mwhip_digest_compute")
+        _Computed.compute(self)
         return self.read()
 
     def read(self) -> np.ndarray:
@@ -655,37 +728,65 @@ class StateDigest(_ExecObject):
         self._sim.sync()
         return self.tensor.cpu().numpy().view(np.uint64)
 
-    def compute_async(self) -> None:
-        handle = self._live()
-        self._check(self._rt.mwhip_digest_compute_async(self._exec, handle),
-                    "mwhip_digest_compute_async")
-
     @property
     def tensor(self):
         """torch int64 [groups, worlds] over the device buffer (no copy)."""
         self._live()
-        if self._tensor is None:
-            import torch
+        return self._wrap("tensor", self.buffer_ptr, np.int64,
+                          (len(self.groups), self.num_worlds))
 
-            from .tensor import DeviceColumn
-            self._tensor = torch.as_tensor(
-                DeviceColumn(self.buffer_ptr, np.int64, (len(self.groups), self.num_worlds)),
-                device=torch.device("cuda", self._sim.gpu_id))
-        return self._tensor
-
-    def every_step(self, on: bool = True) -> None:
-        """Every replay of a step graph recomputes this digest (waits for the
-        stream and rebuilds the launch graphs); on=False turns it off again."""
-        handle = self._live()
-        if not on and not self._every_step:
-            return
-        self._check(self._rt.mwhip_set_step_digest(self._exec, handle if on else 0),
-                    "mwhip_set_step_digest")
-        self._every_step = bool(on)
-        # (the rebuilt graphs are looked up by the same handles)
+    def _step_args(self, handle: int, on: bool) -> tuple:
+        # (the executor has one step digest: set by its handle, unset by 0)
+        return (handle if on else 0,)
 
 
-class WorldView(_ExecObject):
+class _WorldColumns(_Cells):
+    """What WorldView and WorldWrite share: columns of ONE table, named as the
+    dump list names them, per column a device buffer of [worlds, max_rows]
+    cells, and int32 [worlds] counts."""
+
+    _what = ""      # in messages
+
+    def __init__(self, sim: "Simulator", table: str, columns, max_rows: int):
+        names, of_table = _table_columns(sim, table, self._what)
+        _need_column_ids(sim)
+        if columns is None:
+            columns = self._default_columns(sim, names, of_table)
+        columns = list(columns)
+        for name in columns:
+            if name not in of_table:
+                raise KeyError(f"{self._what}: {name!r} is not a column of table {table!r}")
+        if not columns:
+            raise ValueError(f"{self._what}: no columns")
+        if len(set(columns)) != len(columns):
+            raise ValueError(f"{self._what}: a column is listed twice")
+        self._open(sim)
+        self.table = table
+        self.columns = columns
+        self.max_rows = int(max_rows)
+        self.num_worlds = sim.num_worlds
+        self.archetype, comps = _one_table(sim, names, columns)
+        self._create(self.archetype, (C.c_uint32 * len(comps))(*comps), len(comps),
+                     min(max(self.max_rows, 0), 0xFFFFFFFF))
+        self._open_buffers(columns)
+        self.counts_ptr = self._pointer("counts")
+
+    @staticmethod
+    def _default_columns(sim, names, of_table):
+        return of_table
+
+    def _shape(self) -> tuple:
+        return self.num_worlds, self.max_rows
+
+    @property
+    def counts(self):
+        """torch int32 [worlds] over the device buffer (no copy): each world's
+        rows in the table as the last compute or apply found them, which may
+        exceed max_rows."""
+        return self._int32("counts", self.counts_ptr, self.num_worlds)
+
+
+class WorldView(_Computed, _WorldColumns):
     """A dense, zero-padded, world-major copy of columns of ONE table on the
     device: per column uint8 [worlds, max_rows, cell_bytes], plus int32 [worlds]
     row counts that are NOT clipped to max_rows (counts[w] > max_rows: rows were
@@ -699,110 +800,8 @@ class WorldView(_ExecObject):
     records [K, worlds, max_rows, ...]).  close() frees it; Simulator.close()
     orphans what is left."""
 
-    _kind, _destroy, _list = "world view", "mwhip_view_destroy", "_views"
-
-    def __init__(self, sim: "Simulator", table: str, columns, max_rows: int):
-        names = [c[0] for c in sim._columns]
-        of_table = [n for n in names if n.split(".", 1)[0] == table]
-        if not of_table:
-            raise KeyError(f"world_view(): no table {table!r} in the dump list")
-        if columns is None:
-            columns = of_table
-        columns = list(columns)
-        for name in columns:
-            if name not in of_table:
-                raise KeyError(f"world_view(): {name!r} is not a column of table {table!r}")
-        if not columns:
-            raise ValueError("world_view(): no columns")
-        if len(set(columns)) != len(columns):
-            raise ValueError("world_view(): a column is listed twice")
-        if not hasattr(sim.lib, "sim_hip_column_ids"):
-            raise RuntimeError("this simulator library has no sim_hip_column_ids: rebuild it")
-        self._sim = sim
-        self.table = table
-        self.columns = columns
-        self.max_rows = int(max_rows)
-        self.num_worlds = sim.num_worlds
-        self._rt = runtime_lib()
-        self._exec = sim.hip_exec()
-        self._tensors = {}
-        self._every_step = False
-        self.handle = 0
-        archetypes = set()
-        comps = (C.c_uint32 * len(columns))()
-        for p, name in enumerate(columns):
-            arch, comp = C.c_uint32(0), C.c_uint32(0)
-            if sim.lib.sim_hip_column_ids(sim.handle, names.index(name), C.byref(arch),
-                                          C.byref(comp)) != 0:
-                raise RuntimeError(f"sim_hip_column_ids({name}) failed")
-            archetypes.add(arch.value)
-            comps[p] = comp.value
-        assert len(archetypes) == 1, archetypes
-        self.archetype = archetypes.pop()
-        handle = C.c_uint64(0)
-        self._check(self._rt.mwhip_view_create(
-            self._exec, self.archetype, comps, len(columns),
-            min(max(self.max_rows, 0), 0xFFFFFFFF), C.byref(handle)), "mwhip_view_create")
-        self.handle = int(handle.value)
-        self._buffers = {}
-        for p, name in enumerate(columns):
-            nbytes, cell = C.c_uint64(0), C.c_uint32(0)
-            ptr = self._rt.mwhip_view_buffer(self._exec, self.handle, p, C.byref(nbytes),
-                                             C.byref(cell))
-            assert ptr and nbytes.value == self.num_worlds * self.max_rows * cell.value
-            self._buffers[name] = (int(ptr), int(cell.value))
-        self.counts_ptr = int(self._rt.mwhip_view_counts(self._exec, self.handle) or 0)
-
-    def _orphan(self) -> None:
-        super()._orphan()
-        self._tensors = {}
-
-    def compute(self) -> "WorldView":
-        """Rewrites every buffer and the counts; waits for the executor's stream."""
-        self._check(self._rt.mwhip_view_compute(self._exec, self._live()),
-                    "mwhip_view_compute")
-        return self
-
-    def compute_async(self) -> None:
-        self._check(self._rt.mwhip_view_compute_async(self._exec, self._live()),
-                    "mwhip_view_compute_async")
-
-    def buffer_ptr(self, name: str) -> int:
-        """Device address of column `name`'s [worlds, max_rows, cell_bytes] bytes."""
-        self._live()
-        return self._buffers[name][0]
-
-    def cell_bytes(self, name: str) -> int:
-        return self._buffers[name][1]
-
-    def _wrap(self, key, ptr, dtype, shape):
-        if key not in self._tensors:
-            import torch
-
-            from .tensor import DeviceColumn
-            self._tensors[key] = torch.as_tensor(
-                DeviceColumn(ptr, dtype, shape),
-                device=torch.device("cuda", self._sim.gpu_id))
-        return self._tensors[key]
-
-    def tensor(self, name: str, dtype=None):
-        """torch uint8 [worlds, max_rows, cell_bytes] over the device buffer of
-        column `name` (no copy), or, with a numpy dtype, [worlds, max_rows,
-        cell_bytes // itemsize] of that type."""
-        self._live()
-        ptr, cell = self._buffers[name]
-        dt = np.dtype(np.uint8 if dtype is None else dtype)
-        if cell % dt.itemsize != 0:
-            raise TypeError(f"{name}: cells of {cell} bytes do not hold whole {dt} items")
-        return self._wrap((name, dt.str), ptr, dt.type,
-                          (self.num_worlds, self.max_rows, cell // dt.itemsize))
-
-    @property
-    def counts(self):
-        """torch int32 [worlds] over the device buffer (no copy): each world's
-        rows in the table, which may exceed max_rows."""
-        self._live()
-        return self._wrap(("", "counts"), self.counts_ptr, np.int32, (self.num_worlds,))
+    _kind, _stem, _list = "world view", "view", "_views"
+    _what = "world_view()"
 
     def handle_source(self, name: str, first_byte: int = 0, handles: int = 1):
         """The slab of column `name` as a source of Simulator.entity_gather():
@@ -817,18 +816,8 @@ class WorldView(_ExecObject):
                              f"cells of {cell} bytes")
         return (ptr, self.num_worlds * self.max_rows, cell, int(first_byte), int(handles))
 
-    def every_step(self, on: bool = True) -> None:
-        """Every replay of a step graph recomputes this view (waits for the
-        stream and rebuilds the launch graphs); on=False turns it off again."""
-        handle = self._live()
-        if not on and not self._every_step:
-            return
-        self._check(self._rt.mwhip_set_step_view(self._exec, handle, 1 if on else 0),
-                    "mwhip_set_step_view")
-        self._every_step = bool(on)
 
-
-class WorldWrite(_ExecObject):
+class WorldWrite(_Applied, _WorldColumns):
     """The inverse of a WorldView: tensors on the device that are scattered
     into columns of ONE table.  Per column uint8 [worlds, max_rows, cell_bytes]
     (tensor(name): exactly the layout of a WorldView of the same columns and
@@ -854,87 +843,17 @@ class WorldWrite(_ExecObject):
     feeds K queued steps K different injections.  close() frees it;
     Simulator.close() orphans what is left."""
 
-    _kind, _destroy, _list = "world write", "mwhip_write_destroy", "_writes"
+    _kind, _stem, _list = "world write", "write", "_writes"
+    _what = "world_write()"
 
     def __init__(self, sim: "Simulator", table: str, columns, max_rows: int):
-        names = [c[0] for c in sim._columns]
-        of_table = [n for n in names if n.split(".", 1)[0] == table]
-        if not of_table:
-            raise KeyError(f"world_write(): no table {table!r} in the dump list")
-        if not hasattr(sim.lib, "sim_hip_column_ids"):
-            raise RuntimeError("this simulator library has no sim_hip_column_ids: rebuild it")
+        super().__init__(sim, table, columns, max_rows)
+        self._take_ptr = self._pointer("take")
 
-        def ids(name):
-            arch, comp = C.c_uint32(0), C.c_uint32(0)
-            if sim.lib.sim_hip_column_ids(sim.handle, names.index(name), C.byref(arch),
-                                          C.byref(comp)) != 0:
-                raise RuntimeError(f"sim_hip_column_ids({name}) failed")
-            return arch.value, comp.value
-
-        if columns is None:
-            # (component 0 is Entity, 1 is WorldID: include/mwhip.h)
-            columns = [n for n in of_table if ids(n)[1] not in (0, 1)]
-        columns = list(columns)
-        for name in columns:
-            if name not in of_table:
-                raise KeyError(f"world_write(): {name!r} is not a column of table {table!r}")
-        if not columns:
-            raise ValueError("world_write(): no columns")
-        if len(set(columns)) != len(columns):
-            raise ValueError("world_write(): a column is listed twice")
-        self._sim = sim
-        self.table = table
-        self.columns = columns
-        self.max_rows = int(max_rows)
-        self.num_worlds = sim.num_worlds
-        self._rt = runtime_lib()
-        self._exec = sim.hip_exec()
-        self._tensors = {}
-        self._every_step = False
-        self.handle = 0
-        archetypes = set()
-        comps = (C.c_uint32 * len(columns))()
-        for p, name in enumerate(columns):
-            arch, comps[p] = ids(name)
-            archetypes.add(arch)
-        assert len(archetypes) == 1, archetypes
-        self.archetype = archetypes.pop()
-        handle = C.c_uint64(0)
-        self._check(self._rt.mwhip_write_create(
-            self._exec, self.archetype, comps, len(columns),
-            min(max(self.max_rows, 0), 0xFFFFFFFF), C.byref(handle)), "mwhip_write_create")
-        self.handle = int(handle.value)
-        self._buffers = {}
-        for p, name in enumerate(columns):
-            nbytes, cell = C.c_uint64(0), C.c_uint32(0)
-            ptr = self._rt.mwhip_write_buffer(self._exec, self.handle, p, C.byref(nbytes),
-                                              C.byref(cell))
-            assert ptr and nbytes.value == self.num_worlds * self.max_rows * cell.value
-            self._buffers[name] = (int(ptr), int(cell.value))
-        self._take_ptr = int(self._rt.mwhip_write_take(self._exec, self.handle) or 0)
-        self.counts_ptr = int(self._rt.mwhip_write_counts(self._exec, self.handle) or 0)
-
-    def _orphan(self) -> None:
-        super()._orphan()
-        self._tensors = {}
-
-    def apply(self) -> "WorldWrite":
-        """Writes the table; waits for the executor's stream."""
-        self._check(self._rt.mwhip_write_apply(self._exec, self._live()),
-                    "mwhip_write_apply")
-        return self
-
-    def apply_async(self) -> None:
-        self._check(self._rt.mwhip_write_apply_async(self._exec, self._live()),
-                    "mwhip_write_apply_async")
-
-    def buffer_ptr(self, name: str) -> int:
-        """Device address of column `name`'s [worlds, max_rows, cell_bytes] bytes."""
-        self._live()
-        return self._buffers[name][0]
-
-    def cell_bytes(self, name: str) -> int:
-        return self._buffers[name][1]
+    @staticmethod
+    def _default_columns(sim, names, of_table):
+        # (component 0 is Entity, 1 is WorldID: include/mwhip.h)
+        return [n for n in of_table if _column_ids(sim, names.index(n), n)[1] not in (0, 1)]
 
     @property
     def take_ptr(self) -> int:
@@ -942,46 +861,14 @@ class WorldWrite(_ExecObject):
         self._live()
         return self._take_ptr
 
-    _wrap = WorldView._wrap
-
-    def tensor(self, name: str, dtype=None):
-        """torch uint8 [worlds, max_rows, cell_bytes] over the device buffer of
-        column `name` (no copy), or, with a numpy dtype, [worlds, max_rows,
-        cell_bytes // itemsize] of that type.  The caller fills it."""
-        self._live()
-        ptr, cell = self._buffers[name]
-        dt = np.dtype(np.uint8 if dtype is None else dtype)
-        if cell % dt.itemsize != 0:
-            raise TypeError(f"{name}: cells of {cell} bytes do not hold whole {dt} items")
-        return self._wrap((name, dt.str), ptr, dt.type,
-                          (self.num_worlds, self.max_rows, cell // dt.itemsize))
-
     @property
     def take(self):
         """torch int32 [worlds] over the device buffer (no copy): the leading
         rows of each world to write.  The caller fills it."""
-        self._live()
-        return self._wrap(("", "take"), self._take_ptr, np.int32, (self.num_worlds,))
-
-    @property
-    def counts(self):
-        """torch int32 [worlds] over the device buffer (no copy): each world's
-        rows in the table as the last apply found them, not clipped."""
-        self._live()
-        return self._wrap(("", "counts"), self.counts_ptr, np.int32, (self.num_worlds,))
-
-    def every_step(self, on: bool = True) -> None:
-        """Every replay of a step graph applies this write first (waits for the
-        stream and rebuilds the launch graphs); on=False turns it off again."""
-        handle = self._live()
-        if not on and not self._every_step:
-            return
-        self._check(self._rt.mwhip_set_step_write(self._exec, handle, 1 if on else 0),
-                    "mwhip_set_step_write")
-        self._every_step = bool(on)
+        return self._int32("take", self._take_ptr, self.num_worlds)
 
 
-class WorldReduce(_ExecObject):
+class WorldReduce(_Computed, _StepObject):
     """One number per world, element and term about ONE table, on the device:
     per term a [worlds, elems] tensor of sums, minima, maxima, largest
     magnitudes, counts of non-zero or of non-finite values over each world's
@@ -1006,18 +893,14 @@ class WorldReduce(_ExecObject):
     this step's alarms to the next queued step).  close() frees it;
     Simulator.close() orphans what is left."""
 
-    _kind, _destroy, _list = "world reduce", "mwhip_reduce_destroy", "_reduces"
+    _kind, _stem, _list = "world reduce", "reduce", "_reduces"
 
     def __init__(self, sim: "Simulator", table: str, terms):
         from . import reduce_ref
 
         info = {c[0]: c for c in sim._columns}
-        names = list(info)
-        of_table = [n for n in names if n.split(".", 1)[0] == table]
-        if not of_table:
-            raise KeyError(f"world_reduce(): no table {table!r} in the dump list")
-        if not hasattr(sim.lib, "sim_hip_column_ids"):
-            raise RuntimeError("this simulator library has no sim_hip_column_ids: rebuild it")
+        names, of_table = _table_columns(sim, table, "world_reduce()")
+        _need_column_ids(sim)
         terms = list(terms)
         if not terms:
             raise ValueError("world_reduce(): no terms")
@@ -1046,32 +929,17 @@ class WorldReduce(_ExecObject):
             if options:
                 raise TypeError(f"world_reduce(): unknown options {sorted(options)}")
             self.terms.append((column, term))
-        self._sim = sim
+        self._open(sim)
         self.table = table
         self.num_worlds = sim.num_worlds
-        self._rt = runtime_lib()
-        self._exec = sim.hip_exec()
-        self._tensors = {}
-        self._every_step = False
-        self.handle = 0
-        archetypes = set()
-        arr = (ReduceTerm * len(self.terms))()
-        for p, (column, term) in enumerate(self.terms):
-            arch, comp = C.c_uint32(0), C.c_uint32(0)
-            if sim.lib.sim_hip_column_ids(sim.handle, names.index(column), C.byref(arch),
-                                          C.byref(comp)) != 0:
-                raise RuntimeError(f"sim_hip_column_ids({column}) failed")
-            archetypes.add(arch.value)
-            arr[p] = ReduceTerm(comp.value, min(max(term.offset, 0), 0xFFFFFFFF),
-                                min(max(term.elems, 0), 0xFFFFFFFF),
-                                reduce_ref.DTYPES[term.dtype], reduce_ref.OPS[term.op],
-                                reduce_ref.ALARM if term.alarm else 0, term.limit)
-        assert len(archetypes) == 1, archetypes
-        self.archetype = archetypes.pop()
-        handle = C.c_uint64(0)
-        self._check(self._rt.mwhip_reduce_create(self._exec, self.archetype, arr, len(self.terms),
-                                                 C.byref(handle)), "mwhip_reduce_create")
-        self.handle = int(handle.value)
+        self.archetype, comps = _one_table(sim, names, [column for column, _ in self.terms])
+        arr = (ReduceTerm * len(self.terms))(*[
+            ReduceTerm(comp, min(max(term.offset, 0), 0xFFFFFFFF),
+                       min(max(term.elems, 0), 0xFFFFFFFF),
+                       reduce_ref.DTYPES[term.dtype], reduce_ref.OPS[term.op],
+                       reduce_ref.ALARM if term.alarm else 0, term.limit)
+            for comp, (_, term) in zip(comps, self.terms)])
+        self._create(self.archetype, arr, len(self.terms))
         self._buffers = []
         for p, (_, term) in enumerate(self.terms):
             nbytes, elems = C.c_uint64(0), C.c_uint32(0)
@@ -1080,22 +948,8 @@ class WorldReduce(_ExecObject):
             assert ptr and elems.value == term.elems and \
                 nbytes.value == self.num_worlds * term.elems * 4
             self._buffers.append((int(ptr), reduce_ref.result_dtype(term)))
-        self.counts_ptr = int(self._rt.mwhip_reduce_counts(self._exec, self.handle) or 0)
-        self._alarm_ptr = int(self._rt.mwhip_reduce_alarm(self._exec, self.handle) or 0)
-
-    def _orphan(self) -> None:
-        super()._orphan()
-        self._tensors = {}
-
-    def compute(self) -> "WorldReduce":
-        """Rewrites every buffer; waits for the executor's stream."""
-        self._check(self._rt.mwhip_reduce_compute(self._exec, self._live()),
-                    "mwhip_reduce_compute")
-        return self
-
-    def compute_async(self) -> None:
-        self._check(self._rt.mwhip_reduce_compute_async(self._exec, self._live()),
-                    "mwhip_reduce_compute_async")
+        self.counts_ptr = self._pointer("counts")
+        self._alarm_ptr = self._pointer("alarm")
 
     def buffer_ptr(self, i: int) -> int:
         """Device address of term i's [worlds, elems] results (4 bytes each)."""
@@ -1107,8 +961,6 @@ class WorldReduce(_ExecObject):
         """Device address of the int32 [worlds] alarm buffer."""
         self._live()
         return self._alarm_ptr
-
-    _wrap = WorldView._wrap
 
     def tensor(self, i: int):
         """torch [worlds, elems] over the device buffer of term i (no copy) in
@@ -1122,39 +974,43 @@ class WorldReduce(_ExecObject):
     def counts(self):
         """torch int32 [worlds] over the device buffer (no copy): each world's
         rows in the table as the last compute found them."""
-        self._live()
-        return self._wrap(("", "counts"), self.counts_ptr, np.int32, (self.num_worlds,))
+        return self._int32("counts", self.counts_ptr, self.num_worlds)
 
     @property
     def alarm(self):
         """torch int32 [worlds] over the device buffer (no copy): 1 where an
         alarm term tripped in the last compute, else 0."""
-        self._live()
-        return self._wrap(("", "alarm"), self._alarm_ptr, np.int32, (self.num_worlds,))
-
-    def every_step(self, on: bool = True) -> None:
-        """Every replay of a step graph recomputes this reduce (waits for the
-        stream and rebuilds the launch graphs); on=False turns it off again."""
-        handle = self._live()
-        if not on and not self._every_step:
-            return
-        self._check(self._rt.mwhip_set_step_reduce(self._exec, handle, 1 if on else 0),
-                    "mwhip_set_step_reduce")
-        self._every_step = bool(on)
+        return self._int32("alarm", self._alarm_ptr, self.num_worlds)
 
 
-class _HandleCells(_ExecObject):
+class _HandleCells(_Cells):
     """What EntityGather and EntityScatter share: a source of N handles, a list
     of components named as the dump list names them, per component a device
     buffer of N cells, and int32 [N] archetypes and worlds."""
 
     _what = "entity_gather()"   # in messages
 
+    def __init__(self, sim: "Simulator", source, components):
+        comps, components = self._component_list(sim, components)
+        # (a tensor stays where it is while the object exists)
+        self._source, ptr, num_records, record_bytes, first_byte, per = \
+            self._handle_source(source)
+        self._open(sim)
+        self.components = components
+        self.num_handles = num_records * per
+        src = GatherSource(ptr, num_records, record_bytes, first_byte, per, 0)
+        self._create(C.byref(src), comps, len(components))
+        self._open_buffers(components)
+        self.archetypes_ptr = self._pointer("archetypes")
+        self.worlds_ptr = self._pointer("worlds")
+
+    def _shape(self) -> tuple:
+        return (self.num_handles,)
+
     @classmethod
     def _component_list(cls, sim: "Simulator", components):
         """(the component ids as a C array, the names as a list)"""
-        if not hasattr(sim.lib, "sim_hip_column_ids"):
-            raise RuntimeError("this simulator library has no sim_hip_column_ids: rebuild it")
+        _need_column_ids(sim)
         components = list(components)
         if len(set(components)) != len(components):
             raise ValueError(f"{cls._what}: a component is listed twice")
@@ -1195,10 +1051,7 @@ class _HandleCells(_ExecObject):
         for idx, column in enumerate(sim._columns):
             if column[0].split(".", 1)[-1] != name:
                 continue
-            arch, comp = C.c_uint32(0), C.c_uint32(0)
-            if sim.lib.sim_hip_column_ids(sim.handle, idx, C.byref(arch), C.byref(comp)) != 0:
-                raise RuntimeError(f"sim_hip_column_ids({column[0]}) failed")
-            ids.add(int(comp.value))
+            ids.add(_column_ids(sim, idx, column[0])[1])
         if not ids:
             raise KeyError(f"{cls._what}: no column of the dump list is named "
                            f"'<table>.{name}'")
@@ -1209,48 +1062,22 @@ class _HandleCells(_ExecObject):
 
     def _orphan(self) -> None:
         super()._orphan()
-        self._tensors = {}
         self._source = None
-
-    def buffer_ptr(self, name: str) -> int:
-        """Device address of component `name`'s [N, cell_bytes] bytes."""
-        self._live()
-        return self._buffers[name][0]
-
-    def cell_bytes(self, name: str) -> int:
-        return self._buffers[name][1]
-
-    _wrap = WorldView._wrap
-
-    def tensor(self, name: str, dtype=None):
-        """torch uint8 [N, cell_bytes] over the device buffer of component
-        `name` (no copy), or, with a numpy dtype, [N, cell_bytes // itemsize]
-        of that type."""
-        self._live()
-        ptr, cell = self._buffers[name]
-        dt = np.dtype(np.uint8 if dtype is None else dtype)
-        if cell % dt.itemsize != 0:
-            raise TypeError(f"{name}: cells of {cell} bytes do not hold whole {dt} items")
-        return self._wrap((name, dt.str), ptr, dt.type,
-                          (self.num_handles, cell // dt.itemsize))
 
     @property
     def archetypes(self):
         """torch int32 [N] over the device buffer (no copy): the archetype of
         the entity each handle names, -1 where it names nothing."""
-        self._live()
-        return self._wrap(("", "archetypes"), self.archetypes_ptr, np.int32,
-                          (self.num_handles,))
+        return self._int32("archetypes", self.archetypes_ptr, self.num_handles)
 
     @property
     def worlds(self):
         """torch int32 [N] over the device buffer (no copy): the world of the
         entity each handle names, -1 where it names nothing."""
-        self._live()
-        return self._wrap(("", "worlds"), self.worlds_ptr, np.int32, (self.num_handles,))
+        return self._int32("worlds", self.worlds_ptr, self.num_handles)
 
 
-class EntityGather(_HandleCells):
+class EntityGather(_Computed, _HandleCells):
     """The cells of the entities that N handles in device memory name: per
     listed component uint8 [N, cell_bytes] (zero where a handle names nothing
     or its table has no such column), plus int32 [N] `archetypes` and `worlds`
@@ -1268,60 +1095,10 @@ class EntityGather(_HandleCells):
     buffer_ptr(name) records [K, N, ...].  close() frees it; Simulator.close()
     orphans what is left."""
 
-    _kind, _destroy, _list = "entity gather", "mwhip_gather_destroy", "_gathers"
-
-    def __init__(self, sim: "Simulator", source, components):
-        comps, components = self._component_list(sim, components)
-        # (a tensor stays where it is while the gather exists)
-        self._source, ptr, num_records, record_bytes, first_byte, per = \
-            self._handle_source(source)
-        self._sim = sim
-        self.components = components
-        self.num_handles = num_records * per
-        self._rt = runtime_lib()
-        self._exec = sim.hip_exec()
-        self._tensors = {}
-        self._every_step = False
-        self.handle = 0
-        src = GatherSource(ptr, num_records, record_bytes, first_byte, per, 0)
-        handle = C.c_uint64(0)
-        self._check(self._rt.mwhip_gather_create(self._exec, C.byref(src), comps,
-                                                 len(components), C.byref(handle)),
-                    "mwhip_gather_create")
-        self.handle = int(handle.value)
-        self._buffers = {}
-        for p, name in enumerate(components):
-            nbytes, cell = C.c_uint64(0), C.c_uint32(0)
-            buf = self._rt.mwhip_gather_buffer(self._exec, self.handle, p, C.byref(nbytes),
-                                               C.byref(cell))
-            assert buf and nbytes.value == self.num_handles * cell.value
-            self._buffers[name] = (int(buf), int(cell.value))
-        self.archetypes_ptr = int(self._rt.mwhip_gather_archetypes(self._exec, self.handle) or 0)
-        self.worlds_ptr = int(self._rt.mwhip_gather_worlds(self._exec, self.handle) or 0)
-
-    def compute(self) -> "EntityGather":
-        """Rewrites every buffer, archetypes and worlds; waits for the
-        executor's stream."""
-        self._check(self._rt.mwhip_gather_compute(self._exec, self._live()),
-                    "mwhip_gather_compute")
-        return self
-
-    def compute_async(self) -> None:
-        self._check(self._rt.mwhip_gather_compute_async(self._exec, self._live()),
-                    "mwhip_gather_compute_async")
-
-    def every_step(self, on: bool = True) -> None:
-        """Every replay of a step graph recomputes this gather (waits for the
-        stream and rebuilds the launch graphs); on=False turns it off again."""
-        handle = self._live()
-        if not on and not self._every_step:
-            return
-        self._check(self._rt.mwhip_set_step_gather(self._exec, handle, 1 if on else 0),
-                    "mwhip_set_step_gather")
-        self._every_step = bool(on)
+    _kind, _stem, _list = "entity gather", "gather", "_gathers"
 
 
-class EntityScatter(_HandleCells):
+class EntityScatter(_Applied, _HandleCells):
     """The batched ctx.get<T>(e) = v: per listed component a device buffer of N
     cells (tensor(name), uint8 [N, cell_bytes]) and int32 [N] `select`, filled
     by the caller; apply() stores cell i into the entity that handle i of the
@@ -1343,77 +1120,101 @@ class EntityScatter(_HandleCells):
     apply of the replay it runs in.  Step scatters list disjoint components.
     close() frees it; Simulator.close() orphans what is left."""
 
-    _kind, _destroy, _list = "entity scatter", "mwhip_scatter_destroy", "_scatters"
+    _kind, _stem, _list = "entity scatter", "scatter", "_scatters"
     _what = "entity_scatter()"
 
     def __init__(self, sim: "Simulator", source, components):
-        comps, components = self._component_list(sim, components)
-        self._source, ptr, num_records, record_bytes, first_byte, per = \
-            self._handle_source(source)
-        self._sim = sim
-        self.components = components
-        self.num_handles = num_records * per
-        self._rt = runtime_lib()
-        self._exec = sim.hip_exec()
-        self._tensors = {}
-        self._every_step = False
-        self.handle = 0
-        src = GatherSource(ptr, num_records, record_bytes, first_byte, per, 0)
-        handle = C.c_uint64(0)
-        self._check(self._rt.mwhip_scatter_create(self._exec, C.byref(src), comps,
-                                                  len(components), C.byref(handle)),
-                    "mwhip_scatter_create")
-        self.handle = int(handle.value)
-        self._buffers = {}
-        for p, name in enumerate(components):
-            nbytes, cell = C.c_uint64(0), C.c_uint32(0)
-            buf = self._rt.mwhip_scatter_buffer(self._exec, self.handle, p, C.byref(nbytes),
-                                                C.byref(cell))
-            assert buf and nbytes.value == self.num_handles * cell.value
-            self._buffers[name] = (int(buf), int(cell.value))
-        self.select_ptr = int(self._rt.mwhip_scatter_select(self._exec, self.handle) or 0)
-        self.archetypes_ptr = int(self._rt.mwhip_scatter_archetypes(self._exec, self.handle) or 0)
-        self.worlds_ptr = int(self._rt.mwhip_scatter_worlds(self._exec, self.handle) or 0)
-        self.written_ptr = int(self._rt.mwhip_scatter_written(self._exec, self.handle) or 0)
-
-    def apply(self) -> "EntityScatter":
-        """Stores the selected cells and rewrites archetypes, worlds and
-        written; waits for the executor's stream."""
-        self._check(self._rt.mwhip_scatter_apply(self._exec, self._live()),
-                    "mwhip_scatter_apply")
-        return self
-
-    def apply_async(self) -> None:
-        self._check(self._rt.mwhip_scatter_apply_async(self._exec, self._live()),
-                    "mwhip_scatter_apply_async")
+        super().__init__(sim, source, components)
+        self.select_ptr = self._pointer("select")
+        self.written_ptr = self._pointer("written")
 
     @property
     def select(self):
         """torch int32 [N] over the device buffer (no copy), the caller's to
         fill: handle i's cells are stored where it is non-zero."""
-        self._live()
-        return self._wrap(("", "select"), self.select_ptr, np.int32, (self.num_handles,))
+        return self._int32("select", self.select_ptr, self.num_handles)
 
     @property
     def written(self):
         """torch int32 [N] over the device buffer (no copy): 1 where the last
         apply stored handle i's cells (selected, names an entity, and no
         selected handle of higher index names the same one)."""
-        self._live()
-        return self._wrap(("", "written"), self.written_ptr, np.int32, (self.num_handles,))
+        return self._int32("written", self.written_ptr, self.num_handles)
 
-    def every_step(self, on: bool = True) -> None:
-        """Every replay of a step graph applies this scatter (waits for the
-        stream and rebuilds the launch graphs); on=False turns it off again."""
+
+class _TreeQuery(_Computed, _StepObject):
+    """What RayQuery and BoxQuery share: groups (fans, bundles) that each have a
+    world and a point (origin, centre), either in a buffer the query owns or
+    read from the caller's source, and buffers asked for by name
+    (mwhip_<stem>_buffer, _BUFS)."""
+
+    _what = ""      # in messages
+    _BUFS: Dict[str, int] = {}
+    _PER_WORLD = ("", "")       # the constructor's groups-per-world argument, a group
+
+    @classmethod
+    def _source(cls, what: str, source, item_bytes: int):
+        """(the tensor to keep alive or None, RaySource) of None, a device
+        tensor whose rows are the records, or (ptr, record_bytes, first_byte)"""
+        if source is None:
+            return None, RaySource(None, 0, 0)
+        if isinstance(source, tuple):
+            ptr, record_bytes, first_byte = (int(v) for v in source)
+            return None, RaySource(ptr, record_bytes, first_byte)
+        import torch
+
+        if not isinstance(source, torch.Tensor) or not source.is_cuda:
+            raise TypeError(f"{cls._what}: {what} is a torch tensor on the device or a "
+                            "(ptr, record_bytes, first_byte) tuple")
+        if source.element_size() != 4 or not source.is_contiguous() or source.dim() < 1:
+            raise TypeError(f"{cls._what}: the {what} tensor must be contiguous with 4-byte "
+                            f"items, not {source.dtype} {tuple(source.shape)}")
+        record = item_bytes if source.dim() == 1 else int(source.shape[-1]) * 4
+        if record < item_bytes:
+            raise TypeError(f"{cls._what}: rows of {record} bytes are too short for {what}")
+        return source, RaySource(source.data_ptr(), record, 0)
+
+    def _open_query(self, sim: "Simulator", desc, world, count, point: str, given,
+                    per_world: int) -> None:
+        """desc: the descriptor with its numbers filled in; point: its field
+        (and the buffer) of the groups' points, `given` the caller's source"""
+        self._open(sim)
+        keep_w, desc.world = self._source("world", world, 4)
+        keep_c, desc.count = self._source("count", count, 4)
+        keep_o, source = self._source(point, given, 12)
+        setattr(desc, point, source)
+        self._sources = (keep_w, keep_c, keep_o)    # (stay where they are)
+        self._create(C.byref(desc))
+        self._per_world = per_world
+        self._owned = {"world": world is None and per_world == 0, point: given is None}
+
+    def _orphan(self) -> None:
+        super()._orphan()
+        self._sources = ()
+
+    def buffer_ptr(self, name: str) -> int:
+        """Device address of owned buffer `name` (a key of _BUFS)."""
         handle = self._live()
-        if not on and not self._every_step:
-            return
-        self._check(self._rt.mwhip_set_step_scatter(self._exec, handle, 1 if on else 0),
-                    "mwhip_set_step_scatter")
-        self._every_step = bool(on)
+        nbytes = C.c_uint64(0)
+        what = f"mwhip_{self._stem}_buffer"
+        ptr = getattr(self._rt, what)(self._exec, handle, self._BUFS[name], C.byref(nbytes))
+        if not ptr:
+            raise RuntimeError(f"{what}({name}): {self._rt.mwhip_last_error().decode()}")
+        return int(ptr)
+
+    def _tensor(self, name, dtype, shape):
+        self._live()
+        if not self._owned.get(name, True):
+            per_world, group = self._PER_WORLD
+            raise RuntimeError(f"this {self._kind} owns no {name} buffer: " + (
+                f"{per_world} gives each {group} its world" if name == "world"
+                and self._per_world else f"a {name} source was given"))
+        if name not in self._tensors:
+            self._wrap(name, self.buffer_ptr(name), dtype, shape)
+        return self._tensors[name]
 
 
-class RayQuery(_ExecObject):
+class RayQuery(_TreeQuery):
     """N = fans x rays_per_fan rays cast through the worlds' broadphase BVHs by
     one kernel (mwhip_rays_*, include/mwhip.h; madrona_amd/ray_ref.py is the
     exact definition).  The rays of a fan share an origin and a world.  Inputs:
@@ -1439,83 +1240,19 @@ class RayQuery(_ExecObject):
     every replay of a step graph recompute the query behind its step views and
     in front of its step gathers and output rings.  HIP backend only."""
 
-    _kind, _destroy, _list = "ray query", "mwhip_rays_destroy", "_ray_queries"
+    _kind, _stem, _list = "ray query", "rays", "_ray_queries"
     HIT, MISS, SKIPPED, BAD_WORLD, BAD_RAY = 1, 0, -1, -2, -3
     _BUFS = {"world": 0, "origin": 1, "dir": 2, "t_max": 3, "hit_t": 4, "hit": 5, "normal": 6,
              "status": 7}
-
-    @staticmethod
-    def _source(what: str, source, item_bytes: int, who: str = "ray_query()"):
-        """(the tensor to keep alive or None, RaySource) of None, a device
-        tensor whose rows are the records, or (ptr, record_bytes, first_byte)"""
-        if source is None:
-            return None, RaySource(None, 0, 0)
-        if isinstance(source, tuple):
-            ptr, record_bytes, first_byte = (int(v) for v in source)
-            return None, RaySource(ptr, record_bytes, first_byte)
-        import torch
-
-        if not isinstance(source, torch.Tensor) or not source.is_cuda:
-            raise TypeError(f"{who}: {what} is a torch tensor on the device or a "
-                            "(ptr, record_bytes, first_byte) tuple")
-        if source.element_size() != 4 or not source.is_contiguous() or source.dim() < 1:
-            raise TypeError(f"{who}: the {what} tensor must be contiguous with 4-byte "
-                            f"items, not {source.dtype} {tuple(source.shape)}")
-        record = item_bytes if source.dim() == 1 else int(source.shape[-1]) * 4
-        if record < item_bytes:
-            raise TypeError(f"{who}: rows of {record} bytes are too short for {what}")
-        return source, RaySource(source.data_ptr(), record, 0)
+    _what, _PER_WORLD = "ray_query()", ("fans_per_world", "fan")
 
     def __init__(self, sim: "Simulator", fans: int, rays_per_fan: int, world=None, origin=None,
                  fans_per_world: int = 0, count=None):
-        self._sim = sim
         self.num_fans, self.rays_per_fan = int(fans), int(rays_per_fan)
         self.num_rays = self.num_fans * self.rays_per_fan
         self.fans_per_world = int(fans_per_world)
-        self._rt = runtime_lib()
-        self._exec = sim.hip_exec()
-        self._tensors = {}
-        self._every_step = False
-        self.handle = 0
         desc = RaysDesc(self.num_fans, self.rays_per_fan, self.fans_per_world, 0)
-        keep_w, desc.world = self._source("world", world, 4)
-        keep_c, desc.count = self._source("count", count, 4)
-        keep_o, desc.origin = self._source("origin", origin, 12)
-        self._sources = (keep_w, keep_c, keep_o)    # (stay where they are)
-        handle = C.c_uint64(0)
-        self._check(self._rt.mwhip_rays_create(self._exec, C.byref(desc), C.byref(handle)),
-                    "mwhip_rays_create")
-        self.handle = int(handle.value)
-        self._owned = {"world": world is None and self.fans_per_world == 0,
-                       "origin": origin is None}
-
-    def _orphan(self) -> None:
-        super()._orphan()
-        self._tensors = {}
-        self._sources = ()
-
-    _wrap = WorldView._wrap
-
-    def buffer_ptr(self, name: str) -> int:
-        """Device address of owned buffer `name`: world, origin, dir, t_max,
-        hit_t, hit, normal or status."""
-        handle = self._live()
-        nbytes = C.c_uint64(0)
-        ptr = self._rt.mwhip_rays_buffer(self._exec, handle, self._BUFS[name], C.byref(nbytes))
-        if not ptr:
-            raise RuntimeError(f"mwhip_rays_buffer({name}): "
-                               f"{self._rt.mwhip_last_error().decode()}")
-        return int(ptr)
-
-    def _tensor(self, name, dtype, shape):
-        self._live()
-        if not self._owned.get(name, True):
-            raise RuntimeError(f"this ray query owns no {name} buffer: " + (
-                "fans_per_world gives each fan its world" if name == "world"
-                and self.fans_per_world else f"a {name} source was given"))
-        if name not in self._tensors:
-            self._wrap(name, self.buffer_ptr(name), dtype, shape)
-        return self._tensors[name]
+        self._open_query(sim, desc, world, count, "origin", origin, self.fans_per_world)
 
     def worlds(self):
         """int32 [F] (owned: no world source and no fans_per_world)"""
@@ -1554,27 +1291,8 @@ class RayQuery(_ExecObject):
         (ptr, num_records, record_bytes, first_byte, handles_per_record)."""
         return (self.buffer_ptr("hit"), self.num_rays, 8, 0, 1)
 
-    def compute(self) -> "RayQuery":
-        """Rewrites every output; waits for the executor's stream."""
-        self._check(self._rt.mwhip_rays_compute(self._exec, self._live()), "mwhip_rays_compute")
-        return self
 
-    def compute_async(self) -> None:
-        self._check(self._rt.mwhip_rays_compute_async(self._exec, self._live()),
-                    "mwhip_rays_compute_async")
-
-    def every_step(self, on: bool = True) -> None:
-        """Every replay of a step graph recomputes this query (waits for the
-        stream and rebuilds the launch graphs); on=False turns it off again."""
-        handle = self._live()
-        if not on and not self._every_step:
-            return
-        self._check(self._rt.mwhip_set_step_rays(self._exec, handle, 1 if on else 0),
-                    "mwhip_set_step_rays")
-        self._every_step = bool(on)
-
-
-class BoxQuery(_ExecObject):
+class BoxQuery(_TreeQuery):
     """B = bundles x boxes_per_bundle boxes tested through the worlds' broadphase
     BVHs by one kernel: per box the whole list of the entities
     PhysicsSystem::findEntitiesWithinAABB reports, in the order it reports them
@@ -1606,66 +1324,23 @@ class BoxQuery(_ExecObject):
     ray queries and in front of its step gathers and output rings.  HIP backend
     only."""
 
-    _kind, _destroy, _list = "box query", "mwhip_boxes_destroy", "_box_queries"
+    _kind, _stem, _list = "box query", "boxes", "_box_queries"
     OK, SKIPPED, BAD_WORLD, BAD_BOX = 0, -1, -2, -3
     PACKED = 1
     _BUFS = {"world": 0, "centre": 1, "lo": 2, "hi": 3, "status": 4, "count": 5, "hits": 6}
+    _what, _PER_WORLD = "box_query()", ("bundles_per_world", "bundle")
 
     def __init__(self, sim: "Simulator", bundles: int, boxes_per_bundle: int, max_hits: int,
                  world=None, centre=None, bundles_per_world: int = 0, count=None,
                  packed: bool = False):
-        self._sim = sim
         self.num_bundles, self.boxes_per_bundle = int(bundles), int(boxes_per_bundle)
         self.max_hits = int(max_hits)
         self.num_boxes = self.num_bundles * self.boxes_per_bundle
         self.bundles_per_world = int(bundles_per_world)
         self.packed = bool(packed)
-        self._rt = runtime_lib()
-        self._exec = sim.hip_exec()
-        self._tensors = {}
-        self._every_step = False
-        self.handle = 0
         desc = BoxesDesc(self.num_bundles, self.boxes_per_bundle, self.max_hits,
                          self.bundles_per_world, self.PACKED if self.packed else 0, 0)
-        source = lambda what, src, nbytes: RayQuery._source(what, src, nbytes, "box_query()")
-        keep_w, desc.world = source("world", world, 4)
-        keep_c, desc.count = source("count", count, 4)
-        keep_o, desc.centre = source("centre", centre, 12)
-        self._sources = (keep_w, keep_c, keep_o)    # (stay where they are)
-        handle = C.c_uint64(0)
-        self._check(self._rt.mwhip_boxes_create(self._exec, C.byref(desc), C.byref(handle)),
-                    "mwhip_boxes_create")
-        self.handle = int(handle.value)
-        self._owned = {"world": world is None and self.bundles_per_world == 0,
-                       "centre": centre is None}
-
-    def _orphan(self) -> None:
-        super()._orphan()
-        self._tensors = {}
-        self._sources = ()
-
-    _wrap = WorldView._wrap
-
-    def buffer_ptr(self, name: str) -> int:
-        """Device address of owned buffer `name`: world, centre, lo, hi, status,
-        count or hits."""
-        handle = self._live()
-        nbytes = C.c_uint64(0)
-        ptr = self._rt.mwhip_boxes_buffer(self._exec, handle, self._BUFS[name], C.byref(nbytes))
-        if not ptr:
-            raise RuntimeError(f"mwhip_boxes_buffer({name}): "
-                               f"{self._rt.mwhip_last_error().decode()}")
-        return int(ptr)
-
-    def _tensor(self, name, dtype, shape):
-        self._live()
-        if not self._owned.get(name, True):
-            raise RuntimeError(f"this box query owns no {name} buffer: " + (
-                "bundles_per_world gives each bundle its world" if name == "world"
-                and self.bundles_per_world else f"a {name} source was given"))
-        if name not in self._tensors:
-            self._wrap(name, self.buffer_ptr(name), dtype, shape)
-        return self._tensors[name]
+        self._open_query(sim, desc, world, count, "centre", centre, self.bundles_per_world)
 
     def worlds(self):
         """int32 [F] (owned: no world source and no bundles_per_world)"""
@@ -1700,26 +1375,6 @@ class BoxQuery(_ExecObject):
         (ptr, num_records, record_bytes, first_byte, handles_per_record)."""
         return (self.buffer_ptr("hits"), self.num_boxes * self.max_hits, 8, 0, 1)
 
-    def compute(self) -> "BoxQuery":
-        """Rewrites every output; waits for the executor's stream."""
-        self._check(self._rt.mwhip_boxes_compute(self._exec, self._live()),
-                    "mwhip_boxes_compute")
-        return self
-
-    def compute_async(self) -> None:
-        self._check(self._rt.mwhip_boxes_compute_async(self._exec, self._live()),
-                    "mwhip_boxes_compute_async")
-
-    def every_step(self, on: bool = True) -> None:
-        """Every replay of a step graph recomputes this query (waits for the
-        stream and rebuilds the launch graphs); on=False turns it off again."""
-        handle = self._live()
-        if not on and not self._every_step:
-            return
-        self._check(self._rt.mwhip_set_step_boxes(self._exec, handle, 1 if on else 0),
-                    "mwhip_set_step_boxes")
-        self._every_step = bool(on)
-
 
 class Simulator:
     """One simulator instance behind the C API (either backend)."""
@@ -1744,16 +1399,12 @@ class Simulator:
             raise RuntimeError(f"sim_create failed for {lib_path}")
         self.backend = self.lib.sim_backend(self.handle).decode()
         self._async = None
-        self._snapshots: List["Snapshot"] = []
+        # what is open, a list per kind, named by the class's `_list`: _snapshots,
+        # _digests, _views, _writes, _reduces, _gathers, _scatters, _ray_queries,
+        # _box_queries; and _trajectories
         self._trajectories: List["Trajectory"] = []
-        self._digests: List["StateDigest"] = []
-        self._views: List["WorldView"] = []
-        self._writes: List["WorldWrite"] = []
-        self._reduces: List["WorldReduce"] = []
-        self._gathers: List["EntityGather"] = []
-        self._scatters: List["EntityScatter"] = []
-        self._ray_queries: List["RayQuery"] = []
-        self._box_queries: List["BoxQuery"] = []
+        for name in _ExecObject._lists:
+            setattr(self, name, [])
         self._tensor_info: Dict[str, Tuple[int, np.dtype, Tuple[int, ...], bool]] = {}
         for i in range(self.lib.sim_num_tensors(self.handle)):
             info = SimTensorInfo()
@@ -1770,13 +1421,12 @@ class Simulator:
     # -- lifecycle ---------------------------------------------------------
     def close(self) -> None:
         if self.handle:
-            # sim_destroy frees the executor and with it its snapshots, digests,
-            # world views, world writes, world reduces, entity gathers,
-            # entity scatters, ray queries and box queries, and
-            # forgets its output rings (the trajectories keep their tensors)
-            for open_ones in (self._snapshots, self._trajectories, self._digests, self._views,
-                              self._writes, self._reduces, self._gathers, self._scatters,
-                              self._ray_queries, self._box_queries):
+            # sim_destroy frees the executor and with it every object of every
+            # kind (what is left on _snapshots, _digests, _views, _writes,
+            # _reduces, ...), and forgets its output rings (the trajectories
+            # keep their tensors)
+            for name in ["_trajectories", *_ExecObject._lists]:
+                open_ones = getattr(self, name)
                 for obj in open_ones:
                     obj._orphan()
                 open_ones.clear()
@@ -1788,6 +1438,11 @@ class Simulator:
 
     def __exit__(self, *exc):
         self.close()
+
+    def _check(self, rc: int, what: str) -> None:
+        """(a call into the runtime: raises with its message)"""
+        if rc != 0:
+            raise RuntimeError(f"{what} -> {rc}: {runtime_lib().mwhip_last_error().decode()}")
 
     def step(self, n: int = 1) -> None:
         self.lib.sim_step(self.handle, n)
@@ -1862,10 +1517,7 @@ class Simulator:
     def render(self) -> None:
         """MWCudaExecutor::buildRenderGraph + run: TLAS build and ray cast of every
         view into the simulator's "rgb" / "depth" tensors (HIP backend)."""
-        rc = self.lib.sim_hip_render(self.handle)
-        if rc != 0:
-            raise RuntimeError(f"sim_hip_render -> {rc}: "
-                               f"{runtime_lib().mwhip_last_error().decode()}")
+        self._check(self.lib.sim_hip_render(self.handle), "sim_hip_render")
 
     def render_graph(self) -> int:
         """Launch-graph handle of the render pass (for step_async(graph=...))."""
@@ -1933,33 +1585,32 @@ class Simulator:
             raise RuntimeError(f"mwhip_broadphase_carry_stats({graph}) -> {rc}")
         return {"carried_replays": int(counters[0]), "full_replays": int(counters[1])}
 
+    def _make(self, cls, needs: str, *args):
+        """The factories' common part: cls(self, *args) on this simulator's
+        list of them.  needs: who needs the HIP backend, "" for nobody."""
+        if needs and self.backend != "hip":
+            raise RuntimeError(f"{needs} the HIP backend, this is {self.backend!r}")
+        obj = cls(self, *args)
+        getattr(self, cls._list).append(obj)
+        return obj
+
     def snapshot(self) -> "Snapshot":
         """A new, empty Snapshot of this simulator (HIP backend; raises on the
         reference backend, which has no executor to ask)."""
-        if self.backend != "hip":
-            raise RuntimeError(f"snapshots need the HIP backend, this is {self.backend!r}")
-        snap = Snapshot(self)
-        self._snapshots.append(snap)
-        return snap
+        return self._make(Snapshot, "snapshots need")
 
     def digest(self, columns=None) -> "StateDigest":
         """A StateDigest over `columns` of the dump list (names or indices, in
         that order; default: the whole dump list in its order).  Either
         backend: see StateDigest for what the reference backend offers."""
-        dig = StateDigest(self, columns)
-        self._digests.append(dig)
-        return dig
+        return self._make(StateDigest, "", columns)
 
     def world_view(self, table: str, columns=None, max_rows: int = 0) -> "WorldView":
         """A WorldView of `columns` (names as in `columns`, e.g. "Item.Vec3";
         default: every dump-list column of the table) of table `table`, padded
         to max_rows rows per world.  HIP backend; raises on the reference
         backend, which has no executor to ask."""
-        if self.backend != "hip":
-            raise RuntimeError(f"world views need the HIP backend, this is {self.backend!r}")
-        view = WorldView(self, table, columns, max_rows)
-        self._views.append(view)
-        return view
+        return self._make(WorldView, "world views need", table, columns, max_rows)
 
     def world_write(self, table: str, columns=None, max_rows: int = 0) -> "WorldWrite":
         """A WorldWrite into `columns` (names as in `columns`, e.g. "Item.Vec3";
@@ -1967,22 +1618,14 @@ class Simulator:
         WorldID, which cannot be written) of table `table`, max_rows rows per
         world.  HIP backend; raises on the reference backend, which has no
         executor to ask."""
-        if self.backend != "hip":
-            raise RuntimeError(f"world writes need the HIP backend, this is {self.backend!r}")
-        write = WorldWrite(self, table, columns, max_rows)
-        self._writes.append(write)
-        return write
+        return self._make(WorldWrite, "world writes need", table, columns, max_rows)
 
     def world_reduce(self, table: str, terms) -> "WorldReduce":
         """A WorldReduce of table `table`: one result per world and element for
         every term -- (column, op) or (column, op, options), see WorldReduce --
         plus each world's row count and an alarm word per world.  HIP backend;
         raises on the reference backend, which has no executor to ask."""
-        if self.backend != "hip":
-            raise RuntimeError(f"world reduces need the HIP backend, this is {self.backend!r}")
-        reduce = WorldReduce(self, table, terms)
-        self._reduces.append(reduce)
-        return reduce
+        return self._make(WorldReduce, "world reduces need", table, terms)
 
     def entity_gather(self, source, components) -> "EntityGather":
         """An EntityGather of `components` (named by the part of a dump-list
@@ -1992,11 +1635,7 @@ class Simulator:
         num_records, record_bytes, first_byte, handles_per_record) tuple such
         as WorldView.handle_source() gives.  HIP backend; raises on the
         reference backend, which has no executor to ask."""
-        if self.backend != "hip":
-            raise RuntimeError(f"entity gathers need the HIP backend, this is {self.backend!r}")
-        gather = EntityGather(self, source, components)
-        self._gathers.append(gather)
-        return gather
+        return self._make(EntityGather, "entity gathers need", source, components)
 
     def entity_scatter(self, source, components) -> "EntityScatter":
         """An EntityScatter of `components` (named as entity_gather() names
@@ -2004,11 +1643,7 @@ class Simulator:
         `source`, which takes every form entity_gather() takes,
         WorldView.handle_source() included.  HIP backend; raises on the
         reference backend, which has no executor to ask."""
-        if self.backend != "hip":
-            raise RuntimeError(f"entity scatters need the HIP backend, this is {self.backend!r}")
-        scatter = EntityScatter(self, source, components)
-        self._scatters.append(scatter)
-        return scatter
+        return self._make(EntityScatter, "entity scatters need", source, components)
 
     def ray_query(self, fans: int, rays_per_fan: int, world=None, origin=None,
                   fans_per_world: int = 0, count=None) -> "RayQuery":
@@ -2020,11 +1655,8 @@ class Simulator:
         buffers the query owns (worlds(), origins()).  fans_per_world > 0:
         world = f // fans_per_world, the shape of a world view's slab.
         Simulator.close() frees what is left open."""
-        if self.backend != "hip":
-            raise RuntimeError(f"ray queries need the HIP backend, this is {self.backend!r}")
-        query = RayQuery(self, fans, rays_per_fan, world, origin, fans_per_world, count)
-        self._ray_queries.append(query)
-        return query
+        return self._make(RayQuery, "ray queries need", fans, rays_per_fan, world, origin,
+                          fans_per_world, count)
 
     def box_query(self, bundles: int, boxes_per_bundle: int, max_hits: int, world=None,
                   centre=None, bundles_per_world: int = 0, count=None,
@@ -2039,12 +1671,8 @@ class Simulator:
         // bundles_per_world, the shape of a world view's slab.  packed: a box
         per lane instead of a chunk of a bundle per group of 32 lanes (same
         words).  Simulator.close() frees what is left open."""
-        if self.backend != "hip":
-            raise RuntimeError(f"box queries need the HIP backend, this is {self.backend!r}")
-        query = BoxQuery(self, bundles, boxes_per_bundle, max_hits, world, centre,
-                         bundles_per_world, count, packed)
-        self._box_queries.append(query)
-        return query
+        return self._make(BoxQuery, "box queries need", bundles, boxes_per_bundle, max_hits,
+                          world, centre, bundles_per_world, count, packed)
 
     def record(self, names: List[str], steps: int, on_render: bool = False) -> "Trajectory":
         """Records the exported tensors `names` on the device from the next
@@ -2052,12 +1680,7 @@ class Simulator:
         step graph -- step(), step_async(), packed graphs -- or, with
         on_render, of the render graph.  HIP backend; raises on the reference
         backend, which has no executor to ask."""
-        if self.backend != "hip":
-            raise RuntimeError(
-                f"recording on the device needs the HIP backend, this is {self.backend!r}")
-        traj = Trajectory(self, names, steps, on_render)
-        self._trajectories.append(traj)
-        return traj
+        return self._make(Trajectory, "recording on the device needs", names, steps, on_render)
 
     # ---- stream-ordered stepping (HIP backend) -----------------------------------
     def stream(self) -> int:
@@ -2083,12 +1706,9 @@ class Simulator:
         rt = runtime_lib()
         n, ptrs, words = self._pack_descriptor(names)
         out = C.c_uint64(0)
-        rc = rt.mwhip_build_launch_graph_with_pack(
+        self._check(rt.mwhip_build_launch_graph_with_pack(
             self.hip_exec(), self.lib.sim_hip_step_graph(self.handle), n, ptrs,
-            words, self.num_worlds, dst_ptr, C.byref(out))
-        if rc != 0:
-            raise RuntimeError(f"mwhip_build_launch_graph_with_pack -> {rc}: "
-                               f"{rt.mwhip_last_error().decode()}")
+            words, self.num_worlds, dst_ptr, C.byref(out)), "mwhip_build_launch_graph_with_pack")
         return int(out.value)
 
     def step_async(self, n: int = 1, graph: int = 0) -> None:
@@ -2106,8 +1726,7 @@ class Simulator:
         for _ in range(n):
             rc = rt.mwhip_run_async(exec_, graph, stream)
             if rc != 0:
-                raise RuntimeError(
-                    f"mwhip_run_async -> {rc}: {rt.mwhip_last_error().decode()}")
+                self._check(rc, "mwhip_run_async")
 
     def set_input_ring(self, name: str, ring_ptr: int, num_slots: int) -> None:
         """The k-th replay after this call starts by copying slot k % num_slots
@@ -2117,21 +1736,17 @@ class Simulator:
         rt = runtime_lib()
         _, dtype, dims, _ = self._tensor_info[name]
         slot_bytes = int(np.prod(dims)) * dtype.itemsize
-        rc = rt.mwhip_set_input_ring(self.hip_exec(), self.tensor_ptr(name),
-                                     ring_ptr or None, slot_bytes, num_slots)
-        if rc != 0:
-            raise RuntimeError(f"mwhip_set_input_ring -> {rc}: "
-                               f"{rt.mwhip_last_error().decode()}")
+        self._check(rt.mwhip_set_input_ring(self.hip_exec(), self.tensor_ptr(name),
+                                            ring_ptr or None, slot_bytes, num_slots),
+                    "mwhip_set_input_ring")
 
     def stream_wait_replays(self, hip_stream: int) -> None:
         """Makes `hip_stream` (a hipStream_t) wait for every replay queued so
         far, without putting anything on the executor's stream
         (mwhip_stream_wait_replays)."""
         rt = runtime_lib() if self._async is None else self._async[0]
-        rc = rt.mwhip_stream_wait_replays(self.hip_exec(), hip_stream)
-        if rc != 0:
-            raise RuntimeError(f"mwhip_stream_wait_replays -> {rc}: "
-                               f"{rt.mwhip_last_error().decode()}")
+        self._check(rt.mwhip_stream_wait_replays(self.hip_exec(), hip_stream),
+                    "mwhip_stream_wait_replays")
 
     def pack_rows_async(self, names: List[str], dst_ptr: int) -> None:
         """Queues, behind the replays queued so far, the packing of the exported
@@ -2139,19 +1754,12 @@ class Simulator:
         device address `dst_ptr` (mwhip_pack_rows)."""
         rt = runtime_lib()
         n, ptrs, words = self._pack_descriptor(names)
-        rc = rt.mwhip_pack_rows(self.hip_exec(), n, ptrs, words,
-                                self.num_worlds, dst_ptr)
-        if rc != 0:
-            raise RuntimeError(
-                f"mwhip_pack_rows -> {rc}: {rt.mwhip_last_error().decode()}")
+        self._check(rt.mwhip_pack_rows(self.hip_exec(), n, ptrs, words,
+                                       self.num_worlds, dst_ptr), "mwhip_pack_rows")
 
     def sync(self) -> None:
         """Waits for the queued replays; raises on a device-side error flag."""
-        rt = runtime_lib()
-        rc = rt.mwhip_synchronize(self.hip_exec())
-        if rc != 0:
-            raise RuntimeError(
-                f"mwhip_synchronize -> {rc}: {rt.mwhip_last_error().decode()}")
+        self._check(runtime_lib().mwhip_synchronize(self.hip_exec()), "mwhip_synchronize")
 
     def profile(self, reps: int = 20, graph: int = 0):
         """Per-kernel timing of one step (HIP events on the executor's stream,
@@ -2164,7 +1772,7 @@ class Simulator:
                              graph or self.lib.sim_hip_step_graph(self.handle),
                              reps, stats, 512)
         if n < 0:
-            raise RuntimeError(f"mwhip_profile -> {n}: {rt.mwhip_last_error().decode()}")
+            self._check(n, "mwhip_profile")
         return [dict(name=stats[i].name.decode(), kind=int(stats[i].node_kind),
                      avg_us=float(stats[i].avg_us), algo_bytes=float(stats[i].algo_bytes),
                      rows=float(stats[i].rows),

@@ -559,4 +559,14 @@ void *sim_hip_exec(SimHandle *h)
 #endif
 }
 
+void *sim_hip_cxx_exec(SimHandle *h)
+{
+#ifdef SIM_BACKEND_REF_CPU
+    (void)h;
+    return nullptr;
+#else
+    return (void *)h->exec;
+#endif
+}
+
 }

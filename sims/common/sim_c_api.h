@@ -108,6 +108,9 @@ SIM_API uint64_t sim_hip_render_graph(SimHandle *h);
 
 /* HIP backend only (NULL/0 on the reference): opaque mwhip_exec* for profiling */
 SIM_API void *sim_hip_exec(SimHandle *h);
+/* HIP backend only (NULL on the reference): the madrona::MWCudaExecutor * the
+ * simulator owns, for tests that drive the C++ classes of <madrona/mw_gpu.hpp> */
+SIM_API void *sim_hip_cxx_exec(SimHandle *h);
 /* launch-graph handle of the per-step graph inside that executor (0 on the reference) */
 SIM_API uint64_t sim_hip_step_graph(SimHandle *h);
 

@@ -92,6 +92,20 @@ REDUCECONF_API uint32_t REDUCECONF_CAT(REDUCECONF_NAME, _cycle)(MWCudaExecutor *
             term.dims()[0] != counts.dims()[0] || alarm.dims()[0] != counts.dims()[0]) {
         return 0;
     }
+    // every term's tensor is in its result type: Float32 for SUM / MIN / MAX
+    // of F32 and for ABSMAX, Int32 otherwise
+    for (uint32_t i = 0; i < num_terms; i++) {
+        const Tensor each = third.termTensor(i);
+        const bool is_float = terms[i].dtype == MWHIP_REDUCE_F32 &&
+            terms[i].op <= MWHIP_REDUCE_ABSMAX;
+        if (each.devicePtr() == nullptr || each.numDims() != 2 ||
+                each.dims()[0] != counts.dims()[0] ||
+                each.dims()[1] != (int64_t)terms[i].num_elems ||
+                each.type() != (is_float ? madrona::py::TensorElementType::Float32 :
+                                madrona::py::TensorElementType::Int32)) {
+            return 0;
+        }
+    }
     return (uint32_t)term.dims()[1];
 }
 

@@ -220,6 +220,14 @@ struct WorldBlock {
     uint8_t solverSlot[MAXB];               // 0xFF: an inert static body
     static constexpr uint32_t noSlot = 0xFFu;
     WaveCandidate candidates[maxCandidates];
+    // the face that separated a hull-hull candidate when it was last tested in
+    // this step (sepFaceEntry, step_narrowphase.inl; 0: none): a byte beside
+    // the list, not the spare high bits of WaveCandidate::a / ::b -- no reader
+    // of the list, here or of its spilled tail in HBM, has to mask anything,
+    // and two worlds' bytes still fit under the 20 480 B of eight workgroups
+    // per CU.  Zeroed when the list is written; spilled candidates have none.
+    alignas(4) uint8_t sepFace[maxCandidates];
+    static_assert(maxCandidates % 4 == 0);
     float lambdas[maxContacts];
 
     JointConstraint joints[maxJoints];
@@ -871,6 +879,33 @@ __device__ __attribute__((always_inline)) inline FramedWorld loadWorldFramed(
 // the constraint solve of a substep over the block (solveSubstepConstraints)
 #include "step_solve.inl"
 
+// The two narrowphase paths that no shape of the Escape Room or Hide-and-Seek
+// takes, out of line: inlined, they were a third of the kernel's code, in the
+// middle of its hottest loop.  Called from loops of their
+// own behind the hull-hull loop, so that nothing of that loop is live across
+// the calls.  Bit 0 of the result: a contact was written.
+// (hulls of more vertices or faces than the scratch holds; bit 1: *too_big*)
+template <int LPW>
+__device__ __attribute__((noinline, cold)) uint32_t
+hullHullLargeOutOfLine(uint32_t lane, const PairSetup &pair,
+                       HullScratch *scratch, PackedContact *out)
+{
+    bool too_big = false;
+    const bool found = hullHullWaveLazy<LPW>(lane, pair, scratch, out, &too_big);
+    return (found ? 1u : 0u) | (too_big ? 2u : 0u);
+}
+
+// (faces of more corners than the clipping scratch holds; bit 1: unsupported)
+__device__ __attribute__((noinline, cold)) inline uint32_t
+collidePairStoredOutOfLine(const PairSetup &pair, math::Vector3 *tmp_vertices,
+                           geo::Plane *tmp_faces, PackedContact *out)
+{
+    bool unsupported = false;
+    const bool found = collidePairStored(pair, tmp_vertices, tmp_faces,
+        MADRONA_PHYS_MAX_HULL_ELEMS, out, &unsupported);
+    return (found ? 1u : 0u) | (unsupported ? 2u : 0u);
+}
+
 // Wavefronts per SIMD.  The step is bound by instruction issue and by the
 // latency of its LDS / HBM round trips (SQ counters, profiles/r06_phys_occupancy_
 // counters.jsonl: one wavefront per SIMD issues 59 % of its cycles and waits
@@ -932,6 +967,11 @@ physicsStepLdsKernel(EcsState *S, void *node_data, uint32_t, uint32_t)
 
 #ifdef MADRONA_PHYS_PROFILE_LDS_HH
 #define MADRONA_PHYS_PROFILE_LDS 1
+    // (slots 9 and 10: remembered separating faces that settled their pair, and
+    // that did not -- counted by the lane whose pair it is)
+#define PHYS_SEP_PROF(slot) atomicAdd(&prof_lds[group][slot], 1u)
+#else
+#define PHYS_SEP_PROF(slot) do {} while (0)
 #endif
 #ifdef MADRONA_PHYS_PROFILE_LDS
     // (the phase profile of a build that keeps its registers: the accumulators
@@ -1272,6 +1312,11 @@ physicsStepLdsKernel(EcsState *S, void *node_data, uint32_t, uint32_t)
             mwhip::raiseError(S, mwhip::kErrTableOverflow);
             continue;
         }
+        // (a new list: no candidate's separating face is known)
+        for (uint32_t i = lane; i < (uint32_t)Block::maxCandidates / 4u;
+             i += (uint32_t)LPW) {
+            ((uint32_t *)w->sepFace)[i] = 0u;
+        }
         wave::phaseFence();
         PHYS_PROF(1);
 
@@ -1348,6 +1393,7 @@ physicsStepLdsKernel(EcsState *S, void *node_data, uint32_t, uint32_t)
                 PackedContact *stage = w->contacts() + num_contacts;
                 bool has_contact = false;
                 bool too_big = false;
+                bool large = false;     // hull-hull, hulls beyond the scratch
                 bool unsupported = false;
 
                 uint32_t kind = 0;      // 1: this lane alone, 2: whole wave
@@ -1443,6 +1489,25 @@ physicsStepLdsKernel(EcsState *S, void *node_data, uint32_t, uint32_t)
                                     (solo_rank - first) * Scratch::polyDwords,
                                 stage + lane, &too_big, &unsupported,
                                 Scratch::polyVerts);
+                        }
+                    }
+
+                    // A hull-hull pair that a face separated when it was last
+                    // tested in this step: that face alone, on this lane.  If it
+                    // still separates the pair there is no contact and no
+                    // cooperative test; else the entry goes and the pair is
+                    // tested like any other.  (Before the ballots below: both
+                    // halves derive who tests what from them.)
+                    if (kind == 2 && chunk + lane < (uint32_t)Block::maxCandidates) {
+                        const uint32_t entry = w->sepFace[chunk + lane];
+                        if (entry != 0u) {
+                            if (sepFaceSeparates(pair, entry)) {
+                                kind = 0;
+                                PHYS_SEP_PROF(9);
+                            } else {
+                                w->sepFace[chunk + lane] = 0;
+                                PHYS_SEP_PROF(10);
+                            }
                         }
                     }
                 }
@@ -1552,6 +1617,8 @@ physicsStepLdsKernel(EcsState *S, void *node_data, uint32_t, uint32_t)
                     }
 
                     bool pair_too_big = false;
+                    bool pair_large = false;
+                    uint32_t pair_sep_face = 0;
                     const Block *pair_world = steal ? partner_w : w;
                     const uint32_t c = (steal ? partner_chunk : chunk) + src;
                     const WaveCandidate candidate =
@@ -1562,15 +1629,22 @@ physicsStepLdsKernel(EcsState *S, void *node_data, uint32_t, uint32_t)
                     PackedContact *pair_out = steal ?
                         partner_w->contacts() + partner_contacts + src : stage + src;
                     // every lane writes the same contact to the owner's slot
-                    const bool found = hullHullWave<LPW>(lane, shared_pair,
+                    // (hulls that do not fit the scratch are only marked here)
+                    const bool found = hullHullWave<LPW, true>(lane, shared_pair,
                         w->scratch.hull(), pair_out, &pair_too_big,
-                        PHYS_HH_PROF());
-                    // the lane that owns the candidate learns the outcome
+                        PHYS_HH_PROF(), &pair_large, &pair_sep_face);
+                    // the lane that owns the candidate learns the outcome, and
+                    // notes the face that separated the pair (or that none did)
                     const uint32_t outcome = __shfl(
-                        (found ? 1u : 0u) | (pair_too_big ? 2u : 0u), 0, LPW);
+                        (found ? 1u : 0u) | (pair_too_big ? 2u : 0u) |
+                        (pair_large ? 4u : 0u) | (pair_sep_face << 3), 0, LPW);
                     if (!steal && lane == src) {
                         has_contact = (outcome & 1u) != 0u;
                         too_big = (outcome & 2u) != 0u;
+                        large = (outcome & 4u) != 0u;
+                        if (chunk + lane < (uint32_t)Block::maxCandidates) {
+                            w->sepFace[chunk + lane] = (uint8_t)(outcome >> 3);
+                        }
                     }
                     if constexpr (worlds_per_wave == 2) {
                         const uint32_t theirs =
@@ -1578,6 +1652,10 @@ physicsStepLdsKernel(EcsState *S, void *node_data, uint32_t, uint32_t)
                         if (taken_from_me >= 0 && (int32_t)lane == taken_from_me) {
                             has_contact = (theirs & 1u) != 0u;
                             too_big = (theirs & 2u) != 0u;
+                            large = (theirs & 4u) != 0u;
+                            if (chunk + lane < (uint32_t)Block::maxCandidates) {
+                                w->sepFace[chunk + lane] = (uint8_t)(theirs >> 3);
+                            }
                         }
                     }
 #ifdef MADRONA_PHYS_PROFILE
@@ -1592,11 +1670,32 @@ physicsStepLdsKernel(EcsState *S, void *node_data, uint32_t, uint32_t)
 #endif
                 }
 
+                // Hulls of more vertices or faces than the LDS scratch holds
+                // (none in the Escape Room or Hide-and-Seek shapes): the same
+                // cooperative test on lazily evaluated hulls, by the world's
+                // own lanes, after the loop above and out of line -- a second
+                // copy of the SAT does not sit in the middle of the hot one.
+                uint64_t large_pairs = wave::groupBallot<LPW>(large);
+                while (large_pairs != 0) {
+                    const uint32_t src = (uint32_t)__builtin_ctzll(large_pairs);
+                    large_pairs &= large_pairs - 1;
+                    const PairSetup large_pair = ldsSetupPair(w, obj_mgr,
+                        candidateAt(chunk + src));
+                    const uint32_t outcome = __shfl(
+                        hullHullLargeOutOfLine<LPW>(lane, large_pair,
+                            w->scratch.hull(), stage + src), 0, LPW);
+                    if (lane == src) {
+                        has_contact = (outcome & 1u) != 0u;
+                        too_big = (outcome & 2u) != 0u;
+                    }
+                    wave::phaseFence();
+                }
+
                 // Hulls whose faces outgrow the LDS scratch (rare: none in the
                 // Escape Room or Hide-and-Seek shapes): the generic routine,
                 // one lane at a time through the world's scratch in HBM -- no
                 // per-lane arrays in private memory for a path that is almost
-                // never taken.
+                // never taken, and out of line like the one above.
                 uint64_t big_pairs = wave::groupBallot<LPW>(too_big);
                 while (big_pairs != 0) {
                     const uint32_t src = (uint32_t)__builtin_ctzll(big_pairs);
@@ -1612,9 +1711,10 @@ physicsStepLdsKernel(EcsState *S, void *node_data, uint32_t, uint32_t)
                             tmp_faces + MADRONA_PHYS_MAX_HULL_ELEMS);
                         PairSetup pair = ldsSetupPair(w, obj_mgr,
                                                       candidateAt(chunk + lane));
-                        has_contact = collidePairStored(pair, tmp_vertices,
-                            tmp_faces, MADRONA_PHYS_MAX_HULL_ELEMS, stage + lane,
-                            &unsupported);
+                        const uint32_t outcome = collidePairStoredOutOfLine(pair,
+                            tmp_vertices, tmp_faces, stage + lane);
+                        has_contact = (outcome & 1u) != 0u;
+                        unsupported = unsupported || (outcome & 2u) != 0u;
                     }
                     wave::phaseFence();
                 }
@@ -1623,17 +1723,26 @@ physicsStepLdsKernel(EcsState *S, void *node_data, uint32_t, uint32_t)
                 }
                 wave::phaseFence();
 
-                // compact in place: all reads, then all writes
+                // compact in place, 16 bytes of every contact at a time: all
+                // reads of a piece, then all its writes (piece p of a slot is
+                // only ever written from piece p of another) -- a whole
+                // contact per lane would go through private memory
                 uint64_t mask = wave::groupBallot<LPW>(has_contact);
                 const uint32_t rank = wave::rankInGroup(mask, lane);
                 const bool moves = has_contact && rank != lane;
-                PackedContact moved;
-                if (moves) {
-                    moved = stage[lane];
-                }
-                wave::phaseFence();
-                if (moves) {
-                    stage[rank] = moved;
+                // (the contacts start at `shared`: 16-byte aligned)
+                static_assert(sizeof(PackedContact) % sizeof(uint4) == 0);
+#pragma unroll
+                for (uint32_t piece = 0;
+                     piece < sizeof(PackedContact) / sizeof(uint4); piece++) {
+                    uint4 moved = { 0, 0, 0, 0 };
+                    if (moves) {
+                        moved = ((const uint4 *)(stage + lane))[piece];
+                    }
+                    wave::phaseFence();
+                    if (moves) {
+                        ((uint4 *)(stage + rank))[piece] = moved;
+                    }
                 }
                 num_contacts += (uint32_t)__builtin_popcountll(mask);
                 chunk += width;
@@ -1749,6 +1858,7 @@ physicsStepLdsKernel(EcsState *S, void *node_data, uint32_t, uint32_t)
 #undef PHYS_PROF
 #define PHYS_PROF(slot) do {} while (0)
 #endif
+#undef PHYS_SEP_PROF
 #ifdef MADRONA_PHYS_PROFILE
     if (lane == 0 && S->moduleData[1] != nullptr) {
         unsigned long long *dst = (unsigned long long *)S->moduleData[1];

@@ -208,34 +208,120 @@ struct HullHullProf {
 #endif
 };
 
+// ---------------------------------------------------------------------------
+// The separating face of a hull-hull pair, remembered.  A
+// face query's separation is the maximum over the hull's faces f of
+// getHullDistanceFromPlane(plane(f), other): one face with a distance > 0
+// makes the maximum > 0 and the pair contact-free, whatever the other faces
+// and the edges say (the sequential queryFaceDirections stops at the first
+// such face for the same reason).  A pair that a face separated is likely to
+// be separated by that face when it is tested again a substep later; one lane
+// then settles with one face what the cooperative test settles with all of
+// them and both hulls staged.
+// An entry is one byte: 0 = nothing known, sepFaceOfA | f or sepFaceOfB | f =
+// face f (< sepFaceLimit) of that hull separated the pair.
+// ---------------------------------------------------------------------------
+inline constexpr uint32_t sepFaceLimit = 16;
+inline constexpr uint32_t sepFaceOfA = 0x10;
+inline constexpr uint32_t sepFaceOfB = 0x20;
+
+__device__ inline uint32_t sepFaceEntry(bool of_a, CountT face_idx)
+{
+    if (face_idx < 0 || face_idx >= (CountT)sepFaceLimit) {
+        return 0u;
+    }
+    return (of_a ? sepFaceOfA : sepFaceOfB) | (uint32_t)face_idx;
+}
+
+// Does the face `entry` names separate the pair now?  The distance is that of
+// the cooperative face query for that face, bit for bit: the plane and the
+// other hull's vertices come from the expressions makeHullStateWave stores
+// (LazyHull), the minimum from getHullDistanceFromPlane.  An entry that names
+// no face of the pair's hulls says nothing (false).
+__device__ inline bool sepFaceSeparates(const PairSetup &pair, uint32_t entry,
+                                        float *distance = nullptr)
+{
+    const bool of_a = (entry & sepFaceOfA) != 0u;
+    if (of_a == ((entry & sepFaceOfB) != 0u) ||
+            (entry & ~(sepFaceOfA | sepFaceOfB | (sepFaceLimit - 1u))) != 0u) {
+        return false;
+    }
+    const uint32_t f = entry & (sepFaceLimit - 1u);
+    const CollisionPrimitive *owner_prim = of_a ? pair.aPrim : pair.bPrim;
+    const CollisionPrimitive *other_prim = of_a ? pair.bPrim : pair.aPrim;
+    const PrimitiveTransform &owner_txfm = of_a ? pair.a : pair.b;
+    const PrimitiveTransform &other_txfm = of_a ? pair.b : pair.a;
+    if (f >= owner_prim->hull.halfEdgeMesh.numFaces) {
+        return false;
+    }
+    const LazyHull owner(owner_prim->hull.halfEdgeMesh, owner_txfm.pos,
+                         owner_txfm.rot, owner_txfm.scale, false);
+    const LazyHull other(other_prim->hull.halfEdgeMesh, other_txfm.pos,
+                         other_txfm.rot, other_txfm.scale, false);
+    const float face_dist = getHullDistanceFromPlane(owner.plane((CountT)f), other);
+    if (distance != nullptr) {
+        *distance = face_dist;
+    }
+    return face_dist > 0.0f;
+}
+
 template <int LPW = 64, typename ScratchT, typename HullA, typename HullB,
           typename OutT>
 __device__ inline bool hullHullWaveSAT(uint32_t lane, const PairSetup &pair,
                                        HullA &a, const HullB &b,
                                        ScratchT *scratch,
                                        OutT *out, bool *too_big,
-                                       HullHullProf prof = HullHullProf {});
+                                       HullHullProf prof = HullHullProf {},
+                                       uint32_t *sep_face = nullptr);
+
+// do both hulls of the pair fit the scratch of a cooperative test?
+template <typename ScratchT>
+__device__ inline bool hullsFitScratch(const PairSetup &pair)
+{
+    const HalfEdgeMesh &a_mesh = pair.aPrim->hull.halfEdgeMesh;
+    const HalfEdgeMesh &b_mesh = pair.bPrim->hull.halfEdgeMesh;
+    return a_mesh.numVertices <= ScratchT::elems &&
+        a_mesh.numFaces <= ScratchT::elems &&
+        b_mesh.numVertices <= ScratchT::elems &&
+        b_mesh.numFaces <= ScratchT::elems;
+}
+
+// hulls larger than the scratch: evaluated lazily, every lane its own view
+template <int LPW = 64, typename ScratchT = HullScratch,
+          typename OutT = ContactConstraint>
+__device__ inline bool
+hullHullWaveLazy(uint32_t lane, const PairSetup &pair, ScratchT *scratch,
+                 OutT *out, bool *too_big, HullHullProf prof = HullHullProf {})
+{
+    const HalfEdgeMesh &a_mesh = pair.aPrim->hull.halfEdgeMesh;
+    const HalfEdgeMesh &b_mesh = pair.bPrim->hull.halfEdgeMesh;
+    LazyHull a(a_mesh, pair.a.pos, pair.a.rot, pair.a.scale);
+    LazyHull b(b_mesh, pair.b.pos, pair.b.rot, pair.b.scale);
+    return hullHullWaveSAT<LPW>(lane, pair, a, b, scratch, out, too_big, prof);
+}
 
 // Hull-hull pair handled by a group of LPW lanes (`pair` is uniform across the
 // group; `lane` = index inside it).  Returns false with *too_big set when the
 // clipped polygon may not fit the LDS scratch.
 // (A template so that only the device pass instantiates it.  Keeping it out of
 // line to confine its register footprint was measured: 1166 -> 1637 us.)
-template <int LPW = 64, typename ScratchT = HullScratch,
-          typename OutT = ContactConstraint>
+// (DEFER_LARGE: a pair whose hulls do not fit the scratch is not tested here --
+// *large is set and the caller runs hullHullWaveLazy on it where it likes: the
+// LDS step does, out of line and behind its hull-hull loop)
+template <int LPW = 64, bool DEFER_LARGE = false,
+          typename ScratchT = HullScratch, typename OutT = ContactConstraint>
 __device__ inline bool
 hullHullWave(uint32_t lane, const PairSetup &pair,
                                     ScratchT *scratch,
                                     OutT *out, bool *too_big,
-                                    HullHullProf prof = HullHullProf {})
+                                    HullHullProf prof = HullHullProf {},
+                                    [[maybe_unused]] bool *large = nullptr,
+                                    uint32_t *sep_face = nullptr)
 {
     const HalfEdgeMesh &a_mesh = pair.aPrim->hull.halfEdgeMesh;
     const HalfEdgeMesh &b_mesh = pair.bPrim->hull.halfEdgeMesh;
 
-    if (a_mesh.numVertices <= ScratchT::elems &&
-        a_mesh.numFaces <= ScratchT::elems &&
-        b_mesh.numVertices <= ScratchT::elems &&
-        b_mesh.numFaces <= ScratchT::elems) {
+    if (hullsFitScratch<ScratchT>(pair)) {
         // small hulls: transform once into LDS
         HullState a = makeHullStateWave<LPW>(lane, a_mesh, pair.a,
             scratch->hullVerts[0], scratch->hullPlanes[0]);
@@ -249,12 +335,15 @@ hullHullWave(uint32_t lane, const PairSetup &pair,
 #endif
         prof.mark(lane, 0);     // hulls into LDS
         return hullHullWaveSAT<LPW>(lane, pair, a, b, scratch, out, too_big,
-                                    prof);
+                                    prof, sep_face);
     }
 
-    LazyHull a(a_mesh, pair.a.pos, pair.a.rot, pair.a.scale);
-    LazyHull b(b_mesh, pair.b.pos, pair.b.rot, pair.b.scale);
-    return hullHullWaveSAT<LPW>(lane, pair, a, b, scratch, out, too_big, prof);
+    if constexpr (DEFER_LARGE) {
+        *large = true;
+        return false;
+    } else {
+        return hullHullWaveLazy<LPW>(lane, pair, scratch, out, too_big, prof);
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -523,12 +612,18 @@ __device__ inline bool hullHullWaveSAT(uint32_t lane, const PairSetup &pair,
                                        HullA &a, const HullB &b,
                                        ScratchT *scratch,
                                        OutT *out, bool *too_big,
-                                       HullHullProf prof)
+                                       HullHullProf prof,
+                                       uint32_t *sep_face)
 {
+    // (*sep_face: where a separated test ended, for the caller to try that
+    // face alone next time -- sepFaceEntry; the caller has zeroed it)
     FaceQuery face_query_a = queryFaceDirectionsWave<LPW>(lane, a, b);
     prof.mark(lane, 1);
     if (face_query_a.separation > 0.0f) {
         prof.count(lane, 5);
+        if (sep_face != nullptr) {
+            *sep_face = sepFaceEntry(true, face_query_a.faceIdx);
+        }
         return false;
     }
 
@@ -536,6 +631,9 @@ __device__ inline bool hullHullWaveSAT(uint32_t lane, const PairSetup &pair,
     prof.mark(lane, 2);
     if (face_query_b.separation > 0.0f) {
         prof.count(lane, 6);
+        if (sep_face != nullptr) {
+            *sep_face = sepFaceEntry(false, face_query_b.faceIdx);
+        }
         return false;
     }
 

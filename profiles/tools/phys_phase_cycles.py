@@ -3,14 +3,22 @@
     make -C madrona_amd OUT=_build_prof EXTRA=-DMADRONA_PHYS_PROFILE=1 runtime \\
          _build_prof/libescape_room_phys_hip.so
 
-the kernel then adds s_memtime deltas per phase to ecs_state::moduleData[1])."""
+the kernel then adds s_memtime deltas per phase to ecs_state::moduleData[1]).
+
+    python profiles/tools/phys_phase_cycles.py [WORLDS [SIM]]
+
+SIM: escape_room_phys (default) or hideseek.  With PHYS_PROFILE_HH_IN_LDS=1 and a
+-DMADRONA_PHYS_PROFILE_LDS_HH build: the stages of the cooperative hull-hull
+tests and what the remembered separating faces did."""
 import sys, os, ctypes as C
 os.environ.setdefault('MADRONA_HIP_BUILD_DIR', '_build_prof')
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from madrona_amd.simlib import Simulator, hip_lib_path, runtime_lib
 W = int(sys.argv[1]) if len(sys.argv) > 1 else 8192
-with Simulator(hip_lib_path('escape_room_phys'), W, seed=5, flags=200) as hip:
+SIM = sys.argv[2] if len(sys.argv) > 2 else 'escape_room_phys'
+AGENTS = 5 if SIM == 'hideseek' else 2
+with Simulator(hip_lib_path(SIM), W, seed=5, flags=200) as hip:
     rt = runtime_lib()
     rt.mwhip_alloc_device.restype = C.c_void_p
     rt.mwhip_alloc_device.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
@@ -19,8 +27,8 @@ with Simulator(hip_lib_path('escape_room_phys'), W, seed=5, flags=200) as hip:
     import torch
     rng = np.random.default_rng(0)
     # a new action set every step (the bench's input ring)
-    ring = np.stack([np.stack([rng.integers(0, 4, (W, 2)), rng.integers(0, 8, (W, 2)),
-                               rng.integers(-2, 3, (W, 2)), rng.integers(0, 2, (W, 2))], -1)
+    ring = np.stack([np.stack([rng.integers(0, 4, (W, AGENTS)), rng.integers(0, 8, (W, AGENTS)),
+                               rng.integers(-2, 3, (W, AGENTS)), rng.integers(0, 2, (W, AGENTS))], -1)
                      for _ in range(61)]).astype(np.int32)
     dev = torch.from_numpy(ring).cuda()
     hip.set_input_ring('action', dev.data_ptr(), 61)
@@ -33,6 +41,9 @@ with Simulator(hip_lib_path('escape_room_phys'), W, seed=5, flags=200) as hip:
     rt.mwhip_memcpy_d2h(out.ctypes.data, buf, 256)
     if os.environ.get('PHYS_PROFILE_HH_IN_LDS'):
         # (-DMADRONA_PHYS_PROFILE_LDS_HH: the hull-hull stages sit in slots 0..8)
+        settled, unsettled = float(out[9]) / N / W, float(out[10]) / N / W
+        print(f'remembered separating faces per world and step: {settled:.2f} settled '
+              f'their pair on one lane, {unsettled:.2f} did not (the pair was tested)')
         hh, events, out = np.concatenate([out[:9], np.zeros(7, np.uint64)]), out[12:16], np.zeros(12, np.uint64)
         out[0] = 1
     else:

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded() and mwhip_digest_*() / mwhip_set_step_digest() (a per-world hash of chosen columns computed on the device) and mwhip_view_*() / mwhip_set_step_view() (padded per-world tensors of a table's columns) and mwhip_write_*() / mwhip_set_step_write() (padded per-world tensors scattered into a table's columns) and mwhip_reduce_term / mwhip_reduce_*() / mwhip_set_step_reduce() (per-world sums, extrema, counts and alarms of a table's columns) and mwhip_gather_source / mwhip_gather_*() / mwhip_set_step_gather() (the cells of the entities a run of handles in device memory names) and mwhip_scatter_*() / mwhip_set_step_scatter() (cells written into the entities such a run of handles names, the highest index winning among duplicates) and mwhip_rays_desc / mwhip_ray_args / mwhip_set_ray_kernel() / mwhip_rays_*() / mwhip_set_step_rays() (tensors of rays cast through the worlds' broadphase BVHs by a kernel the simulator's code object registers) and mwhip_boxes_desc / mwhip_box_args / mwhip_set_box_kernel() / mwhip_boxes_*() / mwhip_set_step_boxes() (tensors of boxes tested through the same BVHs, the whole list of each box's entities, by a second kernel the simulator's code object registers) and MWHIP_NODE_CARRIED / mwhip_broadphase_carry_stats() (launches a steady replay leaves out, a bit of mwhip_node_desc::kind that earlier libraries never set); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
+#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded() and mwhip_digest_*() / mwhip_set_step_digest() (a per-world hash of chosen columns computed on the device) and mwhip_view_*() / mwhip_set_step_view() (padded per-world tensors of a table's columns) and mwhip_write_*() / mwhip_set_step_write() (padded per-world tensors scattered into a table's columns) and mwhip_reduce_term / mwhip_reduce_*() / mwhip_set_step_reduce() (per-world sums, extrema, counts and alarms of a table's columns) and mwhip_gather_source / mwhip_gather_*() / mwhip_set_step_gather() (the cells of the entities a run of handles in device memory names) and mwhip_scatter_*() / mwhip_set_step_scatter() (cells written into the entities such a run of handles names, the highest index winning among duplicates) and mwhip_rays_desc / mwhip_ray_args / mwhip_set_ray_kernel() / mwhip_rays_*() / mwhip_set_step_rays() (tensors of rays cast through the worlds' broadphase BVHs by a kernel the simulator's code object registers) and mwhip_boxes_desc / mwhip_box_args / mwhip_set_box_kernel() / mwhip_boxes_*() / mwhip_set_step_boxes() (tensors of boxes tested through the same BVHs, the whole list of each box's entities, by a second kernel the simulator's code object registers) and mwhip_contacts_desc / mwhip_contact_args / mwhip_set_contact_kernel() / mwhip_contacts_*() / mwhip_set_step_contacts() (per-world tensors of the touching primitive pairs and their manifolds, the step's narrowphase run from outside by a third kernel the simulator's code object registers) and MWHIP_NODE_CARRIED / mwhip_broadphase_carry_stats() (launches a steady replay leaves out, a bit of mwhip_node_desc::kind that earlier libraries never set); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
 
 typedef struct mwhip_exec mwhip_exec; /* opaque; == MWCudaExecutor::Impl */
 
@@ -1480,6 +1480,130 @@ int mwhip_boxes_compute(mwhip_exec *exec, uint64_t boxes);
 int mwhip_boxes_compute_async(mwhip_exec *exec, uint64_t boxes);
 void *mwhip_boxes_buffer(mwhip_exec *exec, uint64_t boxes, uint32_t which, uint64_t *bytes_out);
 int mwhip_set_step_boxes(mwhip_exec *exec, uint64_t boxes, int on);
+
+/* Contact queries (added under ABI 9): per world the primitive pairs of its
+ * rigid bodies that TOUCH, with the manifold the narrowphase of the physics step
+ * builds for each -- which bodies, where, how deep (DESIGN.md §36;
+ * madrona_amd/contact_ref.py is the same definition in numpy with the
+ * narrowphase injected).  The step drops its contacts inside its kernel; this
+ * query runs the same narrowphase again, from outside.
+ * WHICH PAIRS.  The bodies of world w are the rows of the rigid-body archetypes
+ * in the step's iteration order, k = 0 .. n - 1.  Every pair k_lo < k_hi that is
+ * not Static-Static, and of it every primitive pair (aPrim, bPrim) of the two
+ * objects, where body `a` is the one with the LOWER ENTITY ID (as the step's
+ * broadphase assigns it); the pair is then ordered by primitive type as the step
+ * orders it.  A primitive pair is a contact iff the world boxes of the two
+ * primitives intersect (the step's own test) and the narrowphase returns a
+ * manifold with at least one point.  No BVH is involved: the result is a
+ * function of the tables alone.
+ * ORDER: ascending (k_lo, k_hi, aPrim * b_num_prims + bPrim).
+ * POSES.  Default: the SOLVER POSES, position and rotation of a body's
+ * xpbd::PreSolvePositional -- the poses the solver's last substep built its
+ * contacts at, where a resting body penetrates by about g h^2 instead of 0 +- an
+ * ulp; a body whose stored rotation is exactly (0, 0, 0, 0), never stepped since
+ * it was created, is taken at its current pose.  MWHIP_CONTACTS_CURRENT_POSES:
+ * Position and Rotation as they are now.  Scale, ObjectID and ResponseType are
+ * always the current ones.
+ * INPUT.  select[w], optional int32 per world: 0 skips the world.  Either a
+ * buffer the query owns (desc.own_select != 0; 1 at creation) or a SOURCE of the
+ * caller's, a mwhip_ray_source with a ray query's rules; neither: every world.
+ * OUTPUTS, owned, 256-byte aligned, every one rewritten in full by every compute
+ * (K = max_contacts):
+ *   status[w]        int32: MWHIP_CONTACTS_OK 0, MWHIP_CONTACTS_SKIPPED -1
+ *                    (select[w] == 0), MWHIP_CONTACTS_UNSORTED -2 (a rigid-body
+ *                    table waits for its world sort: no world has a row range),
+ *                    MWHIP_CONTACTS_UNSUPPORTED -3 (a primitive pair no path
+ *                    supports).  No sticky error flag is raised.
+ *   count[w]         int32: the world's contacts, NOT capped by K; 0 unless OK.
+ *   pairs[w][k][2]   Entity { uint32 gen; int32 id } x 2: the body that owns the
+ *                    reference feature, then the other (a reference face's body;
+ *                    `a` for an edge contact; the plane; of a sphere pair `b`).
+ *                    Entity::none() behind min(count, K): a valid
+ *                    mwhip_gather_source of W x K x 2 handles, record_bytes 8.
+ *   num_points[w][k] int32, 1 .. 4
+ *   normal[w][k][3]  float32
+ *   points[w][k][4][4]  float32: xyz world position, w penetration depth; point
+ *                    slots >= num_points are zero.
+ *                    All three zero behind min(count, K).
+ * THE KERNEL lives in the simulator's code object
+ * (phys_impl/contact_query.inl): PhysicsSystem::setupPhysicsStepTasks hands its
+ * host stub over with mwhip_set_contact_kernel (NULL is ignored); caps bit 0
+ * (MWHIP_CONTACT_CAP_SOLVER_POSES): the simulator's bodies have solver poses
+ * (XPBD).  Its single argument is a mwhip_contact_args by value.  A wavefront per
+ * world.  Two mappings that leave the same words: cooperative (the default: the
+ * step kernel's narrowphase on chunks of 64 pairs whose boxes intersect) and
+ * MWHIP_CONTACTS_PLAIN (every such pair through the generic single-lane
+ * routine, the definition itself).
+ * mwhip_set_step_contacts(on != 0): every replay of every STEP graph recomputes
+ * the query directly behind the step box queries and in front of the step
+ * gathers (which may read `pairs`).  Up to MWHIP_MAX_STEP_CONTACTS, ONE launch
+ * for all, listed by mwhip_profile as "contacts" with role "contacts"; none when
+ * none is set.  Destroying a step query unsets it.  Contact queries are derived
+ * state: snapshots do not save them.
+ * Errors (non-zero, text in mwhip_last_error(), nothing changed or allocated):
+ * -3 for an unknown handle or one of another executor; -2 for no registered
+ * kernel, solver poses asked of a simulator without them ("this simulator has
+ * no solver poses"), max_contacts == 0, W x K x 2 > 2^31 - 1, an unknown flag,
+ * a bad source (as for rays; also a source together with own_select), a fifth
+ * step query; -10 for buffers that cannot be allocated.
+ * (No reference counterpart: the reference clears its contacts every substep.) */
+#define MWHIP_MAX_STEP_CONTACTS 4
+#define MWHIP_CONTACTS_OK 0
+#define MWHIP_CONTACTS_SKIPPED (-1)
+#define MWHIP_CONTACTS_UNSORTED (-2)
+#define MWHIP_CONTACTS_UNSUPPORTED (-3)
+#define MWHIP_CONTACTS_CURRENT_POSES 1u     /* mwhip_contacts_desc::flags */
+#define MWHIP_CONTACTS_PLAIN 2u
+#define MWHIP_CONTACT_CAP_SOLVER_POSES 1u   /* mwhip_set_contact_kernel caps */
+#define MWHIP_CONTACTS_BUF_SELECT 0u
+#define MWHIP_CONTACTS_BUF_STATUS 1u
+#define MWHIP_CONTACTS_BUF_COUNT 2u
+#define MWHIP_CONTACTS_BUF_PAIRS 3u
+#define MWHIP_CONTACTS_BUF_NUM_POINTS 4u
+#define MWHIP_CONTACTS_BUF_NORMAL 5u
+#define MWHIP_CONTACTS_BUF_POINTS 6u
+#define MWHIP_CONTACTS_NUM_BUFS 7u
+typedef struct mwhip_contacts_desc {
+    uint32_t max_contacts;          /* K >= 1 */
+    uint32_t flags;                 /* MWHIP_CONTACTS_CURRENT_POSES | _PLAIN */
+    uint32_t own_select;            /* != 0: an owned select buffer */
+    uint32_t pad_;
+    mwhip_ray_source select;        /* src == NULL: none (or the owned one) */
+} mwhip_contacts_desc;
+/* what the kernel reads of one query (device-resident, filled by the runtime;
+ * first_byte is already added to the source) */
+typedef struct mwhip_contact_plan {
+    void *state;                    /* the executor's ecs state on the device */
+    const char *select_src;         /* NULL: every world */
+    int32_t *status;                /* [W] */
+    int32_t *count;                 /* [W] */
+    uint32_t *pairs;                /* [W][K][2][2] */
+    int32_t *num_points;            /* [W][K] */
+    float *normal;                  /* [W][K][3] */
+    float *points;                  /* [W][K][4][4] */
+    uint32_t select_stride;         /* bytes */
+    uint32_t max_contacts, flags, num_worlds;
+} mwhip_contact_plan;
+/* the kernel's argument, by value: a wavefront serves world w of every plan,
+ * one plan after the other; items[p] == the number of worlds */
+typedef struct mwhip_contact_args {
+    uint32_t num_plans;
+    uint32_t pad_;
+    uint32_t items[MWHIP_MAX_STEP_CONTACTS];
+    const mwhip_contact_plan *plans[MWHIP_MAX_STEP_CONTACTS];
+} mwhip_contact_args;
+/* the simulator's contact kernel: __global__ void(mwhip_contact_args), 256 threads */
+int mwhip_set_contact_kernel(mwhip_exec *exec, const void *kernel, uint32_t caps);
+int mwhip_contacts_create(mwhip_exec *exec, const mwhip_contacts_desc *desc,
+                          uint64_t *contacts_out);
+void mwhip_contacts_destroy(mwhip_exec *exec, uint64_t contacts);
+/* waits for the executor's stream */
+int mwhip_contacts_compute(mwhip_exec *exec, uint64_t contacts);
+/* queued on the executor's stream behind the replays queued so far */
+int mwhip_contacts_compute_async(mwhip_exec *exec, uint64_t contacts);
+void *mwhip_contacts_buffer(mwhip_exec *exec, uint64_t contacts, uint32_t which,
+                            uint64_t *bytes_out);
+int mwhip_set_step_contacts(mwhip_exec *exec, uint64_t contacts, int on);
 
 #ifdef __cplusplus
 }

@@ -39,3 +39,5 @@ def build_oracle() -> None:
         # MeshBVH queries behind the manager's probes)
         _make(oracle_dir, "_ref/libmesh_cast_ref.so",
               "_ref/libmesh_cast_ref_speed.so")
+        # contact_probe (contact queries): likewise
+        _make(oracle_dir, "_ref/libcontact_probe_ref.so")

@@ -282,6 +282,7 @@ struct mwhip_gather_rec;        // (entity_gather.hip)
 struct mwhip_scatter_rec;       // (entity_scatter.hip)
 struct mwhip_rays_rec;          // (ray_query.hip)
 struct mwhip_boxes_rec;         // (box_query.hip)
+struct mwhip_contacts_rec;      // (contact_query.hip)
 
 // What a replay carries besides its task graphs.  Every launch graph is built
 // from it (the input rings, the step writes and the step scatters open a step graph, the rest are tail stages:
@@ -330,6 +331,9 @@ struct ReplayExtras {
     // mwhip_set_step_boxes: those every step replay recomputes, in one launch
     // directly behind the step ray queries
     std::vector<uint64_t> stepBoxes;
+    // mwhip_set_step_contacts: those every step replay recomputes, in one
+    // launch directly behind the step box queries
+    std::vector<uint64_t> stepContacts;
 };
 
 struct mwhip_exec {
@@ -428,6 +432,11 @@ struct mwhip_exec {
     const void *rayKernel = nullptr;
     // mwhip_set_box_kernel: the simulator's boxQueryKernel, likewise
     const void *boxKernel = nullptr;
+    // mwhip_set_contact_kernel: the simulator's contactQueryKernel (null: it
+    // has no rigid-body step, hence no narrowphase) and what it can do
+    // (MWHIP_CONTACT_CAP_*)
+    const void *contactKernel = nullptr;
+    uint32_t contactCaps = 0;
     void *pforBodyScratch = nullptr;        // 8 bytes: where report mode writes
     // MADRONA_MWHIP_EXEC_CONFIG_FILE (the reference's
     // MADRONA_MWGPU_EXEC_CONFIG_FILE, cuda_exec.cpp:2115-2172): per task-graph
@@ -459,6 +468,7 @@ struct mwhip_exec {
     ExecObjectTable<mwhip_scatter_rec> scatters;   // mwhip_scatter_create
     ExecObjectTable<mwhip_rays_rec> rays;          // mwhip_rays_create
     ExecObjectTable<mwhip_boxes_rec> boxes;        // mwhip_boxes_create
+    ExecObjectTable<mwhip_contacts_rec> contacts;  // mwhip_contacts_create
 };
 
 // Bumped by what changes device memory or fails without naming an executor
@@ -549,6 +559,9 @@ MWHIP_RT int stepRaysStage(mwhip_exec *exec, const LaunchGraph &lg,
 MWHIP_RT int stepBoxesStage(mwhip_exec *exec, const LaunchGraph &lg,
                             std::vector<KernelLaunch> &out);
       // (box_query.hip)
+MWHIP_RT int stepContactsStage(mwhip_exec *exec, const LaunchGraph &lg,
+                               std::vector<KernelLaunch> &out);
+      // (contact_query.hip)
 MWHIP_RT int stepScatterStage(mwhip_exec *exec, const LaunchGraph &lg,
                               std::vector<KernelLaunch> &out);
       // (entity_scatter.hip)

@@ -688,6 +688,7 @@ extern "C" void mwhip_destroy(mwhip_exec *exec)
     exec->scatters.clear();
     exec->rays.clear();
     exec->boxes.clear();
+    exec->contacts.clear();
     for (void *p : exec->allocations) {
         (void)hipFree(p);
     }

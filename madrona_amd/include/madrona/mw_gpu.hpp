@@ -177,8 +177,8 @@ friend class MWCudaExecutor;
 namespace detail {
 
 // What MWHipSnapshot, MWHipDigest, MWHipWorldView, MWHipWorldWrite,
-// MWHipWorldReduce, MWHipEntityGather, MWHipEntityScatter, MWHipRayQuery and
-// MWHipBoxQuery share: the move-only handle
+// MWHipWorldReduce, MWHipEntityGather, MWHipEntityScatter, MWHipRayQuery,
+// MWHipBoxQuery and MWHipContactQuery share: the move-only handle
 // of an object that belongs to an executor (mwhip_<kind>_create / _destroy,
 // include/mwhip.h), the device its buffers are on, and how one of those
 // buffers becomes a py::Tensor.  Kind: { name, destroy(exec, handle) }.
@@ -290,6 +290,10 @@ struct RayQueryKind {
 struct BoxQueryKind {
     static constexpr const char *name = "box query";
     static void destroy(mwhip_exec *exec, uint64_t handle) { mwhip_boxes_destroy(exec, handle); }
+};
+struct ContactQueryKind {
+    static constexpr const char *name = "contact query";
+    static void destroy(mwhip_exec *exec, uint64_t handle) { mwhip_contacts_destroy(exec, handle); }
 };
 
 }
@@ -756,6 +760,96 @@ private:
     uint64_t num_bundles_;
     uint64_t num_boxes_;
     uint64_t max_hits_;
+
+friend class MWCudaExecutor;
+};
+
+// Which bodies touch, where and how deep: per world int32 status
+// (MWHIP_CONTACTS_OK, _SKIPPED, _UNSORTED, _UNSUPPORTED), int32 count (not capped)
+// and the first maxContacts() contacts in the order (k_lo, k_hi, primitive
+// pair) -- the Entity handles of the body that owns the reference feature and of
+// the other, the number of points, the normal, and four points (xyz world
+// position, w depth; zero from the number of points on).  mwhip_contacts_*,
+// include/mwhip.h, is the exact definition: which pairs are tested, that solver
+// poses (xpbd::PreSolvePositional) are the default and what
+// MWHIP_CONTACTS_CURRENT_POSES takes instead, that no BVH is walked.  Needs a
+// simulator that sets up a rigid-body step.  An extension of this backend.
+// Belongs to the executor that made it and must not outlive it, nor its source.
+class MWHipContactQuery : public detail::ExecObject<detail::ContactQueryKind> {
+public:
+    MWHipContactQuery() : num_worlds_(0), max_contacts_(0) {}
+
+    // waits for the executor's stream
+    void compute() { req(mwhip_contacts_compute(exec_, handle_), "compute"); }
+    // queued on the executor's stream behind the replays queued so far
+    void computeAsync() { req(mwhip_contacts_compute_async(exec_, handle_), "computeAsync"); }
+
+    // the input the query owns if desc.own_select was set: int32 [numWorlds()]
+    py::Tensor selectTensor() const
+    {
+        return tensor(buffer(MWHIP_CONTACTS_BUF_SELECT), Elem::Int32, { num_worlds_ },
+                      "selectTensor");
+    }
+
+    // outputs: int32 [numWorlds()] twice; int32 [numWorlds()][maxContacts()][4]
+    // (ref gen, ref id, alt gen, alt id); int32 [numWorlds()][maxContacts()];
+    // float [numWorlds()][maxContacts()][3]; float [numWorlds()][maxContacts()][16]
+    py::Tensor statusTensor() const
+    {
+        return tensor(buffer(MWHIP_CONTACTS_BUF_STATUS), Elem::Int32, { num_worlds_ },
+                      "statusTensor");
+    }
+    py::Tensor countsTensor() const
+    {
+        return tensor(buffer(MWHIP_CONTACTS_BUF_COUNT), Elem::Int32, { num_worlds_ },
+                      "countsTensor");
+    }
+    py::Tensor pairsTensor() const
+    {
+        return tensor(buffer(MWHIP_CONTACTS_BUF_PAIRS), Elem::Int32,
+                      { num_worlds_, max_contacts_, 4 }, "pairsTensor");
+    }
+    py::Tensor numPointsTensor() const
+    {
+        return tensor(buffer(MWHIP_CONTACTS_BUF_NUM_POINTS), Elem::Int32,
+                      { num_worlds_, max_contacts_ }, "numPointsTensor");
+    }
+    py::Tensor normalsTensor() const
+    {
+        return tensor(buffer(MWHIP_CONTACTS_BUF_NORMAL), Elem::Float32,
+                      { num_worlds_, max_contacts_, 3 }, "normalsTensor");
+    }
+    py::Tensor pointsTensor() const
+    {
+        return tensor(buffer(MWHIP_CONTACTS_BUF_POINTS), Elem::Float32,
+                      { num_worlds_, max_contacts_, 16 }, "pointsTensor");
+    }
+
+    // the pairs as the source of an entity gather or scatter: numWorlds() x
+    // maxContacts() x 2 handles (a contact's ref, then its alt)
+    mwhip_gather_source handleSource() const
+    {
+        void *ptr = buffer(MWHIP_CONTACTS_BUF_PAIRS);
+        req(ptr != nullptr ? 0 : -1, "handleSource");
+        return mwhip_gather_source { ptr, num_worlds_ * max_contacts_ * 2u, 8u, 0u, 1u, 0u };
+    }
+
+    uint64_t maxContacts() const { return max_contacts_; }
+
+private:
+    MWHipContactQuery(mwhip_exec *exec, uint64_t contacts, uint64_t num_worlds,
+                      uint64_t max_contacts, int32_t gpu_id)
+        : ExecObject(exec, contacts, gpu_id), num_worlds_(num_worlds),
+          max_contacts_(max_contacts)
+    {}
+
+    void *buffer(uint32_t which) const
+    {
+        return mwhip_contacts_buffer(exec_, handle_, which, nullptr);
+    }
+
+    uint64_t num_worlds_;
+    uint64_t max_contacts_;
 
 friend class MWCudaExecutor;
 };
@@ -1272,6 +1366,26 @@ public:
     void setStepBoxes(const MWHipBoxQuery *boxes, bool on)
     {
         setStep(mwhip_set_step_boxes, boxes, "setStepBoxes", on ? 1 : 0);
+    }
+
+    // per world up to desc.max_contacts touching primitive pairs of its rigid
+    // bodies with their manifolds (see MWHipContactQuery and
+    // mwhip_contacts_desc)
+    MWHipContactQuery makeContactQuery(const mwhip_contacts_desc &desc)
+    {
+        uint64_t contacts = 0;
+        req(mwhip_contacts_create(exec_, &desc, &contacts), "makeContactQuery");
+        return MWHipContactQuery(exec_, contacts, mwhip_num_worlds(exec_), desc.max_contacts,
+                                 gpu_id_);
+    }
+
+    // on: every replay of a step graph recomputes `contacts` directly behind
+    // its step box queries and in front of its step gathers (which may read
+    // the pairs), its pack node and its output rings (up to
+    // MWHIP_MAX_STEP_CONTACTS queries, one launch for all); off: no longer
+    void setStepContacts(const MWHipContactQuery *contacts, bool on)
+    {
+        setStep(mwhip_set_step_contacts, contacts, "setStepContacts", on ? 1 : 0);
     }
 
     // Device-resident rings (extensions of this backend, include/mwhip.h).

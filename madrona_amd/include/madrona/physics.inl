@@ -1761,6 +1761,8 @@ bvhUpdateKernel(EcsState *S, void *, uint32_t, uint32_t)
 #include <madrona/phys_impl/ray_query.inl>
 // the box queries' kernel (mwhip_boxes_*): boxQueryKernel
 #include <madrona/phys_impl/box_query.inl>
+// the contact queries' kernel (mwhip_contacts_*): contactQueryKernel
+#include <madrona/phys_impl/contact_query.inl>
 }
 #endif // __HIPCC__
 
@@ -2232,8 +2234,12 @@ MADRONA_HOST_API inline TaskGraphNodeID setupBroadphaseTasks(
 namespace detail {
 
 #if MADRONA_ON_HOST
+// (step_segments == false: a simulator whose step keeps no candidates and
+// contacts of its own -- TGS -- and needs the block only for what a contact
+// query reads of it: the body archetypes and the per-world hull scratch)
 inline PhysicsScratch *scratchHost(TaskGraphBuilder &builder,
-                                   PhysicsScratch *host_copy_out)
+                                   PhysicsScratch *host_copy_out,
+                                   bool step_segments = true)
 {
     // one scratch block per executor (kept in the executor's module slot 0),
     // shared by every graph that has physics
@@ -2274,9 +2280,9 @@ inline PhysicsScratch *scratchHost(TaskGraphBuilder &builder,
     ps.jointArchetype = TypeTracker::typeID<xpbd::Joint>();
 
     const uint64_t num_worlds = mwhip_num_worlds(exec);
-    ps.candidatesPerWorld = (uint32_t)phys::detail::capacityHint(
+    ps.candidatesPerWorld = !step_segments ? 1u : (uint32_t)phys::detail::capacityHint(
         "MADRONA_MWHIP_MAX_CANDIDATES_PER_WORLD", 256);
-    ps.contactsPerWorld = (uint32_t)phys::detail::capacityHint(
+    ps.contactsPerWorld = !step_segments ? 1u : (uint32_t)phys::detail::capacityHint(
         "MADRONA_MWHIP_MAX_CONTACTS_PER_WORLD", 128);
     ps.worldCandidates = (CandidateCollision *)mwhip_alloc_device(exec,
         num_worlds * ps.candidatesPerWorld * sizeof(CandidateCollision), 0);
@@ -2549,6 +2555,30 @@ MADRONA_HOST_API inline TaskGraphNodeID setupPhysicsStepTasks(
     CountT num_substeps,
     Solver solver)
 {
+#if defined(__HIPCC__)
+    [[maybe_unused]] auto contact_stub = [] __host__ () -> const void * {
+        return (const void *)&kernels::contactQueryKernel;
+    };
+#else
+    auto contact_stub = []() -> const void * { return nullptr; };
+#endif
+#if MADRONA_ON_HOST
+    // a simulator with a rigid-body step has contact queries
+    // (mwhip_contacts_create): the narrowphase is in this code object, the
+    // runtime launches it.  Only XPBD bodies keep the poses their contacts were
+    // solved at (xpbd::PreSolvePositional).  The kernel finds the body tables
+    // and its one-lane-at-a-time hull scratch through the module's scratch
+    // block (the XPBD step makes it below; the TGS step does not use it and
+    // gets it without the step's per-world segments).
+    if (solver == Solver::TGS) {
+        PhysicsScratch contact_ps;
+        detail::scratchHost(builder, &contact_ps, false);
+    }
+    mwhip::check(mwhip_set_contact_kernel(builder.exec(), contact_stub(),
+                     solver == Solver::TGS ? 0u : MWHIP_CONTACT_CAP_SOLVER_POSES),
+                 "set_contact_kernel");
+#endif
+
     if (solver == Solver::TGS) {
         // reference tgs.cpp:225-304 without the stages that have no effect
         // (phys_impl/tgs.hpp): per substep the two integrators, then the leaf

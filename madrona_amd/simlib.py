@@ -162,6 +162,12 @@ class BoxesDesc(C.Structure):
                 ("world", RaySource), ("count", RaySource), ("centre", RaySource)]
 
 
+class ContactsDesc(C.Structure):
+    """mwhip_contacts_desc (include/mwhip.h)."""
+    _fields_ = [("max_contacts", C.c_uint32), ("flags", C.c_uint32),
+                ("own_select", C.c_uint32), ("pad_", C.c_uint32), ("select", RaySource)]
+
+
 class SortStats(C.Structure):
     """mwhip_sort_counters (include/mwhip.h)"""
     _fields_ = [(name, C.c_uint64) for name in
@@ -201,6 +207,7 @@ _KINDS = {
     "scatter": (("apply",), ("select", "archetypes", "worlds", "written")),
     "rays": (("compute",), ()),
     "boxes": (("compute",), ()),
+    "contacts": (("compute",), ()),
 }
 
 _runtime = None
@@ -279,11 +286,12 @@ def runtime_lib() -> C.CDLL:
                  [C.c_void_p, C.POINTER(GatherSource), _U32P, C.c_uint32, _U64P])
     for stem in ("view", "write", "reduce", "gather", "scatter"):
         _declare(lib, f"mwhip_{stem}_buffer", C.c_void_p, _OBJECT + [C.c_uint32, _U64P, _U32P])
-    for stem, desc in (("rays", RaysDesc), ("boxes", BoxesDesc)):
+    for stem, desc in (("rays", RaysDesc), ("boxes", BoxesDesc), ("contacts", ContactsDesc)):
         _declare(lib, f"mwhip_{stem}_create", C.c_int, [C.c_void_p, C.POINTER(desc), _U64P])
         _declare(lib, f"mwhip_{stem}_buffer", C.c_void_p, _OBJECT + [C.c_uint32, _U64P])
     _declare(lib, "mwhip_set_ray_kernel", C.c_int, [C.c_void_p, C.c_void_p])
     _declare(lib, "mwhip_set_box_kernel", C.c_int, [C.c_void_p, C.c_void_p])
+    _declare(lib, "mwhip_set_contact_kernel", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32])
     _runtime = lib
     return lib
 
@@ -319,7 +327,7 @@ class _Checked:
 
 
 class _ExecObject(_Checked):
-    """What Snapshot, StateDigest, WorldView, WorldWrite, WorldReduce, EntityGather, EntityScatter, RayQuery and BoxQuery are: something a simulator's
+    """What Snapshot, StateDigest, WorldView, WorldWrite, WorldReduce, EntityGather, EntityScatter, RayQuery, BoxQuery and ContactQuery are: something a simulator's
     executor owns, named by `handle` there, kept in one of the simulator's
     lists (`_list`) while it is open.  close() frees it and takes it off the
     list (a snapshot too, which used to stay on it until the simulator closed); Simulator.close() frees the executor and orphans
@@ -1142,15 +1150,11 @@ class EntityScatter(_Applied, _HandleCells):
         return self._int32("written", self.written_ptr, self.num_handles)
 
 
-class _TreeQuery(_Computed, _StepObject):
-    """What RayQuery and BoxQuery share: groups (fans, bundles) that each have a
-    world and a point (origin, centre), either in a buffer the query owns or
-    read from the caller's source, and buffers asked for by name
-    (mwhip_<stem>_buffer, _BUFS)."""
+class _Sourced:
+    """What RayQuery, BoxQuery and ContactQuery share: inputs that may be read
+    from the caller's source (mwhip_ray_source)."""
 
     _what = ""      # in messages
-    _BUFS: Dict[str, int] = {}
-    _PER_WORLD = ("", "")       # the constructor's groups-per-world argument, a group
 
     @classmethod
     def _source(cls, what: str, source, item_bytes: int):
@@ -1173,6 +1177,16 @@ class _TreeQuery(_Computed, _StepObject):
         if record < item_bytes:
             raise TypeError(f"{cls._what}: rows of {record} bytes are too short for {what}")
         return source, RaySource(source.data_ptr(), record, 0)
+
+
+class _TreeQuery(_Computed, _Sourced, _StepObject):
+    """What RayQuery and BoxQuery share: groups (fans, bundles) that each have a
+    world and a point (origin, centre), either in a buffer the query owns or
+    read from the caller's source, and buffers asked for by name
+    (mwhip_<stem>_buffer, _BUFS)."""
+
+    _BUFS: Dict[str, int] = {}
+    _PER_WORLD = ("", "")       # the constructor's groups-per-world argument, a group
 
     def _open_query(self, sim: "Simulator", desc, world, count, point: str, given,
                     per_world: int) -> None:
@@ -1376,6 +1390,120 @@ class BoxQuery(_TreeQuery):
         return (self.buffer_ptr("hits"), self.num_boxes * self.max_hits, 8, 0, 1)
 
 
+class ContactQuery(_Computed, _Sourced, _StepObject):
+    """Per world the primitive pairs of its rigid bodies that touch, with the
+    manifold the physics step's narrowphase builds for each: which bodies, where,
+    how deep (mwhip_contacts_*, include/mwhip.h; madrona_amd/contact_ref.py is
+    the exact definition).  The bodies of a world are the rows of its rigid-body
+    tables in the step's order; every pair of them that is not Static-Static and
+    every primitive pair of the two objects is tested, the body of lower entity
+    id as `a`; a pair is a contact iff the primitives' world boxes intersect and
+    the narrowphase returns at least one point.  Contacts come in the order
+    (k_lo, k_hi, primitive pair).  No BVH is walked.
+    poses="solver" (the default, XPBD simulators only) takes each body where the
+    solver's last substep built its contacts (xpbd::PreSolvePositional), where a
+    resting body penetrates by about g h^2 and a resting contact does not
+    flicker; a body never stepped since it was created is taken as it is.
+    poses="current" takes Position and Rotation as they are now, e.g. right
+    after a world write.  Input: selects() int32 [W] if select=True (owned, 1 at
+    creation), or `select` a device tensor / (ptr, record_bytes, first_byte)
+    read when the kernel runs; 0 skips the world.  Outputs, rewritten in full by
+    every compute, zero-copy torch tensors: status() int32 [W] (OK 0, SKIPPED
+    -1, UNSORTED -2, UNSUPPORTED -3), counts() int32 [W] (not capped by K, 0
+    unless OK), pairs() int32 [W, K, 2, 2] ((gen, id) of the body that owns the
+    reference feature, then of the other; -1, -1 behind min(count, K)),
+    num_points() int32 [W, K], normals() float32 [W, K, 3], points() float32 [W,
+    K, 4, 4] (xyz world position, w depth; zero from num_points on and behind
+    min(count, K)).  handle_source() is what entity_gather() / entity_scatter()
+    take to go from pairs to cells.  plain=True sends every pair through the
+    generic single-lane routine, one at a time: the same words, slowly.
+    compute() waits for the executor's stream, compute_async() queues behind the
+    replays queued so far; every_step() makes every replay of a step graph
+    recompute the query behind its step box queries and in front of its step
+    gathers and output rings.  HIP backend only."""
+
+    _kind, _stem, _list = "contact query", "contacts", "_contact_queries"
+    OK, SKIPPED, UNSORTED, UNSUPPORTED = 0, -1, -2, -3
+    CURRENT_POSES, PLAIN = 1, 2
+    _BUFS = {"select": 0, "status": 1, "count": 2, "pairs": 3, "num_points": 4, "normal": 5,
+             "points": 6}
+    _what = "contact_query()"
+
+    def __init__(self, sim: "Simulator", max_contacts: int, select=None, poses: str = "solver",
+                 plain: bool = False):
+        if poses not in ("solver", "current"):
+            raise ValueError(f'contact_query(): poses is "solver" or "current", not {poses!r}')
+        self.max_contacts = int(max_contacts)
+        self.poses, self.plain = poses, bool(plain)
+        self.num_worlds = sim.num_worlds
+        self._open(sim)
+        own = select is True
+        self._source_kept, source = self._source("select", None if own else select, 4)
+        desc = ContactsDesc(self.max_contacts,
+                            (self.CURRENT_POSES if poses == "current" else 0) |
+                            (self.PLAIN if self.plain else 0), 1 if own else 0, 0, source)
+        self._create(C.byref(desc))
+        self._owns_select = own
+
+    def _orphan(self) -> None:
+        super()._orphan()
+        self._source_kept = None
+
+    def buffer_ptr(self, name: str) -> int:
+        """Device address of owned buffer `name` (a key of _BUFS)."""
+        handle = self._live()
+        nbytes = C.c_uint64(0)
+        ptr = self._rt.mwhip_contacts_buffer(self._exec, handle, self._BUFS[name],
+                                             C.byref(nbytes))
+        if not ptr:
+            raise RuntimeError(
+                f"mwhip_contacts_buffer({name}): {self._rt.mwhip_last_error().decode()}")
+        return int(ptr)
+
+    def _tensor(self, name, dtype, shape):
+        self._live()
+        if name not in self._tensors:
+            self._wrap(name, self.buffer_ptr(name), dtype, shape)
+        return self._tensors[name]
+
+    def selects(self):
+        """int32 [W], 1 at creation (owned: select=True)"""
+        if not self._owns_select:
+            raise RuntimeError("this contact query owns no select buffer: make it with "
+                               "select=True")
+        return self._tensor("select", np.int32, (self.num_worlds,))
+
+    def status(self):
+        """int32 [W]: OK 0, SKIPPED -1, UNSORTED -2, UNSUPPORTED -3"""
+        return self._tensor("status", np.int32, (self.num_worlds,))
+
+    def counts(self):
+        """int32 [W]: the world's contacts, not capped by max_contacts"""
+        return self._tensor("count", np.int32, (self.num_worlds,))
+
+    def pairs(self):
+        """int32 [W, K, 2, 2]: (gen, id) of ref, then of alt; -1 behind min(count, K)"""
+        return self._tensor("pairs", np.int32, (self.num_worlds, self.max_contacts, 2, 2))
+
+    def num_points(self):
+        """int32 [W, K]"""
+        return self._tensor("num_points", np.int32, (self.num_worlds, self.max_contacts))
+
+    def normals(self):
+        """float32 [W, K, 3]"""
+        return self._tensor("normal", np.float32, (self.num_worlds, self.max_contacts, 3))
+
+    def points(self):
+        """float32 [W, K, 4, 4]: xyz world position, w penetration depth"""
+        return self._tensor("points", np.float32, (self.num_worlds, self.max_contacts, 4, 4))
+
+    def handle_source(self):
+        """The pairs as a source of Simulator.entity_gather() / entity_scatter():
+        (ptr, num_records, record_bytes, first_byte, handles_per_record);
+        handle 2 * (w * K + k) is contact k's ref, the next one its alt."""
+        return (self.buffer_ptr("pairs"), self.num_worlds * self.max_contacts * 2, 8, 0, 1)
+
+
 class Simulator:
     """One simulator instance behind the C API (either backend)."""
 
@@ -1401,7 +1529,7 @@ class Simulator:
         self._async = None
         # what is open, a list per kind, named by the class's `_list`: _snapshots,
         # _digests, _views, _writes, _reduces, _gathers, _scatters, _ray_queries,
-        # _box_queries; and _trajectories
+        # _box_queries, _contact_queries; and _trajectories
         self._trajectories: List["Trajectory"] = []
         for name in _ExecObject._lists:
             setattr(self, name, [])
@@ -1673,6 +1801,18 @@ class Simulator:
         words).  Simulator.close() frees what is left open."""
         return self._make(BoxQuery, "box queries need", bundles, boxes_per_bundle, max_hits,
                           world, centre, bundles_per_world, count, packed)
+
+    def contact_query(self, max_contacts: int, select=None, poses: str = "solver",
+                      plain: bool = False) -> "ContactQuery":
+        """A ContactQuery: per world up to `max_contacts` touching primitive
+        pairs of its rigid bodies with their manifolds (HIP backend, a simulator
+        with a rigid-body step).  poses: "solver" (XPBD: where the last substep
+        solved them) or "current".  select: None (every world), True (an owned
+        int32 per world, selects()), a device tensor whose rows are the records
+        or (ptr, record_bytes, first_byte).  plain: the generic routine, pair
+        after pair (same words).  Simulator.close() frees what is left open."""
+        return self._make(ContactQuery, "contact queries need", max_contacts, select, poses,
+                          plain)
 
     def record(self, names: List[str], steps: int, on_render: bool = False) -> "Trajectory":
         """Records the exported tensors `names` on the device from the next

@@ -127,11 +127,6 @@ struct GatherColumn {
     uint32_t wordBytes;             // 16 / 8 / 4 / 1
     uint32_t wordsPerRow;
     unsigned long long invMagic;    // floor(2^64 / wordsPerRow) + 1
-    // rows of whole dwords move in 16-byte chunks of the destination
-    // (gatherRowsWide); 0: word by word as described above
-    uint32_t rowDwords;
-    uint32_t pad_;
-    unsigned long long invMagicDwords;  // floor(2^64 / rowDwords) + 1
 };
 
 // One workgroup of the gather: slice `slice` of `numSlices` of a column.  The
@@ -167,7 +162,6 @@ struct SortBatch {
     GatherSlice *gatherSlicesDev = nullptr;
     uint32_t numGatherSlices = 0;
     bool hasPinned = false;         // a sorted table has exported columns
-    bool gatherWide = false;        // some column moves in 16-byte chunks (sortGather<true>)
     uint32_t maxCapacity = 0;
     // every table of the batch holds few rows: one launch (sortSmall) instead
     // of the chain.  Decided from the rows the tables hold when the graph is

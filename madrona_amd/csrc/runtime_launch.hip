@@ -189,19 +189,6 @@ static int makeSortBatch(mwhip_exec *exec,
             gc.wordsPerRow = bytes / gc.wordBytes;
             gc.invMagic = gc.wordsPerRow <= 1 ? 0ull :
                 (~0ull / gc.wordsPerRow) + 1ull;
-            // MADRONA_MWHIP_GATHER_WIDE=1: rows of whole dwords in 16-byte chunks
-            // of the destination (round 3's default).  Re-measured in round 4
-            // next to the blocked assignment (profiles/r04_sort_variants.jsonl):
-            // word by word is as fast or faster at every size -- 15.0 against
-            // 15.6 us at 4096 Escape-Room worlds, 28.1 against 30.7 at 8192 with
-            // physics, 168 against 204 at 65536 -- so that is the default again.
-            const bool wide = envU32("MADRONA_MWHIP_GATHER_WIDE", 0) != 0;
-            if (wide && bytes % 4 == 0 && bytes != 0) {
-                gc.rowDwords = bytes / 4;
-                out->gatherWide = true;
-                gc.invMagicDwords = gc.rowDwords <= 1 ? 0ull :
-                    (~0ull / gc.rowDwords) + 1ull;
-            }
             cols.push_back(gc);
         }
         sites.back().numGatherColumns = site_columns;

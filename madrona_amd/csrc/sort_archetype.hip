@@ -647,107 +647,6 @@ __device__ inline void gatherWords(const WordT *__restrict__ src,
     }
 }
 
-// Columns whose rows are whole dwords (all but 1- / 2-byte components), moved in
-// 16-byte chunks of the DESTINATION: dst is a dense array of rows, so chunk k
-// = dwords [4k, 4k + 4) of it is one aligned 16-byte store.  Its source dwords
-// belong to at most two rows when a row has >= 2 dwords, to four rows of a
-// 4-byte column; they are contiguous in the source too whenever those rows are
-// consecutive there (perm[r + 1] == perm[r] + 1) -- almost always: a world
-// sort moves rows in long runs -- and then they are one (dword-aligned) 16-byte
-// load.  12- and 28-byte components (positions, solver state: most of a rigid
-// body's bytes) would otherwise move 4 bytes per lane per instruction.
-struct __attribute__((packed, aligned(4))) Dwords4 { uint32_t x, y, z, w; };
-
-__device__ inline void gatherRowsWide(const uint32_t *__restrict__ src,
-                                      uint32_t *__restrict__ dst,
-                                      const int32_t *__restrict__ perm,
-                                      int32_t num_rows, uint32_t row_dwords,
-                                      unsigned long long inv_magic,
-                                      int32_t first, int32_t step)
-{
-    const long long total = (long long)num_rows * row_dwords;
-    const long long chunks = total >> 2;
-    constexpr int kBatch = 4;
-
-    auto move = [&](long long k0, int count) {
-        // (count <= kBatch chunks k0, k0 + step, ...: independent chains)
-        long long src_at[kBatch];   // source dword of the chunk's first dword
-        int32_t row_b[kBatch];      // source row of the dwords behind `split`
-        uint32_t split[kBatch];     // dwords of the chunk that come from the first row
-        bool contiguous[kBatch];
-        uint4 rows4[kBatch];
-#pragma unroll
-        for (int u = 0; u < kBatch; u++) {
-            if (u >= count) continue;
-            const long long d0 = (k0 + (long long)u * step) << 2;
-            if (row_dwords == 1u) {
-                const uint4 p = *(const uint4 *)(perm + d0);
-                rows4[u] = p;
-                src_at[u] = (long long)(int32_t)p.x;
-                contiguous[u] = p.y == p.x + 1u && p.z == p.x + 2u && p.w == p.x + 3u;
-                split[u] = 1u;
-                row_b[u] = 0;
-            } else {
-                const uint32_t r0 =
-                    (uint32_t)__umul64hi((unsigned long long)d0, inv_magic);
-                const uint32_t o0 = (uint32_t)(d0 - (long long)r0 * row_dwords);
-                const int32_t p0 = perm[r0];
-                // (the chunk ends inside row r0, or in row r0 + 1 which exists:
-                // d0 + 3 < total)
-                const bool crosses = o0 + 4u > row_dwords;
-                const int32_t p1 = crosses ? perm[r0 + 1u] : p0 + 1;
-                src_at[u] = (long long)p0 * row_dwords + o0;
-                split[u] = crosses ? row_dwords - o0 : 4u;
-                row_b[u] = p1;
-                contiguous[u] = p1 == p0 + 1;
-            }
-        }
-        uint4 v[kBatch];
-#pragma unroll
-        for (int u = 0; u < kBatch; u++) {
-            if (u >= count) continue;
-            if (contiguous[u]) {
-                const Dwords4 w = *(const Dwords4 *)(src + src_at[u]);
-                v[u] = make_uint4(w.x, w.y, w.z, w.w);
-            } else if (row_dwords == 1u) {
-                v[u] = make_uint4(src[(int32_t)rows4[u].x], src[(int32_t)rows4[u].y],
-                                  src[(int32_t)rows4[u].z], src[(int32_t)rows4[u].w]);
-            } else {
-                const long long b = (long long)row_b[u] * row_dwords -
-                    (long long)split[u];
-                uint32_t w[4];
-#pragma unroll
-                for (uint32_t e = 0; e < 4u; e++) {
-                    w[e] = e < split[u] ? src[src_at[u] + e] : src[b + e];
-                }
-                v[u] = make_uint4(w[0], w[1], w[2], w[3]);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < kBatch; u++) {
-            if (u >= count) continue;
-            *(uint4 *)(dst + ((k0 + (long long)u * step) << 2)) = v[u];
-        }
-    };
-
-    long long k = first;
-    for (; k + (long long)(kBatch - 1) * step < chunks; k += (long long)kBatch * step) {
-        move(k, kBatch);
-    }
-    for (; k < chunks; k += step) {
-        move(k, 1);
-    }
-    // the last, partial chunk
-    if (first == 0) {
-        for (long long d = chunks << 2; d < total; d++) {
-            const uint32_t row = row_dwords == 1u ? (uint32_t)d :
-                (uint32_t)__umul64hi((unsigned long long)d, inv_magic);
-            const uint32_t off = (uint32_t)(d - (long long)row * row_dwords);
-            dst[d] = src[(long long)perm[row] * row_dwords + off];
-        }
-    }
-}
-
 struct alignas(16) Word16 { uint32_t v[4]; };
 struct alignas(8) Word8 { uint32_t v[2]; };
 
@@ -787,33 +686,29 @@ __device__ inline int32_t compactNumTiles(int32_t prefix);
 
 // One column (blockIdx.y) of one site: rows move from the buffers the table
 // had when the chain started into its current ones.
-template <bool Wide = true>
 __device__ inline void gatherColumn(EcsState *S, const SortSite &site,
                                     const GatherColumn &gc, TableHdr &tbl,
                                     int32_t row_begin, int32_t row_end,
                                     int32_t tid, int32_t stride,
                                     const int32_t *perm_rows = nullptr,
                                     const uint32_t *sorted_keys = nullptr,
-                                    bool published = true,
                                     void *const *recorded = nullptr);
 
 __device__ inline void patchColumn(EcsState *S, const SortSite &site,
                                    const SortState *state, const GatherColumn &gc,
                                    int32_t tid, int32_t stride);
 
-// Wide: some column of the batch moves in 16-byte destination chunks
-// (MADRONA_MWHIP_GATHER_WIDE=1).  The word-by-word kernel is a stream of
-// (index -> word -> store) chains: what it wants is wavefronts in flight, and
-// without the wide routine it fits EIGHT per SIMD (64 registers) -- measured
-// with the register cap alone, spilling the unused wide path
-// (profiles/r04_sort_variants.jsonl): 15.1 -> 12.3 us at 4096 Escape-Room worlds,
-// 28.4 -> 25.9 at 8192 with physics, 177 -> 159 at 65536.
+// Rows move word by word (gatherWords): a stream of (index -> word -> store)
+// chains, and what that wants is wavefronts in flight -- EIGHT per SIMD (64
+// registers).  Measured with the register cap alone: 15.1 -> 12.3 us at 4096
+// Escape-Room worlds, 28.4 -> 25.9 at 8192 with physics, 177 -> 159 at 65536
+// (profiles/r04_sort_variants.jsonl; there too: moving whole-dword rows in
+// 16-byte chunks of the destination is as slow or slower at every size).
 #ifndef MADRONA_SORT_GATHER_WAVES
 #define MADRONA_SORT_GATHER_WAVES 8
 #endif
-template <bool Wide>
 __global__ void __launch_bounds__(kSortThreads)
-__attribute__((amdgpu_waves_per_eu(Wide ? 0 : MADRONA_SORT_GATHER_WAVES)))
+__attribute__((amdgpu_waves_per_eu(MADRONA_SORT_GATHER_WAVES)))
 sortGather(EcsState *S, const SortSite *sites, const GatherColumn *columns,
            const GatherSlice *slices, const MiscOp *trailing_ops,
            uint32_t num_trailing_ops)
@@ -853,19 +748,19 @@ sortGather(EcsState *S, const SortSite *sites, const GatherColumn *columns,
         // stays inside a few pages of every buffer it touches instead of
         // striding over all of them)
         int32_t per = (n_out + (int32_t)slice.numSlices - 1) / (int32_t)slice.numSlices;
-        per = (per + 3) & ~3;       // (16-byte destination chunks stay aligned)
+        per = (per + 3) & ~3;       // (runs start at a multiple of four rows)
         const int32_t row_begin = (int32_t)slice.slice * per;
         const int32_t row_end = row_begin + per < n_out ? row_begin + per : n_out;
         if (row_begin < row_end) {
-            gatherColumn<Wide>(S, site, gc, tbl, row_begin, row_end,
-                               (int32_t)threadIdx.x, (int32_t)kSortThreads,
-                               nullptr, nullptr, true, recorded);
+            gatherColumn(S, site, gc, tbl, row_begin, row_end,
+                         (int32_t)threadIdx.x, (int32_t)kSortThreads,
+                         nullptr, nullptr, recorded);
         }
     } else {
-        gatherColumn<Wide>(S, site, gc, tbl, 0, n_out,
-                           (int32_t)(slice.slice * kSortThreads + threadIdx.x),
-                           (int32_t)(slice.numSlices * kSortThreads),
-                           nullptr, nullptr, true, recorded);
+        gatherColumn(S, site, gc, tbl, 0, n_out,
+                     (int32_t)(slice.slice * kSortThreads + threadIdx.x),
+                     (int32_t)(slice.numSlices * kSortThreads),
+                     nullptr, nullptr, recorded);
     }
 
     // (the passes are over: their histograms and counters are dead)
@@ -892,23 +787,18 @@ sortGather(EcsState *S, const SortSite *sites, const GatherColumn *columns,
 // Rows [row_begin, row_end) of the sorted table.  tid / stride: this thread's
 // index among, and the number of, the threads working on them.
 // perm_rows: the permutation entries of rows [row_begin, row_end) if the caller
-// has them closer than the index buffer.  Wide = false leaves the 16-byte-chunk
-// routine out (and its registers: the word-by-word kernel then fits eight
-// wavefronts per SIMD).
+// has them closer than the index buffer.
 // sorted_keys: ALL sorted keys if the caller has them closer than the key
-// buffer.  published = false: publishSite has not run yet, rows move from the
-// current buffers into the twins (no caller left since the multi-workgroup
-// small sort was removed in round 5).  recorded: { buffer, twin } of every
-// column when the chain started (SortSite::colPtrs): the header's pointers are
-// being swapped by another workgroup and are not read.
-template <bool Wide>
+// buffer.  recorded: { buffer, twin } of every column when the chain started
+// (SortSite::colPtrs): the header's pointers are being swapped by another
+// workgroup and are not read.
 __device__ inline void gatherColumn(EcsState *S, const SortSite &site,
                                     const GatherColumn &gc, TableHdr &tbl,
                                     int32_t row_begin, int32_t row_end,
                                     int32_t tid, int32_t stride,
                                     const int32_t *perm_rows,
                                     const uint32_t *sorted_keys,
-                                    bool published, void *const *recorded)
+                                    void *const *recorded)
 {
     const bool final_in_b = ((site.numPasses - 1) & 1) != 0;
     const int32_t *perm = perm_rows != nullptr ? perm_rows :
@@ -931,7 +821,7 @@ __device__ inline void gatherColumn(EcsState *S, const SortSite &site,
         src = recorded[2 * col];
         dst = recorded[2 * col + 1];
     } else {
-        const bool pinned = !published || (tbl.columnFlags[col] & kColumnPinned) != 0u;
+        const bool pinned = (tbl.columnFlags[col] & kColumnPinned) != 0u;
         src = pinned ? tbl.columns[col] : tbl.columnsAlt[col];
         dst = pinned ? tbl.columnsAlt[col] : tbl.columns[col];
     }
@@ -962,14 +852,6 @@ __device__ inline void gatherColumn(EcsState *S, const SortSite &site,
 
     const size_t row_bytes = tbl.columnBytes[col];
     char *dst_rows = (char *)dst + (size_t)row_begin * row_bytes;
-    if constexpr (Wide) {
-        if (gc.rowDwords != 0u) {
-            gatherRowsWide((const uint32_t *)src, (uint32_t *)dst_rows, perm, n_rows,
-                           gc.rowDwords, gc.invMagicDwords, tid, stride);
-            return;
-        }
-    }
-
     switch (gc.wordBytes) {
     case 16:
         gatherWords<Word16>((const Word16 *)src, (Word16 *)dst_rows, perm, n_rows,
@@ -2279,8 +2161,7 @@ void buildSortLaunches(const SortBatch &batch, std::vector<KernelLaunch> &out)
 
     {
         KernelLaunch k;
-        k.fn = batch.gatherWide ? (const void *)&sortGather<true> :
-                                  (const void *)&sortGather<false>;
+        k.fn = (const void *)&sortGather;
         // one workgroup per slice of a column (runtime.hip, makeSortBatch: the
         // workgroups are shared out over the columns by the bytes they move)
         k.grid = dim3(std::max(batch.numGatherSlices, 1u), 1, 1);
@@ -2288,7 +2169,7 @@ void buildSortLaunches(const SortBatch &batch, std::vector<KernelLaunch> &out)
         k.setArgs(batch.stateDev, batch.sitesDev, batch.gatherColumnsDev,
                   batch.gatherSlicesDev, (const MiscOp *)nullptr, 0u);
         // (the 16-byte variant names itself: tests check which one ran)
-        k.role = batch.gatherWide ? "sort.gather.wide" : "sort.gather";
+        k.role = "sort.gather";
         k.kind = MWHIP_NODE_SORT_ARCHETYPE;
         k.sortBatch = &batch;
         k.sortRole = SortRole::Gather;

@@ -302,8 +302,8 @@ public:
     // ---- staged rebuild (physics.inl bvhUpdateKernel) -------------------------
     // The top-down build is a long chain of dependent accesses to a few KB:
     // run from HBM it is pure latency.  A kernel copies the leaf boxes next to
-    // the CU, runs rebuildStaged() on a *copy* of this object whose arrays point
-    // at that storage, and copies nodes / leaf parents / orders back.
+    // the CU, runs the build on a *copy* of this object whose arrays point at
+    // that storage, and copies nodes / leaf parents / orders back.
     static constexpr uint32_t nodeBytes = 116;
 
     MADRONA_HD inline bool needsRebuild() const { return force_rebuild_; }
@@ -346,16 +346,10 @@ public:
     };
     static constexpr int32_t rebuildStackSize = 64;
 
-    MADRONA_HD inline int32_t rebuildStaged(RebuildStackEntry *stack)
-    {
-        rebuild(stack);
-        return (int32_t)num_nodes_;
-    }
-
 #if defined(__HIPCC__)
-    // Wave-cooperative flavour of the staged rebuild: all 64 lanes call it on
-    // identical rebased copies (<= 64 leaves); builds the same tree, node for
-    // node, as rebuild().  Needs leaf_centers_.
+    // The staged rebuild on a wavefront: all 64 lanes call it on identical
+    // rebased copies (<= 64 leaves); builds the same tree, node for node, as
+    // rebuild().  Needs leaf_centers_.
     __device__ inline int32_t rebuildStagedWave(uint32_t lane,
                                                 RebuildStackEntry *stack);
 

@@ -328,11 +328,6 @@ hullHullWave(uint32_t lane, const PairSetup &pair,
         HullState b = makeHullStateWave<LPW>(lane, b_mesh, pair.b,
             scratch->hullVerts[1], scratch->hullPlanes[1]);
         wave::phaseFence();
-#ifdef MADRONA_PHYS_EAGER_CENTROID
-        // (round 3, for A/B measurements: both centroids up front)
-        hullCentroid(a);
-        hullCentroid(b);
-#endif
         prof.mark(lane, 0);     // hulls into LDS
         return hullHullWaveSAT<LPW>(lane, pair, a, b, scratch, out, too_big,
                                     prof, sep_face);
@@ -577,9 +572,6 @@ __device__ inline bool faceContactWave(uint32_t lane, const SATResult &sat,
                 !std::is_same_v<HullB, HullState>) {
     return false;
   } else {
-#ifdef MADRONA_PHYS_SEQUENTIAL_MANIFOLD
-    return false;
-#else
     // every polygon of the clipping fits the group: the incident face gains at
     // most one vertex per side plane
     if (n_ref + n_inc > (uint32_t)LPW) {
@@ -602,7 +594,6 @@ __device__ inline bool faceContactWave(uint32_t lane, const SATResult &sat,
                           a_is_ref ? pair.bLoc : pair.aLoc, out);
     }
     return true;
-#endif
   }
 }
 
@@ -637,9 +628,7 @@ __device__ inline bool hullHullWaveSAT(uint32_t lane, const PairSetup &pair,
         return false;
     }
 
-#ifndef MADRONA_PHYS_EAGER_CENTROID
     hullCentroid(a);
-#endif
     EdgeQuery edge_query = queryEdgeDirectionsWave<LPW>(lane, a, b);
     prof.mark(lane, 3);
     if (edge_query.separation > 0.0f) {

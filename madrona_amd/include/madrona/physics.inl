@@ -1438,7 +1438,6 @@ struct BvhRebuildStaging {
             buildStack[broadphase::BVH::rebuildStackSize];
         broadphase::BVH::SegmentedScratch segmented;
     };
-    int32_t numNodes;
 };
 
 // The rebuild of ONE world's tree by its wavefront (the tree asked for it: a
@@ -1478,29 +1477,17 @@ __device__ inline void rebuildTreeStaged(broadphase::BVH &bvh, uint32_t lane,
     broadphase::BVH local = bvh.rebased(staging.nodes,
         staging.leafAABBs, staging.leafParents, staging.sortedLeaves,
         staging.traversalOrder, staging.leafCenters);
-#ifdef MADRONA_PHYS_SERIAL_BVH_REBUILD
-    if (lane == 0) {
-        staging.numNodes = local.rebuildStaged(staging.buildStack);
-    }
-    wave::phaseFence();
-    const int32_t num_nodes = staging.numNodes;
-#else
     // breadth first, every range of a level at once (broadphase.inl); the
     // stack machine only if the tree needs more range records than the scratch
     // holds (not expected: a range is a node, and the reference sizes its node
     // array with the same bound)
-#ifdef MADRONA_PHYS_STACK_REBUILD
-    int32_t num_nodes = -1;     // (measurement builds: rounds 2-4's build)
-#else
     int32_t num_nodes = local.rebuildStagedSegmented(lane, &staging.segmented);
     wave::phaseFence();
-#endif
     // (-1: more range records than maxRebuildRanges = 96.  A record is a node,
     // and a build that stays inside its node array -- the condition under
     // which the reference's own build is defined -- numbers at most 85 of them
     // here, so this branch is unreachable from legal inputs
-    // (tests/test_bvh_edges_cpu.py: 49 at most over the planned cases); it is
-    // what MADRONA_PHYS_STACK_REBUILD builds run.)
+    // (tests/test_bvh_edges_cpu.py: 49 at most over the planned cases).)
     if (num_nodes < 0) {
         for (int32_t i = (int32_t)lane; i < num_leaves; i += 64) {
             staging.sortedLeaves[i] = bvh.rawSortedLeaves()[i];
@@ -1555,7 +1542,6 @@ __device__ inline void rebuildTreeStaged(broadphase::BVH &bvh, uint32_t lane,
             mwhip::raiseError(S, mwhip::kErrPhysics);
         }
     }
-#endif
 
     waveCopyDwords(lane, 64u, (uint32_t *)bvh.rawNodes(),
         (const uint32_t *)staging.nodes,
@@ -1757,6 +1743,8 @@ bvhUpdateKernel(EcsState *S, void *, uint32_t, uint32_t)
     }
 }
 
+// what the two kernels below share on the device (treeq): the checked group head
+#include <madrona/phys_impl/tree_query.inl>
 // the ray queries' kernel (mwhip_rays_*): rayQueryKernel
 #include <madrona/phys_impl/ray_query.inl>
 // the box queries' kernel (mwhip_boxes_*): boxQueryKernel

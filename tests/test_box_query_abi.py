@@ -80,6 +80,9 @@ def test_header_says_what_a_box_sees():
                             "box_query.inl")).read()
     assert "boxQueryKernel" in inl and "checkEntityAABBsOverlap<maxBoxes>" in inl
     phys = open(os.path.join(REPO_ROOT, "madrona_amd", "include", "madrona", "physics.inl")).read()
+    assert phys.index("#include <madrona/phys_impl/tree_query.inl>") < \
+        phys.index("#include <madrona/phys_impl/ray_query.inl>") < \
+        phys.index("#include <madrona/phys_impl/box_query.inl>")
     assert "#include <madrona/phys_impl/box_query.inl>" in phys
     assert "mwhip_set_box_kernel(builder.exec()" in phys
 

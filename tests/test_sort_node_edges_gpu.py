@@ -61,7 +61,6 @@ class Case:
     small: str = "1"                # MADRONA_MWHIP_SORT_SMALL
     compact: str = "1"              # MADRONA_MWHIP_SORT_COMPACT
     grid: str = ""                  # MADRONA_MWHIP_SORT_MAX_GRID (unset: "")
-    wide: str = "0"                 # MADRONA_MWHIP_GATHER_WIDE
     carry: str = "1"                # MADRONA_MWHIP_SORT_CARRIES_MISC
     pinned: bool = False
     regrow: str = "churn"           # second phase: churn (+-6) | fill (40) | drain (0)
@@ -76,8 +75,6 @@ class Case:
         parts.append(f"compact{self.compact}")
         if self.grid:
             parts.append(f"grid{self.grid}")
-        if self.wide != "0":
-            parts.append("wide")
         if self.carry != "1":
             parts.append("nocarry")
         if self.pinned:
@@ -132,12 +129,10 @@ def _cases():
         for grid in ("", "1", "3"):
             cs.append(Case(2000, 40000, destroy="some", compact=compact, grid=grid,
                            mode="two" if grid else "random"))
-    for wide in ("0", "1"):
-        for compact in ("0", "2"):
-            cs.append(Case(1500, 30000, destroy="some", compact=compact, wide=wide,
-                           pinned=True))
-    cs.append(Case(1500, 30000, destroy="some", wide="1", grid="3", mode="low_byte"))
-    cs.append(Case(80, 2500, destroy="some", wide="1"))
+    for compact in ("0", "2"):
+        cs.append(Case(1500, 30000, destroy="some", compact=compact, pinned=True))
+    cs.append(Case(1500, 30000, destroy="some", grid="3", mode="low_byte"))
+    cs.append(Case(80, 2500, destroy="some"))
     for carry in ("0", "1"):
         cs.append(Case(1000, 20000, destroy="some", carry=carry))
         cs.append(Case(1000, 20000, destroy="some", carry=carry, compact="2"))
@@ -246,8 +241,7 @@ def _check_path(case: Case, stats, world_sort: bool, rows: int, build_rows=None)
     if case.small != "0" and build_rows <= SMALL_BUILD_ROWS:
         assert names == ["sort.small"] + misc, (world_sort, roles)
         return "small"
-    gather = "sort.gather.wide" if case.wide == "1" else "sort.gather"
-    tail = [gather] + (["sort.finalize"] if case.pinned else []) + misc
+    tail = ["sort.gather"] + (["sort.finalize"] if case.pinned else []) + misc
     tiles = -(-rows // SORT_TILE)
     if world_sort and case.compact == "2":
         assert names == ["sort.compact.prepare", "sort.compact.scatter"] + tail, roles
@@ -310,7 +304,6 @@ def _check_probe(s: Simulator, case: Case, table: Table, what):
 def test_sort_node_edges(built, monkeypatch, case):
     monkeypatch.setenv("MADRONA_MWHIP_SORT_SMALL", case.small)
     monkeypatch.setenv("MADRONA_MWHIP_SORT_COMPACT", case.compact)
-    monkeypatch.setenv("MADRONA_MWHIP_GATHER_WIDE", case.wide)
     monkeypatch.setenv("MADRONA_MWHIP_SORT_CARRIES_MISC", case.carry)
     if case.grid:
         monkeypatch.setenv("MADRONA_MWHIP_SORT_MAX_GRID", case.grid)

@@ -32,7 +32,6 @@ class Stress:
     def __init__(self, monkeypatch, counts, pinned=False, grid="", stay=""):
         monkeypatch.setenv("MADRONA_MWHIP_SORT_SMALL", "0")
         monkeypatch.setenv("MADRONA_MWHIP_SORT_COMPACT", "2")
-        monkeypatch.setenv("MADRONA_MWHIP_GATHER_WIDE", "0")
         monkeypatch.setenv("MADRONA_MWHIP_SORT_CARRIES_MISC", "1")
         for name, value in (("MADRONA_MWHIP_SORT_MAX_GRID", grid),
                             ("MADRONA_MWHIP_SORT_STAY", stay)):

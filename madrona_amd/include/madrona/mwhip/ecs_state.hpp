@@ -71,7 +71,16 @@ enum ColumnFlags : uint32_t {
 //   kErrRender          a world has more than 1024 instances / the instance
 //                       table was unsorted / a traversal stack overflowed: the
 //                       rgb / depth outputs of that world's views are stale or
-//                       partial.
+//                       partial.  The stack: a ray has 24 entries for the
+//                       top-level and the bottom-level walk together; it holds
+//                       the far child of every node both of whose children are
+//                       internal nodes the ray enters.  Morton codes come from
+//                       the low bits of the coordinates' patterns, so the
+//                       top-level depth does not depend on the scene's extent:
+//                       16 such levels on one path render (plus 5 of a
+//                       168-triangle mesh), 26 raise this flag and write
+//                       nothing past the stack (sims/raycast_probe kind 8,
+//                       tests/test_raycast_probe_gpu.py).
 //   kErrSnapshot        a queued mwhip_snapshot_restore_async found that the
 //                       save queued before it had overflowed (a table grew
 //                       past the snapshot's room while both were in flight):

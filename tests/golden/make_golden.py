@@ -54,8 +54,23 @@ def actions_for(sim, step, num_worlds):
                           agents=AGENTS[sim])
 
 
+def raycast_probe_records():
+    """sims/raycast_probe, sixteen worlds (one of each scene kind) after one
+    step: the instance, view and light records and the Morton codes the
+    reference CPU backend produced, per world in a canonical order
+    (tests/raycast_probe_utils.py).  The GPU tests require the HIP backend's
+    tables to hold exactly these rows and render them."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import raycast_probe_utils as U
+    records, _ = U.ref_records(U.KINDS, 0)
+    np.savez_compressed(U.GOLDEN, **records)
+    print(f"wrote {U.GOLDEN} ({os.path.getsize(U.GOLDEN) / 1024:.1f} KiB)")
+
+
 def main():
     only = sys.argv[1:]
+    if not only or "raycast_probe_records" in only:
+        raycast_probe_records()
     for name, (sim, worlds, seed, flags, checkpoints) in CASES.items():
         if only and name not in only:
             continue

@@ -1,15 +1,9 @@
 #include "escape_room_phys/sim.hpp"
 
-#include <madrona/physics_loader.hpp>
-#include <madrona/physics_assets.hpp>
-#include <madrona/importer.hpp>
-#include <madrona/stack_alloc.hpp>
-
-struct SimTraits;
-#include "common/sim_c_api.h"
+#include "common/rigid_body_set.hpp"
 #ifdef ESCPHYS_RENDER
 #include "common/mesh_set.hpp"
-#include "common/cpu_render_bridge.hpp"
+#include "common/render_mgr.hpp"
 #ifndef SIM_BACKEND_REF_CPU
 #include "common/render_config.hpp"
 #endif
@@ -17,8 +11,6 @@ struct SimTraits;
 
 #include <vector>
 #include <string>
-#include <memory>
-#include <array>
 
 namespace {
 
@@ -26,108 +18,21 @@ using namespace madrona;
 using namespace madrona::phys;
 using escphys::SimObject;
 
-// A unit cube hull (quads, outward CCW) stands in for every mesh asset of the
-// real Escape Room (no file importers here): instances scale it per body.
-struct CubeMesh {
-    math::Vector3 positions[8] = {
-        { -0.5f, -0.5f, -0.5f }, { 0.5f, -0.5f, -0.5f },
-        { 0.5f, 0.5f, -0.5f }, { -0.5f, 0.5f, -0.5f },
-        { -0.5f, -0.5f, 0.5f }, { 0.5f, -0.5f, 0.5f },
-        { 0.5f, 0.5f, 0.5f }, { -0.5f, 0.5f, 0.5f },
-    };
-    uint32_t indices[24] = {
-        0, 3, 2, 1,     // -z
-        4, 5, 6, 7,     // +z
-        0, 1, 5, 4,     // -y
-        2, 3, 7, 6,     // +y
-        0, 4, 7, 3,     // -x
-        1, 2, 6, 5,     // +x
-    };
-    uint32_t faceCounts[6] = { 4, 4, 4, 4, 4, 4 };
-};
-
-// Loaders stay alive for the life of the process: worlds keep pointing at the
-// ObjectManager they own.
-std::vector<std::unique_ptr<PhysicsLoader>> &loaders()
-{
-    static std::vector<std::unique_ptr<PhysicsLoader>> list;
-    return list;
-}
-
+// A unit cube hull stands in for every mesh asset of the real Escape Room (no
+// file importers here): instances scale it per body.
 ObjectManager *loadPhysicsObjects(const SimCreateArgs &args)
 {
-#ifdef SIM_BACKEND_REF_CPU
-    (void)args;
-    auto loader = std::make_unique<PhysicsLoader>(ExecMode::CPU, 10);
-#else
-    auto loader = std::make_unique<PhysicsLoader>(ExecMode::CUDA, 10,
-                                                  args.gpu_id);
-#endif
+    simmgr::RigidBodySet set((size_t)SimObject::NumObjects);
+    const uint32_t cube = set.addHull(simmgr::HullSource::box(-0.5f, 0.5f));
 
-    CubeMesh cube;
-    imp::SourceMesh hull_mesh {};
-    hull_mesh.positions = cube.positions;
-    hull_mesh.indices = cube.indices;
-    hull_mesh.faceCounts = cube.faceCounts;
-    hull_mesh.numVertices = 8;
-    hull_mesh.numFaces = 6;
+    set.hull(SimObject::Cube, cube, 0.075f, { 0.5f, 0.75f });
+    set.hull(SimObject::Wall, cube, 0.f, { 0.5f, 0.5f });
+    set.hull(SimObject::Door, cube, 0.f, { 0.5f, 0.5f });
+    set.hull(SimObject::Agent, cube, 1.f, { 0.5f, 0.5f });
+    set.hull(SimObject::Button, cube, 1.f, { 0.5f, 0.5f });
+    set.plane(SimObject::Plane);
 
-    std::array<SourceCollisionPrimitive, (size_t)SimObject::NumObjects> prims {};
-    std::array<SourceCollisionObject, (size_t)SimObject::NumObjects> objs {};
-
-    auto setup_hull = [&](SimObject obj, float inv_mass,
-                          RigidBodyFrictionData friction) {
-        SourceCollisionPrimitive &prim = prims[(size_t)obj];
-        prim.type = CollisionPrimitive::Type::Hull;
-        prim.hullInput.hullIDX = 0;
-
-        objs[(size_t)obj] = SourceCollisionObject {
-            Span<const SourceCollisionPrimitive>(&prim, 1),
-            inv_mass,
-            friction,
-        };
-    };
-
-    setup_hull(SimObject::Cube, 0.075f, { 0.5f, 0.75f });
-    setup_hull(SimObject::Wall, 0.f, { 0.5f, 0.5f });
-    setup_hull(SimObject::Door, 0.f, { 0.5f, 0.5f });
-    setup_hull(SimObject::Agent, 1.f, { 0.5f, 0.5f });
-    setup_hull(SimObject::Button, 1.f, { 0.5f, 0.5f });
-
-    {
-        SourceCollisionPrimitive &prim = prims[(size_t)SimObject::Plane];
-        prim.type = CollisionPrimitive::Type::Plane;
-        objs[(size_t)SimObject::Plane] = SourceCollisionObject {
-            Span<const SourceCollisionPrimitive>(&prim, 1),
-            0.f,
-            { 0.5f, 0.5f },
-        };
-    }
-
-    StackAlloc tmp_alloc;
-    RigidBodyAssets rigid_body_assets;
-    CountT num_rigid_body_data_bytes;
-    void *rigid_body_data = RigidBodyAssets::processRigidBodyAssets(
-        Span<const imp::SourceMesh>(&hull_mesh, 1),
-        Span<const SourceCollisionObject>(objs.data(), (CountT)objs.size()),
-        false, tmp_alloc, &rigid_body_assets, &num_rigid_body_data_bytes);
-
-    if (rigid_body_data == nullptr) {
-        FATAL("Invalid collision hull input");
-    }
-
-    // agents turn about z only: infinite inertia about x and y
-    rigid_body_assets.metadatas[(size_t)SimObject::Agent]
-        .mass.invInertiaTensor.x = 0.f;
-    rigid_body_assets.metadatas[(size_t)SimObject::Agent]
-        .mass.invInertiaTensor.y = 0.f;
-
-    loader->loadRigidBodies(rigid_body_assets);
-    free(rigid_body_data);
-
-    ObjectManager *mgr = &loader->getObjectManager();
-    loaders().push_back(std::move(loader));
-    return mgr;
+    return set.load(args, 10, simmgr::turnAboutZOnly(SimObject::Agent));
 }
 
 #ifdef ESCPHYS_RENDER
@@ -164,12 +69,9 @@ const simmesh::MeshSet &meshes()
     return set;
 }
 
-uint32_t g_resolution = 0;
-#ifdef SIM_BACKEND_REF_CPU
 // floor + 4 borders + 2 agents + 3 rooms x 9 = 34 instances, 2 views per world
 constexpr uint32_t kMaxRecordsPerWorld = 64;
-simmgr::CpuRenderBridge *g_bridge = nullptr;
-#endif
+simmgr::RenderMgr g_render;
 #endif
 
 }
@@ -189,48 +91,35 @@ struct SimTraits {
     // backend's, whose CPU mode has no ray caster either)
     static Sim::Config makeConfig(const SimCreateArgs &args)
     {
-#if defined(ESCPHYS_RENDER) && defined(SIM_BACKEND_REF_CPU)
-        delete g_bridge;
-        g_bridge = new simmgr::CpuRenderBridge(
-            args.num_worlds, kMaxRecordsPerWorld, 64,
-            escphys::consts::numAgents, kMaxRecordsPerWorld);
+#ifdef ESCPHYS_RENDER
+        g_render = simmgr::RenderMgr(args, kMaxRecordsPerWorld,
+                                     escphys::consts::numAgents,
+                                     kMaxRecordsPerWorld);
 #endif
         return Sim::Config {
             args.seed, args.world_base, args.flags & 0xFFFFu,
             loadPhysicsObjects(args),
 #ifdef ESCPHYS_RENDER
             (args.flags >> 25) & 1u,
-#ifdef SIM_BACKEND_REF_CPU
-            &g_bridge->bridge,
-#else
-            nullptr,
-#endif
+            g_render.bridge(),
 #endif
         };
     }
 
-#if defined(ESCPHYS_RENDER) && defined(SIM_BACKEND_REF_CPU)
-    static void preStep() { g_bridge->beginStep(); }
-#endif
-
 #ifdef ESCPHYS_RENDER
+    static void preStep() { g_render.beginStep(); }
+
     static const simmesh::MeshSet &renderMeshes() { return meshes(); }
 
 #ifndef SIM_BACKEND_REF_CPU
     static madrona::Optional<madrona::CudaBatchRenderConfig> renderConfig(
         const SimCreateArgs &args)
     {
-        madrona::CudaBatchRenderConfig cfg {};
-        cfg.renderMode = (args.flags >> 24) & 1u ?
-            madrona::CudaBatchRenderConfig::RenderMode::Depth :
-            madrona::CudaBatchRenderConfig::RenderMode::RGBD;
         if (((args.flags >> 26) & 1u) != 0u) {
-            g_resolution = 0;
             return madrona::Optional<madrona::CudaBatchRenderConfig>::none();
         }
-        cfg.renderResolution = (args.flags >> 16) & 0xFFu;
-        if (cfg.renderResolution == 0) cfg.renderResolution = 64;
-        g_resolution = cfg.renderResolution;
+        madrona::CudaBatchRenderConfig cfg {};
+        g_render.readRenderFlags(cfg, args.flags, 24, 16, 64);
         cfg.maxViewsPerWorld = escphys::consts::numAgents;
         simmgr::meshesToRenderConfig(meshes(), cfg);
         return madrona::Optional<madrona::CudaBatchRenderConfig>::make(cfg);
@@ -272,12 +161,9 @@ void SimTraits::describeTensors(T &out, uint32_t num_worlds)
                     (uint32_t)ExportID::Lidar });
     out.push_back({ "steps_remaining", SIM_I32, { W, A, 1 },
                     (uint32_t)ExportID::StepsRemaining });
-#if defined(ESCPHYS_RENDER) && !defined(SIM_BACKEND_REF_CPU)
-    const int64_t R = g_resolution;
-    if (R != 0) {
-        out.push_back({ "rgb", SIM_U8, { W * A, R, R, 4 }, (uint32_t)ExportID::RGB });
-        out.push_back({ "depth", SIM_F32, { W * A, R, R }, (uint32_t)ExportID::Depth });
-    }
+#ifdef ESCPHYS_RENDER
+    g_render.describeTensors(out, W * A, (uint32_t)ExportID::RGB,
+                             (uint32_t)ExportID::Depth);
 #endif
 }
 
@@ -341,20 +227,5 @@ void SimTraits::describeColumns(T &cols)
 }
 
 #ifdef ESCPHYS_RENDER
-// CPU mode: the instance (kind 0, 64 B) / view (kind 1, 48 B) records the
-// reference appended to its bridge during the last step, arrival order, + the
-// (world << 32 | entity id) key of each.  Returns the count (-1 on HIP: there
-// the render entities' rows are the records).
-extern "C" SIM_API int64_t render_prep_bridge_records(int32_t kind, void *dst,
-                                                      uint64_t *keys_dst,
-                                                      uint64_t max_records)
-{
-#ifdef SIM_BACKEND_REF_CPU
-    if (g_bridge == nullptr) return -1;
-    return g_bridge->records(kind, dst, keys_dst, max_records);
-#else
-    (void)kind; (void)dst; (void)keys_dst; (void)max_records;
-    return -1;
-#endif
-}
+SIM_RENDER_BRIDGE_RECORDS(g_render)
 #endif

@@ -30,6 +30,11 @@ CASES = {
     "hideseek_w8": ("hideseek", 8, 5, 40, [1, 5, 25, 110]),
     # sphere primitives (GJK sphere-hull), random kicks, no actions
     "ball_pit_w8": ("ball_pit", 8, 5, 50, [1, 10, 40, 120]),
+    # the other rigid-body loaders (8 worlds: contact_probe's four scene kinds go
+    # by world index, broadphase_only's worlds differ)
+    "tgs_drop_w8": ("tgs_drop", 8, 5, 0, [1, 10, 40]),
+    "broadphase_only_w8": ("broadphase_only", 8, 5, 0, [1, 10, 40]),
+    "contact_probe_w8": ("contact_probe", 8, 5, 0, [1, 10, 40]),
 }
 
 AGENTS = {"escape_room": 2, "escape_room_phys": 2, "hideseek": 5}

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded() and mwhip_digest_*() / mwhip_set_step_digest() (a per-world hash of chosen columns computed on the device) and mwhip_view_*() / mwhip_set_step_view() (padded per-world tensors of a table's columns) and mwhip_write_*() / mwhip_set_step_write() (padded per-world tensors scattered into a table's columns) and mwhip_reduce_term / mwhip_reduce_*() / mwhip_set_step_reduce() (per-world sums, extrema, counts and alarms of a table's columns) and mwhip_gather_source / mwhip_gather_*() / mwhip_set_step_gather() (the cells of the entities a run of handles in device memory names) and mwhip_scatter_*() / mwhip_set_step_scatter() (cells written into the entities such a run of handles names, the highest index winning among duplicates) and mwhip_rays_desc / mwhip_ray_args / mwhip_set_ray_kernel() / mwhip_rays_*() / mwhip_set_step_rays() (tensors of rays cast through the worlds' broadphase BVHs by a kernel the simulator's code object registers) and mwhip_boxes_desc / mwhip_box_args / mwhip_set_box_kernel() / mwhip_boxes_*() / mwhip_set_step_boxes() (tensors of boxes tested through the same BVHs, the whole list of each box's entities, by a second kernel the simulator's code object registers) and mwhip_contacts_desc / mwhip_contact_args / mwhip_set_contact_kernel() / mwhip_contacts_*() / mwhip_set_step_contacts() (per-world tensors of the touching primitive pairs and their manifolds, the step's narrowphase run from outside by a third kernel the simulator's code object registers) and MWHIP_NODE_CARRIED / mwhip_broadphase_carry_stats() (launches a steady replay leaves out, a bit of mwhip_node_desc::kind that earlier libraries never set); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
+#define MWHIP_ABI_VERSION 9u   /* 9: mwhip_snapshot_*() (all world state saved and restored on the device) and, added under 9 without a bump (no struct a simulator library is compiled against changed), mwhip_set_output_ring() / mwhip_output_ring_recorded() and mwhip_digest_*() / mwhip_set_step_digest() (a per-world hash of chosen columns computed on the device) and mwhip_view_*() / mwhip_set_step_view() (padded per-world tensors of a table's columns) and mwhip_write_*() / mwhip_set_step_write() (padded per-world tensors scattered into a table's columns) and mwhip_reduce_term / mwhip_reduce_*() / mwhip_set_step_reduce() (per-world sums, extrema, counts and alarms of a table's columns) and mwhip_gather_source / mwhip_gather_*() / mwhip_set_step_gather() (the cells of the entities a run of handles in device memory names) and mwhip_scatter_*() / mwhip_set_step_scatter() (cells written into the entities such a run of handles names, the highest index winning among duplicates) and mwhip_rays_desc / mwhip_ray_args / mwhip_set_ray_kernel() / mwhip_rays_*() / mwhip_set_step_rays() (tensors of rays cast through the worlds' broadphase BVHs by a kernel the simulator's code object registers) and mwhip_boxes_desc / mwhip_box_args / mwhip_set_box_kernel() / mwhip_boxes_*() / mwhip_set_step_boxes() (tensors of boxes tested through the same BVHs, the whole list of each box's entities, by a second kernel the simulator's code object registers) and mwhip_contacts_desc / mwhip_contact_args / mwhip_set_contact_kernel() / mwhip_contacts_*() / mwhip_set_step_contacts() (per-world tensors of the touching primitive pairs and their manifolds, the step's narrowphase run from outside by a third kernel the simulator's code object registers) and mwhip_shapes_desc / mwhip_shape_args / mwhip_set_shape_kernel() / mwhip_shapes_*() / mwhip_set_step_shapes() (tensors of posed collision shapes tested against the worlds' bodies, the same narrowphase by a fourth kernel the simulator's code object registers) and MWHIP_NODE_CARRIED / mwhip_broadphase_carry_stats() (launches a steady replay leaves out, a bit of mwhip_node_desc::kind that earlier libraries never set); 8: mwhip_persist_bytes_used() (the persistent region's bump offset); 7: mwhip_node_desc::pfor_group_kernel (a node's body is only called from the group kernel of the code object that defines it); 6: mwhip_node_desc::write_mask (same-dependency nodes whose signatures clash keep their own launches); 5: mwhip_node_desc::pfor_body, mwhip_pfor_body(), mwhip_set_pfor_group_kernel() (side-by-side ParallelFor nodes in one launch); 4: io_declared */
 
 typedef struct mwhip_exec mwhip_exec; /* opaque; == MWCudaExecutor::Impl */
 
@@ -1604,6 +1604,163 @@ int mwhip_contacts_compute_async(mwhip_exec *exec, uint64_t contacts);
 void *mwhip_contacts_buffer(mwhip_exec *exec, uint64_t contacts, uint32_t which,
                             uint64_t *bytes_out);
 int mwhip_set_step_contacts(mwhip_exec *exec, uint64_t contacts, int on);
+
+/* Shape queries (added under ABI 9): S = F x G posed collision shapes, F bundles
+ * of G shapes that share a world, each tested against the rigid bodies of its
+ * world with the narrowphase of the physics step -- "if this object stood THERE,
+ * what would it touch, where, and how deep?" (DESIGN.md §39;
+ * madrona_amd/shape_ref.py is the same definition in numpy with the narrowphase
+ * injected).  Shape s = f * G + g is shape g of bundle f.
+ * INPUTS.  world[f] int32 per bundle, count[w] int32 per WORLD (only with
+ * bundles_per_world > 0: world = f / bundles_per_world, and bundle f with
+ * f % bundles_per_world >= count[world] is SKIPPED) and exclude[s], one Entity
+ * { uint32 gen; int32 id } per shape, are each a buffer the query owns (world,
+ * exclude) or a SOURCE of the caller's, a mwhip_ray_source with a ray query's
+ * rules; count is a source or nothing.  A body whose Entity column equals
+ * exclude[s], gen and id both, is not tested against shape s; Entity::none()
+ * excludes nothing.  Always owned: object[s] int32 (an object of the
+ * ObjectManager, < desc.num_objects -- the manager keeps no count on the
+ * device, so num_objects >= 1 is the caller's statement of how many it holds),
+ * position[s] 3 floats, rotation[s] 4 floats (w, x, y, z), scale[s] 3 floats.
+ * At creation object is 0, position 0, rotation (1, 0, 0, 0), scale 1, exclude
+ * none, world 0.
+ * WHAT IS TESTED.  The bodies of the shape's world are the rows of the
+ * rigid-body archetypes in the step's iteration order, k = 0 .. n - 1, at their
+ * CURRENT Position, Rotation and Scale.  Every body that is not excluded, Static
+ * ones included, and of it every primitive pair c = shapePrim * body_num_prims +
+ * bodyPrim.  The shape is argument `a` of the step's pair setup, which then
+ * orders the two by primitive type.  The pair is a hit iff the world boxes of
+ * the two primitives intersect (the step's own test) and the narrowphase returns
+ * a manifold of at least one point.  ORDER: ascending (k, c).  No BVH is walked:
+ * the result is a function of the tables and the inputs alone.
+ * OUTPUTS, owned, 256-byte aligned, every one rewritten in full by every compute
+ * (K = max_hits):
+ *   status[s]        int32: MWHIP_SHAPES_OK 0, _SKIPPED -1, _BAD_WORLD -2 (world
+ *                    outside [0, W)), _BAD_SHAPE -3 (a non-finite component of
+ *                    position, rotation or scale, or an object outside [0,
+ *                    num_objects)), _UNSORTED -4 (a rigid-body table waits for
+ *                    its world sort), _UNSUPPORTED -5 (a primitive pair no path
+ *                    supports).  Checked in the order world, count, then per
+ *                    shape; nothing behind a failed check is read.  No sticky
+ *                    error flag is raised.
+ *   count[s]         int32: hits, NOT capped by K; 0 unless OK.
+ *   hits[s][k]       Entity of the body touched; Entity::none() behind
+ *                    min(count, K): a valid mwhip_gather_source of S x K handles,
+ *                    record_bytes 8.
+ *   shape_is_ref[s][k] int32: 1 where the contact's reference side
+ *                    (ContactConstraint::ref) is the shape, else 0.  The normal
+ *                    points away from the reference side: out of the shape where
+ *                    1, out of the body (towards the shape) where 0 -- a
+ *                    reference face's or the plane's outward normal, away from
+ *                    `a` for an edge contact, from the hull to the sphere.  The
+ *                    one exception is a sphere-sphere pair, whose normal points
+ *                    from `a` to the reference `b`.
+ *   num_points[s][k] int32, 1 .. 4
+ *   normal[s][k][3]  float32
+ *   points[s][k][4][4]  float32: xyz world position, w penetration depth; point
+ *                    slots >= num_points are zero.
+ *                    All four zero behind min(count, K).
+ * THE KERNEL lives in the simulator's code object (phys_impl/shape_query.inl):
+ * PhysicsSystem::setupPhysicsStepTasks hands its host stub over with
+ * mwhip_set_shape_kernel (NULL is ignored) together with the bytes of HBM
+ * scratch a wavefront needs for the generic single-lane routine (0 with a
+ * kernel: -2).  The executor
+ * owns ONE block of that many bytes per wavefront of the largest grid, made by
+ * the first create and shared by all shape queries (computes are
+ * stream-ordered).  Its single argument is a mwhip_shape_args by value.  A
+ * wavefront per bundle.  Two mappings that leave the same words: cooperative
+ * (the default) and MWHIP_SHAPES_PLAIN (every pair whose boxes intersect
+ * through the generic single-lane routine, the definition itself).
+ * mwhip_set_step_shapes(on != 0): every replay of every STEP graph recomputes
+ * the query directly behind the step contact queries and in front of the step
+ * gathers (which may read `hits`).  Up to MWHIP_MAX_STEP_SHAPES, ONE launch for
+ * all, listed by mwhip_profile as "shapes" with role "shapes"; none when none is
+ * set.  Destroying a step query unsets it.  Shape queries are derived state:
+ * snapshots do not save them.
+ * Errors (non-zero, text in mwhip_last_error(), nothing changed or allocated):
+ * -3 for an unknown handle or one of another executor; -2 for no registered
+ * kernel, num_bundles, shapes_per_bundle, max_hits or num_objects of 0, S x K >
+ * 2^31 - 1, an unknown flag, a bad source (as for rays), a count source without
+ * bundles_per_world, a fifth step query; -10 for buffers that cannot be
+ * allocated.
+ * (No reference counterpart.) */
+#define MWHIP_MAX_STEP_SHAPES 4
+#define MWHIP_SHAPES_OK 0
+#define MWHIP_SHAPES_SKIPPED (-1)
+#define MWHIP_SHAPES_BAD_WORLD (-2)
+#define MWHIP_SHAPES_BAD_SHAPE (-3)
+#define MWHIP_SHAPES_UNSORTED (-4)
+#define MWHIP_SHAPES_UNSUPPORTED (-5)
+#define MWHIP_SHAPES_PLAIN 1u               /* mwhip_shapes_desc::flags */
+#define MWHIP_SHAPES_BUF_WORLD 0u
+#define MWHIP_SHAPES_BUF_EXCLUDE 1u
+#define MWHIP_SHAPES_BUF_OBJECT 2u
+#define MWHIP_SHAPES_BUF_POSITION 3u
+#define MWHIP_SHAPES_BUF_ROTATION 4u
+#define MWHIP_SHAPES_BUF_SCALE 5u
+#define MWHIP_SHAPES_BUF_STATUS 6u
+#define MWHIP_SHAPES_BUF_COUNT 7u
+#define MWHIP_SHAPES_BUF_HITS 8u
+#define MWHIP_SHAPES_BUF_SHAPE_IS_REF 9u
+#define MWHIP_SHAPES_BUF_NUM_POINTS 10u
+#define MWHIP_SHAPES_BUF_NORMAL 11u
+#define MWHIP_SHAPES_BUF_POINTS 12u
+#define MWHIP_SHAPES_NUM_BUFS 13u
+typedef struct mwhip_shapes_desc {
+    uint32_t num_bundles;           /* F >= 1 */
+    uint32_t shapes_per_bundle;     /* G >= 1 */
+    uint32_t max_hits;              /* K >= 1 */
+    uint32_t num_objects;           /* >= 1: the objects the ObjectManager holds */
+    uint32_t bundles_per_world;     /* > 0: world = f / bundles_per_world */
+    uint32_t flags;                 /* MWHIP_SHAPES_PLAIN */
+    mwhip_ray_source world;         /* src == NULL: the owned buffer (or the rule) */
+    mwhip_ray_source count;         /* src == NULL: every bundle */
+    mwhip_ray_source exclude;       /* src == NULL: the owned buffer */
+} mwhip_shapes_desc;
+/* what the kernel reads of one query (device-resident, filled by the runtime;
+ * first_byte is already added to the sources) */
+typedef struct mwhip_shape_plan {
+    void *state;                    /* the executor's ecs state on the device */
+    const char *world_src;          /* unused with bundles_per_world > 0 */
+    const char *count_src;          /* NULL: every bundle */
+    const char *exclude_src;
+    const int32_t *object;          /* [S] */
+    const float *position;          /* [S][3] */
+    const float *rotation;          /* [S][4] */
+    const float *scale;             /* [S][3] */
+    int32_t *status;                /* [S] */
+    int32_t *count;                 /* [S] */
+    uint32_t *hits;                 /* [S][K][2] */
+    int32_t *shape_is_ref;          /* [S][K] */
+    int32_t *num_points;            /* [S][K] */
+    float *normal;                  /* [S][K][3] */
+    float *points;                  /* [S][K][4][4] */
+    char *scratch;                  /* scratch_waves x scratch_stride bytes */
+    uint32_t world_stride, count_stride, exclude_stride;   /* bytes */
+    uint32_t num_bundles, shapes_per_bundle, max_hits, num_objects, bundles_per_world, flags;
+    uint32_t scratch_stride;        /* bytes per wavefront */
+    uint32_t scratch_waves;         /* wavefronts the block serves */
+    uint32_t pad_;
+} mwhip_shape_plan;
+/* the kernel's argument, by value: wavefronts stride over the bundles of all
+ * plans, plan after plan; items[p] == plan p's bundles */
+typedef struct mwhip_shape_args {
+    uint32_t num_plans;
+    uint32_t pad_;
+    uint32_t items[MWHIP_MAX_STEP_SHAPES];
+    const mwhip_shape_plan *plans[MWHIP_MAX_STEP_SHAPES];
+} mwhip_shape_args;
+/* the simulator's shape kernel: __global__ void(mwhip_shape_args), 256 threads */
+int mwhip_set_shape_kernel(mwhip_exec *exec, const void *kernel,
+                           uint32_t scratch_bytes_per_wavefront);
+int mwhip_shapes_create(mwhip_exec *exec, const mwhip_shapes_desc *desc, uint64_t *shapes_out);
+void mwhip_shapes_destroy(mwhip_exec *exec, uint64_t shapes);
+/* waits for the executor's stream */
+int mwhip_shapes_compute(mwhip_exec *exec, uint64_t shapes);
+/* queued on the executor's stream behind the replays queued so far */
+int mwhip_shapes_compute_async(mwhip_exec *exec, uint64_t shapes);
+void *mwhip_shapes_buffer(mwhip_exec *exec, uint64_t shapes, uint32_t which, uint64_t *bytes_out);
+int mwhip_set_step_shapes(mwhip_exec *exec, uint64_t shapes, int on);
 
 #ifdef __cplusplus
 }

@@ -283,6 +283,7 @@ struct mwhip_scatter_rec;       // (entity_scatter.hip)
 struct mwhip_rays_rec;          // (ray_query.hip)
 struct mwhip_boxes_rec;         // (box_query.hip)
 struct mwhip_contacts_rec;      // (contact_query.hip)
+struct mwhip_shapes_rec;        // (shape_query.hip)
 
 // What a replay carries besides its task graphs.  Every launch graph is built
 // from it (the input rings, the step writes and the step scatters open a step graph, the rest are tail stages:
@@ -334,6 +335,9 @@ struct ReplayExtras {
     // mwhip_set_step_contacts: those every step replay recomputes, in one
     // launch directly behind the step box queries
     std::vector<uint64_t> stepContacts;
+    // mwhip_set_step_shapes: those every step replay recomputes, in one launch
+    // directly behind the step contact queries
+    std::vector<uint64_t> stepShapes;
 };
 
 struct mwhip_exec {
@@ -437,6 +441,13 @@ struct mwhip_exec {
     // (MWHIP_CONTACT_CAP_*)
     const void *contactKernel = nullptr;
     uint32_t contactCaps = 0;
+    // mwhip_set_shape_kernel: the simulator's shapeQueryKernel, likewise, the
+    // bytes of scratch a wavefront of it needs (a multiple of 256) and the block
+    // the first mwhip_shapes_create makes of them (in `allocations`)
+    const void *shapeKernel = nullptr;
+    uint32_t shapeScratchBytes = 0;
+    char *shapeScratch = nullptr;
+    uint32_t shapeScratchWaves = 0;
     void *pforBodyScratch = nullptr;        // 8 bytes: where report mode writes
     // MADRONA_MWHIP_EXEC_CONFIG_FILE (the reference's
     // MADRONA_MWGPU_EXEC_CONFIG_FILE, cuda_exec.cpp:2115-2172): per task-graph
@@ -469,6 +480,7 @@ struct mwhip_exec {
     ExecObjectTable<mwhip_rays_rec> rays;          // mwhip_rays_create
     ExecObjectTable<mwhip_boxes_rec> boxes;        // mwhip_boxes_create
     ExecObjectTable<mwhip_contacts_rec> contacts;  // mwhip_contacts_create
+    ExecObjectTable<mwhip_shapes_rec> shapes;      // mwhip_shapes_create
 };
 
 // Bumped by what changes device memory or fails without naming an executor
@@ -562,6 +574,9 @@ MWHIP_RT int stepBoxesStage(mwhip_exec *exec, const LaunchGraph &lg,
 MWHIP_RT int stepContactsStage(mwhip_exec *exec, const LaunchGraph &lg,
                                std::vector<KernelLaunch> &out);
       // (contact_query.hip)
+MWHIP_RT int stepShapesStage(mwhip_exec *exec, const LaunchGraph &lg,
+                             std::vector<KernelLaunch> &out);
+      // (shape_query.hip)
 MWHIP_RT int stepScatterStage(mwhip_exec *exec, const LaunchGraph &lg,
                               std::vector<KernelLaunch> &out);
       // (entity_scatter.hip)

@@ -2,9 +2,10 @@
 // views (world_view.hip), world writes (world_write.hip), world reduces
 // (world_reduce.hip), entity gathers (entity_gather.hip), entity scatters
 // (entity_scatter.hip), ray queries (ray_query.hip), box queries
-// (box_query.hip) and contact queries (contact_query.hip) share on the host
-// (what the last eight share as step-batched objects is in
-// step_batch.hpp, what the last three share besides in tree_query.hpp).  An
+// (box_query.hip), contact queries (contact_query.hip) and shape queries
+// (shape_query.hip) share on the host
+// (what the last nine share as step-batched objects is in
+// step_batch.hpp, what the last four share besides in tree_query.hpp).  An
 // executor object
 // is a record with device memory of its own, made by mwhip_<kind>_create, named
 // by a handle, used through mwhip_<kind>_* and freed by mwhip_<kind>_destroy or

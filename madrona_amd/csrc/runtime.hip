@@ -689,6 +689,7 @@ extern "C" void mwhip_destroy(mwhip_exec *exec)
     exec->rays.clear();
     exec->boxes.clear();
     exec->contacts.clear();
+    exec->shapes.clear();
     for (void *p : exec->allocations) {
         (void)hipFree(p);
     }

@@ -1181,8 +1181,9 @@ static int packStage(mwhip_exec *, const LaunchGraph &lg, std::vector<KernelLaun
 // THE ORDER IS A CONTRACT.  What derives tensors from the step's state (the
 // render pass, the step digest, the step views, the step ray queries and the
 // step box queries -- whose origins and centres may be a step view's slab --,
-// the step contact queries, the step gathers -- which may read a step view's
-// slab, a ray or box query's hits or a contact query's pairs --, the step
+// the step contact queries, the step shape queries, the step gathers -- which
+// may read a step view's slab, a ray, box or shape query's hits or a contact
+// query's pairs --, the step
 // reduces) comes first, so that what
 // carries tensors away (the pack node, the output rings) sees this step's
 // values: a ring over a view's buffer records the view of the same replay.
@@ -1193,6 +1194,7 @@ static constexpr TailStage kTailStages[] = {
     stepRaysStage,      // step graphs, mwhip_set_step_rays (ray_query.hip)
     stepBoxesStage,     // step graphs, mwhip_set_step_boxes (box_query.hip)
     stepContactsStage,  // step graphs, mwhip_set_step_contacts (contact_query.hip)
+    stepShapesStage,    // step graphs, mwhip_set_step_shapes (shape_query.hip)
     stepGatherStage,    // step graphs, mwhip_set_step_gather (entity_gather.hip)
     stepReduceStage,    // step graphs, mwhip_set_step_reduce (world_reduce.hip)
     packStage,          // mwhip_build_launch_graph_with_pack

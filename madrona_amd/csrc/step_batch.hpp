@@ -1,6 +1,6 @@
 // Step-batched executor objects: what world views, world writes, world reduces,
-// entity gathers, entity scatters, ray queries, box queries and contact queries
-// share on the host beyond exec_objects.hpp.  Such an object can be computed (or
+// entity gathers, entity scatters, ray queries, box queries, contact queries and shape
+// queries share on the host beyond exec_objects.hpp.  Such an object can be computed (or
 // applied) alone, or be SET: every step replay then serves all set objects of
 // its kind in ONE launch whose argument is a batch of their plans
 // (madrona/mwhip/plan_batch.hpp).  Here, once: the step set and its cap, the
@@ -78,7 +78,7 @@ inline dim3 waveGrid(const mwhip_exec *exec, uint32_t items, uint32_t waves_per_
 }
 
 // The batch of ONE object: what a compute or an apply launches with.  Args is a
-// PlanBatch, mwhip_ray_args, mwhip_box_args or mwhip_contact_args; a record has
+// PlanBatch, mwhip_ray_args, mwhip_box_args, mwhip_contact_args or mwhip_shape_args; a record has
 // items and planDev.
 template <typename Args, typename Rec>
 inline Args singleBatch(const Rec &rec)

@@ -5,8 +5,8 @@
 // owned buffer or a mwhip_ray_source of the caller's, or, for the world, the
 // rule world = group / groups_per_world.  Here, once: the record, its one
 // allocation, the refusals about the sources, where the kernel reads an item,
-// the _buffer accessor.  Contact queries (contact_query.hip), which go through
-// no tree, use the record, the allocation, the item source and the accessor.
+// the _buffer accessor.  Contact queries (contact_query.hip) and shape queries
+// (shape_query.hip), which go through no tree, use the record, the allocation, the item source and the accessor.
 // Host code only; included behind exec_internal.hpp.
 // Not installed.
 #pragma once

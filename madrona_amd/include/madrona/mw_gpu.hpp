@@ -178,7 +178,7 @@ namespace detail {
 
 // What MWHipSnapshot, MWHipDigest, MWHipWorldView, MWHipWorldWrite,
 // MWHipWorldReduce, MWHipEntityGather, MWHipEntityScatter, MWHipRayQuery,
-// MWHipBoxQuery and MWHipContactQuery share: the move-only handle
+// MWHipBoxQuery, MWHipContactQuery and MWHipShapeQuery share: the move-only handle
 // of an object that belongs to an executor (mwhip_<kind>_create / _destroy,
 // include/mwhip.h), the device its buffers are on, and how one of those
 // buffers becomes a py::Tensor.  Kind: { name, destroy(exec, handle) }.
@@ -294,6 +294,10 @@ struct BoxQueryKind {
 struct ContactQueryKind {
     static constexpr const char *name = "contact query";
     static void destroy(mwhip_exec *exec, uint64_t handle) { mwhip_contacts_destroy(exec, handle); }
+};
+struct ShapeQueryKind {
+    static constexpr const char *name = "shape query";
+    static void destroy(mwhip_exec *exec, uint64_t handle) { mwhip_shapes_destroy(exec, handle); }
 };
 
 }
@@ -854,6 +858,134 @@ private:
 friend class MWCudaExecutor;
 };
 
+// "If this object stood THERE, what would it touch, where, and how deep?":
+// numShapes() = numBundles() x shapes-per-bundle posed collision shapes, the
+// shapes of a bundle in one world, each tested against the rigid bodies of its
+// world with the step's narrowphase.  Per shape int32 status (MWHIP_SHAPES_OK,
+// _SKIPPED, _BAD_WORLD, _BAD_SHAPE, _UNSORTED, _UNSUPPORTED), int32 count (not
+// capped) and the first maxHits() hits in the order (body, primitive pair): the
+// Entity of the body touched, whether the contact's reference side is the
+// shape, the number of points, the normal, and four points (xyz world position,
+// w depth; zero from the number of points on).  mwhip_shapes_*, include/mwhip.h,
+// is the exact definition: which pairs are tested, at the bodies' current
+// poses, that no BVH is walked.  Needs a simulator that sets up a rigid-body
+// step.  An extension of this backend.  Belongs to the executor that made it
+// and must not outlive it, nor its sources.
+class MWHipShapeQuery : public detail::ExecObject<detail::ShapeQueryKind> {
+public:
+    MWHipShapeQuery() : num_bundles_(0), num_shapes_(0), max_hits_(0) {}
+
+    // waits for the executor's stream
+    void compute() { req(mwhip_shapes_compute(exec_, handle_), "compute"); }
+    // queued on the executor's stream behind the replays queued so far
+    void computeAsync() { req(mwhip_shapes_compute_async(exec_, handle_), "computeAsync"); }
+
+    // inputs the query owns: int32 [numBundles()] (no world source, no
+    // bundles_per_world), int32 [numShapes()][2] (gen, id; no exclude source),
+    // int32 [numShapes()], float [numShapes()][3], [numShapes()][4] (w, x, y, z)
+    // and [numShapes()][3]
+    py::Tensor worldsTensor() const
+    {
+        return tensor(buffer(MWHIP_SHAPES_BUF_WORLD), Elem::Int32, { num_bundles_ },
+                      "worldsTensor");
+    }
+    py::Tensor excludesTensor() const
+    {
+        return tensor(buffer(MWHIP_SHAPES_BUF_EXCLUDE), Elem::Int32, { num_shapes_, 2 },
+                      "excludesTensor");
+    }
+    py::Tensor objectsTensor() const
+    {
+        return tensor(buffer(MWHIP_SHAPES_BUF_OBJECT), Elem::Int32, { num_shapes_ },
+                      "objectsTensor");
+    }
+    py::Tensor positionsTensor() const
+    {
+        return tensor(buffer(MWHIP_SHAPES_BUF_POSITION), Elem::Float32, { num_shapes_, 3 },
+                      "positionsTensor");
+    }
+    py::Tensor rotationsTensor() const
+    {
+        return tensor(buffer(MWHIP_SHAPES_BUF_ROTATION), Elem::Float32, { num_shapes_, 4 },
+                      "rotationsTensor");
+    }
+    py::Tensor scalesTensor() const
+    {
+        return tensor(buffer(MWHIP_SHAPES_BUF_SCALE), Elem::Float32, { num_shapes_, 3 },
+                      "scalesTensor");
+    }
+
+    // outputs: int32 [numShapes()] twice; int32 [numShapes()][maxHits()][2]
+    // (gen, id); int32 [numShapes()][maxHits()] twice; float
+    // [numShapes()][maxHits()][3]; float [numShapes()][maxHits()][16]
+    py::Tensor statusTensor() const
+    {
+        return tensor(buffer(MWHIP_SHAPES_BUF_STATUS), Elem::Int32, { num_shapes_ },
+                      "statusTensor");
+    }
+    py::Tensor countsTensor() const
+    {
+        return tensor(buffer(MWHIP_SHAPES_BUF_COUNT), Elem::Int32, { num_shapes_ },
+                      "countsTensor");
+    }
+    py::Tensor hitsTensor() const
+    {
+        return tensor(buffer(MWHIP_SHAPES_BUF_HITS), Elem::Int32, { num_shapes_, max_hits_, 2 },
+                      "hitsTensor");
+    }
+    py::Tensor shapeIsRefTensor() const
+    {
+        return tensor(buffer(MWHIP_SHAPES_BUF_SHAPE_IS_REF), Elem::Int32,
+                      { num_shapes_, max_hits_ }, "shapeIsRefTensor");
+    }
+    py::Tensor numPointsTensor() const
+    {
+        return tensor(buffer(MWHIP_SHAPES_BUF_NUM_POINTS), Elem::Int32,
+                      { num_shapes_, max_hits_ }, "numPointsTensor");
+    }
+    py::Tensor normalsTensor() const
+    {
+        return tensor(buffer(MWHIP_SHAPES_BUF_NORMAL), Elem::Float32,
+                      { num_shapes_, max_hits_, 3 }, "normalsTensor");
+    }
+    py::Tensor pointsTensor() const
+    {
+        return tensor(buffer(MWHIP_SHAPES_BUF_POINTS), Elem::Float32,
+                      { num_shapes_, max_hits_, 16 }, "pointsTensor");
+    }
+
+    // the hits as the source of an entity gather or scatter: numShapes() x
+    // maxHits() handles
+    mwhip_gather_source handleSource() const
+    {
+        void *ptr = buffer(MWHIP_SHAPES_BUF_HITS);
+        req(ptr != nullptr ? 0 : -1, "handleSource");
+        return mwhip_gather_source { ptr, num_shapes_ * max_hits_, 8u, 0u, 1u, 0u };
+    }
+
+    uint64_t numBundles() const { return num_bundles_; }
+    uint64_t numShapes() const { return num_shapes_; }
+    uint64_t maxHits() const { return max_hits_; }
+
+private:
+    MWHipShapeQuery(mwhip_exec *exec, uint64_t shapes, uint64_t num_bundles,
+                    uint64_t num_shapes, uint64_t max_hits, int32_t gpu_id)
+        : ExecObject(exec, shapes, gpu_id), num_bundles_(num_bundles), num_shapes_(num_shapes),
+          max_hits_(max_hits)
+    {}
+
+    void *buffer(uint32_t which) const
+    {
+        return mwhip_shapes_buffer(exec_, handle_, which, nullptr);
+    }
+
+    uint64_t num_bundles_;
+    uint64_t num_shapes_;
+    uint64_t max_hits_;
+
+friend class MWCudaExecutor;
+};
+
 // The batched ctx.get<T>(e) = v: per listed component uint8 [N][cell bytes] on
 // the device and int32 [N] select, filled by the caller; apply() stores cell i
 // into the entity handle i of the source names, where select[i] != 0, and among
@@ -1386,6 +1518,27 @@ public:
     void setStepContacts(const MWHipContactQuery *contacts, bool on)
     {
         setStep(mwhip_set_step_contacts, contacts, "setStepContacts", on ? 1 : 0);
+    }
+
+    // desc.num_bundles x desc.shapes_per_bundle posed collision shapes tested
+    // against the bodies of their worlds, up to desc.max_hits hits each with
+    // their manifolds (see MWHipShapeQuery and mwhip_shapes_desc)
+    MWHipShapeQuery makeShapeQuery(const mwhip_shapes_desc &desc)
+    {
+        uint64_t shapes = 0;
+        req(mwhip_shapes_create(exec_, &desc, &shapes), "makeShapeQuery");
+        return MWHipShapeQuery(exec_, shapes, desc.num_bundles,
+                               (uint64_t)desc.num_bundles * desc.shapes_per_bundle,
+                               desc.max_hits, gpu_id_);
+    }
+
+    // on: every replay of a step graph recomputes `shapes` directly behind its
+    // step contact queries and in front of its step gathers (which may read
+    // the hits), its pack node and its output rings (up to
+    // MWHIP_MAX_STEP_SHAPES queries, one launch for all); off: no longer
+    void setStepShapes(const MWHipShapeQuery *shapes, bool on)
+    {
+        setStep(mwhip_set_step_shapes, shapes, "setStepShapes", on ? 1 : 0);
     }
 
     // Device-resident rings (extensions of this backend, include/mwhip.h).

@@ -1751,6 +1751,10 @@ bvhUpdateKernel(EcsState *S, void *, uint32_t, uint32_t)
 #include <madrona/phys_impl/box_query.inl>
 // the contact queries' kernel (mwhip_contacts_*): contactQueryKernel
 #include <madrona/phys_impl/contact_query.inl>
+// what kernels that run the narrowphase from outside the step store of a manifold
+#include <madrona/phys_impl/query_store.inl>
+// the shape queries' kernel (mwhip_shapes_*): shapeQueryKernel
+#include <madrona/phys_impl/shape_query.inl>
 }
 #endif // __HIPCC__
 
@@ -2550,6 +2554,13 @@ MADRONA_HOST_API inline TaskGraphNodeID setupPhysicsStepTasks(
 #else
     auto contact_stub = []() -> const void * { return nullptr; };
 #endif
+#if defined(__HIPCC__)
+    [[maybe_unused]] auto shape_stub = [] __host__ () -> const void * {
+        return (const void *)&kernels::shapeQueryKernel;
+    };
+#else
+    auto shape_stub = []() -> const void * { return nullptr; };
+#endif
 #if MADRONA_ON_HOST
     // a simulator with a rigid-body step has contact queries
     // (mwhip_contacts_create): the narrowphase is in this code object, the
@@ -2565,6 +2576,13 @@ MADRONA_HOST_API inline TaskGraphNodeID setupPhysicsStepTasks(
     mwhip::check(mwhip_set_contact_kernel(builder.exec(), contact_stub(),
                      solver == Solver::TGS ? 0u : MWHIP_CONTACT_CAP_SOLVER_POSES),
                  "set_contact_kernel");
+    // ... and shape queries (mwhip_shapes_create): the same narrowphase on
+    // posed shapes that are no table rows.  Two wavefronts of that kernel may
+    // be in the same world, so its one-lane-at-a-time hull scratch is a slot
+    // per wavefront of a block the runtime owns, not the world's.
+    mwhip::check(mwhip_set_shape_kernel(builder.exec(), shape_stub(),
+                                        PhysicsScratch::hullScratchBytes),
+                 "set_shape_kernel");
 #endif
 
     if (solver == Solver::TGS) {

@@ -168,6 +168,14 @@ class ContactsDesc(C.Structure):
                 ("own_select", C.c_uint32), ("pad_", C.c_uint32), ("select", RaySource)]
 
 
+class ShapesDesc(C.Structure):
+    """mwhip_shapes_desc (include/mwhip.h)."""
+    _fields_ = [("num_bundles", C.c_uint32), ("shapes_per_bundle", C.c_uint32),
+                ("max_hits", C.c_uint32), ("num_objects", C.c_uint32),
+                ("bundles_per_world", C.c_uint32), ("flags", C.c_uint32),
+                ("world", RaySource), ("count", RaySource), ("exclude", RaySource)]
+
+
 class SortStats(C.Structure):
     """mwhip_sort_counters (include/mwhip.h)"""
     _fields_ = [(name, C.c_uint64) for name in
@@ -208,6 +216,7 @@ _KINDS = {
     "rays": (("compute",), ()),
     "boxes": (("compute",), ()),
     "contacts": (("compute",), ()),
+    "shapes": (("compute",), ()),
 }
 
 _runtime = None
@@ -286,12 +295,14 @@ def runtime_lib() -> C.CDLL:
                  [C.c_void_p, C.POINTER(GatherSource), _U32P, C.c_uint32, _U64P])
     for stem in ("view", "write", "reduce", "gather", "scatter"):
         _declare(lib, f"mwhip_{stem}_buffer", C.c_void_p, _OBJECT + [C.c_uint32, _U64P, _U32P])
-    for stem, desc in (("rays", RaysDesc), ("boxes", BoxesDesc), ("contacts", ContactsDesc)):
+    for stem, desc in (("rays", RaysDesc), ("boxes", BoxesDesc), ("contacts", ContactsDesc),
+                       ("shapes", ShapesDesc)):
         _declare(lib, f"mwhip_{stem}_create", C.c_int, [C.c_void_p, C.POINTER(desc), _U64P])
         _declare(lib, f"mwhip_{stem}_buffer", C.c_void_p, _OBJECT + [C.c_uint32, _U64P])
     _declare(lib, "mwhip_set_ray_kernel", C.c_int, [C.c_void_p, C.c_void_p])
     _declare(lib, "mwhip_set_box_kernel", C.c_int, [C.c_void_p, C.c_void_p])
     _declare(lib, "mwhip_set_contact_kernel", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32])
+    _declare(lib, "mwhip_set_shape_kernel", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32])
     _runtime = lib
     return lib
 
@@ -327,7 +338,7 @@ class _Checked:
 
 
 class _ExecObject(_Checked):
-    """What Snapshot, StateDigest, WorldView, WorldWrite, WorldReduce, EntityGather, EntityScatter, RayQuery, BoxQuery and ContactQuery are: something a simulator's
+    """What Snapshot, StateDigest, WorldView, WorldWrite, WorldReduce, EntityGather, EntityScatter, RayQuery, BoxQuery, ContactQuery and ShapeQuery are: something a simulator's
     executor owns, named by `handle` there, kept in one of the simulator's
     lists (`_list`) while it is open.  close() frees it and takes it off the
     list (a snapshot too, which used to stay on it until the simulator closed); Simulator.close() frees the executor and orphans
@@ -1151,7 +1162,7 @@ class EntityScatter(_Applied, _HandleCells):
 
 
 class _Sourced:
-    """What RayQuery, BoxQuery and ContactQuery share: inputs that may be read
+    """What RayQuery, BoxQuery, ContactQuery and ShapeQuery share: inputs that may be read
     from the caller's source (mwhip_ray_source)."""
 
     _what = ""      # in messages
@@ -1504,6 +1515,154 @@ class ContactQuery(_Computed, _Sourced, _StepObject):
         return (self.buffer_ptr("pairs"), self.num_worlds * self.max_contacts * 2, 8, 0, 1)
 
 
+class ShapeQuery(_Computed, _Sourced, _StepObject):
+    """"If this object stood THERE, what would it touch, where, and how deep?":
+    S = bundles x shapes_per_bundle posed collision shapes, the shapes of a
+    bundle in one world, each tested against the rigid bodies of its world with
+    the physics step's narrowphase (mwhip_shapes_*, include/mwhip.h;
+    madrona_amd/shape_ref.py is the exact definition).  Shape s = f * G + g is
+    shape g of bundle f.  Inputs: worlds() int32 [F] and excludes() int32 [S, 2]
+    (gen, id) -- each owned unless a source was given, a device tensor or (ptr,
+    record_bytes, first_byte), read when the kernel runs and kept in place while
+    the query exists; bundles_per_world > 0 replaces worlds() by world = f //
+    bundles_per_world, and `count`, an int32 per world, then SKIPS bundles f %
+    bundles_per_world >= count[world] --, and, always owned, objects() int32 [S]
+    (an object of the simulator's ObjectManager, < num_objects), positions()
+    float32 [S, 3], rotations() float32 [S, 4] (w, x, y, z) and scales() float32
+    [S, 3]; at creation object 0 at the identity pose and unit scale in world 0,
+    excluding nothing.  A body whose Entity equals a shape's exclude is not
+    tested against it (the agent itself).  Every other body of the world, Static
+    ones included, is tested at its CURRENT Position, Rotation and Scale, every
+    primitive pair c = shapePrim * body_num_prims + bodyPrim of it, the shape as
+    the step's `a`; a pair is a hit iff the primitives' world boxes intersect
+    and the narrowphase returns at least one point.  Hits come in the order
+    (body k, c).  No BVH is walked.  Outputs, rewritten in full by every compute,
+    zero-copy torch tensors: status() int32 [S] (OK 0, SKIPPED -1, BAD_WORLD -2,
+    BAD_SHAPE -3, UNSORTED -4, UNSUPPORTED -5), counts() int32 [S] (not capped by
+    K, 0 unless OK), hits() int32 [S, K, 2] ((gen, id) of the body touched; -1,
+    -1 behind min(count, K)), shape_is_ref() int32 [S, K] (1: the contact's
+    reference side is the shape, and the normal points out of the shape; 0: out
+    of the body), num_points() int32 [S, K], normals() float32 [S, K, 3],
+    points() float32 [S, K, 4, 4] (xyz world position, w depth; zero from
+    num_points on and behind min(count, K)).  What torch writes into the inputs
+    on its own stream must have landed before a compute or a step reads it.
+    handle_source() is what entity_gather() / entity_scatter() take to go from
+    hits to cells.  plain=True sends every pair through the generic single-lane
+    routine, one at a time: the same words.  compute() waits for the executor's
+    stream, compute_async() queues behind the replays queued so far;
+    every_step() makes every replay of a step graph recompute the query behind
+    its step contact queries and in front of its step gathers and output rings.
+    HIP backend only."""
+
+    _kind, _stem, _list = "shape query", "shapes", "_shape_queries"
+    OK, SKIPPED, BAD_WORLD, BAD_SHAPE, UNSORTED, UNSUPPORTED = 0, -1, -2, -3, -4, -5
+    PLAIN = 1
+    _BUFS = {"world": 0, "exclude": 1, "object": 2, "position": 3, "rotation": 4, "scale": 5,
+             "status": 6, "count": 7, "hits": 8, "shape_is_ref": 9, "num_points": 10,
+             "normal": 11, "points": 12}
+    _what = "shape_query()"
+
+    def __init__(self, sim: "Simulator", bundles: int, shapes_per_bundle: int, max_hits: int,
+                 num_objects: int, world=None, bundles_per_world: int = 0, count=None,
+                 exclude=None, plain: bool = False):
+        self.num_bundles, self.shapes_per_bundle = int(bundles), int(shapes_per_bundle)
+        self.num_shapes = self.num_bundles * self.shapes_per_bundle
+        self.max_hits, self.num_objects = int(max_hits), int(num_objects)
+        self.bundles_per_world, self.plain = int(bundles_per_world), bool(plain)
+        self._open(sim)
+        desc = ShapesDesc(self.num_bundles, self.shapes_per_bundle, self.max_hits,
+                          self.num_objects, self.bundles_per_world,
+                          self.PLAIN if self.plain else 0)
+        keep_w, desc.world = self._source("world", world, 4)
+        keep_c, desc.count = self._source("count", count, 4)
+        keep_e, desc.exclude = self._source("exclude", exclude, 8)
+        self._sources = (keep_w, keep_c, keep_e)    # (stay where they are)
+        self._create(C.byref(desc))
+        self._owned = {"world": world is None and self.bundles_per_world == 0,
+                       "exclude": exclude is None}
+
+    def _orphan(self) -> None:
+        super()._orphan()
+        self._sources = ()
+
+    def buffer_ptr(self, name: str) -> int:
+        """Device address of owned buffer `name` (a key of _BUFS)."""
+        handle = self._live()
+        nbytes = C.c_uint64(0)
+        ptr = self._rt.mwhip_shapes_buffer(self._exec, handle, self._BUFS[name], C.byref(nbytes))
+        if not ptr:
+            raise RuntimeError(
+                f"mwhip_shapes_buffer({name}): {self._rt.mwhip_last_error().decode()}")
+        return int(ptr)
+
+    def _tensor(self, name, dtype, shape):
+        self._live()
+        if not self._owned.get(name, True):
+            raise RuntimeError(f"this shape query owns no {name} buffer: " + (
+                "bundles_per_world gives each bundle its world" if name == "world"
+                and self.bundles_per_world else f"a {name} source was given"))
+        if name not in self._tensors:
+            self._wrap(name, self.buffer_ptr(name), dtype, shape)
+        return self._tensors[name]
+
+    def worlds(self):
+        """int32 [F] (owned: no world source and no bundles_per_world)"""
+        return self._tensor("world", np.int32, (self.num_bundles,))
+
+    def excludes(self):
+        """int32 [S, 2]: (gen, id), -1, -1 (nothing) at creation (owned: no exclude source)"""
+        return self._tensor("exclude", np.int32, (self.num_shapes, 2))
+
+    def objects(self):
+        """int32 [S]"""
+        return self._tensor("object", np.int32, (self.num_shapes,))
+
+    def positions(self):
+        """float32 [S, 3]"""
+        return self._tensor("position", np.float32, (self.num_shapes, 3))
+
+    def rotations(self):
+        """float32 [S, 4]: w, x, y, z"""
+        return self._tensor("rotation", np.float32, (self.num_shapes, 4))
+
+    def scales(self):
+        """float32 [S, 3]"""
+        return self._tensor("scale", np.float32, (self.num_shapes, 3))
+
+    def status(self):
+        """int32 [S]: OK 0, SKIPPED -1, BAD_WORLD -2, BAD_SHAPE -3, UNSORTED -4, UNSUPPORTED -5"""
+        return self._tensor("status", np.int32, (self.num_shapes,))
+
+    def counts(self):
+        """int32 [S]: the shape's hits, not capped by max_hits"""
+        return self._tensor("count", np.int32, (self.num_shapes,))
+
+    def hits(self):
+        """int32 [S, K, 2]: (gen, id) of the body touched; -1 behind min(count, K)"""
+        return self._tensor("hits", np.int32, (self.num_shapes, self.max_hits, 2))
+
+    def shape_is_ref(self):
+        """int32 [S, K]: 1 where the contact's reference side is the shape"""
+        return self._tensor("shape_is_ref", np.int32, (self.num_shapes, self.max_hits))
+
+    def num_points(self):
+        """int32 [S, K]"""
+        return self._tensor("num_points", np.int32, (self.num_shapes, self.max_hits))
+
+    def normals(self):
+        """float32 [S, K, 3]"""
+        return self._tensor("normal", np.float32, (self.num_shapes, self.max_hits, 3))
+
+    def points(self):
+        """float32 [S, K, 4, 4]: xyz world position, w penetration depth"""
+        return self._tensor("points", np.float32, (self.num_shapes, self.max_hits, 4, 4))
+
+    def handle_source(self):
+        """The hits as a source of Simulator.entity_gather() / entity_scatter():
+        (ptr, num_records, record_bytes, first_byte, handles_per_record)."""
+        return (self.buffer_ptr("hits"), self.num_shapes * self.max_hits, 8, 0, 1)
+
+
 class Simulator:
     """One simulator instance behind the C API (either backend)."""
 
@@ -1529,7 +1688,7 @@ class Simulator:
         self._async = None
         # what is open, a list per kind, named by the class's `_list`: _snapshots,
         # _digests, _views, _writes, _reduces, _gathers, _scatters, _ray_queries,
-        # _box_queries, _contact_queries; and _trajectories
+        # _box_queries, _contact_queries, _shape_queries; and _trajectories
         self._trajectories: List["Trajectory"] = []
         for name in _ExecObject._lists:
             setattr(self, name, [])
@@ -1813,6 +1972,22 @@ class Simulator:
         after pair (same words).  Simulator.close() frees what is left open."""
         return self._make(ContactQuery, "contact queries need", max_contacts, select, poses,
                           plain)
+
+    def shape_query(self, bundles: int, shapes_per_bundle: int, max_hits: int, num_objects: int,
+                    world=None, bundles_per_world: int = 0, count=None, exclude=None,
+                    plain: bool = False) -> "ShapeQuery":
+        """A ShapeQuery: `bundles` x `shapes_per_bundle` posed collision shapes
+        tested against the rigid bodies of their worlds, up to `max_hits` hits
+        each with their manifolds (HIP backend, a simulator with a rigid-body
+        step).  num_objects: how many objects the simulator's ObjectManager
+        holds.  world, exclude: None (owned buffers, worlds() / excludes()), a
+        device tensor whose rows are the records or (ptr, record_bytes,
+        first_byte); bundles_per_world > 0: world = f // bundles_per_world, and
+        count (an int32 per world) skips the bundles at or past it.  plain: the
+        generic routine, pair after pair (same words).  Simulator.close() frees
+        what is left open."""
+        return self._make(ShapeQuery, "shape queries need", bundles, shapes_per_bundle, max_hits,
+                          num_objects, world, bundles_per_world, count, exclude, plain)
 
     def record(self, names: List[str], steps: int, on_render: bool = False) -> "Trajectory":
         """Records the exported tensors `names` on the device from the next

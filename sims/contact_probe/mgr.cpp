@@ -29,7 +29,15 @@ struct SimTraits {
     using Engine = contactprobe::Engine;
 
     static constexpr uint32_t numExports = (uint32_t)contactprobe::ExportID::NumExports;
+    // (the probes exist on the HIP backend only: sim.cpp)
+#ifdef SIM_BACKEND_REF_CPU
     static constexpr uint32_t numTaskGraphs = 1;
+#else
+    static constexpr uint32_t numTaskGraphs =
+        (uint32_t)contactprobe::TaskGraphID::NumTaskGraphs;
+#endif
+    // sim_step replays task graph 0 only (the others are test probes)
+    static constexpr bool stepIsTaskGraph0 = true;
 
     static Sim::Config makeConfig(const SimCreateArgs &args)
     {

@@ -46,9 +46,27 @@ inline void countSystem(Engine &, StepCount &steps)
     steps.n += 1;
 }
 
+#ifdef MADRONA_GPU_MODE
+inline void appendSystem(Engine &ctx, StepCount &)
+{
+    makeBody(ctx, Vector3 { 0.f, 0.f, 200.f }, Quat { 1, 0, 0, 0 },
+             Diag3x3 { 1.f, 1.f, 1.f }, SimObject::Cube, ResponseType::Static);
+}
+#endif
+
 void Sim::setupTasks(TaskGraphManager &taskgraph_mgr, const Config &)
 {
-    TaskGraphBuilder &builder = taskgraph_mgr.init(0);
+#ifdef MADRONA_GPU_MODE
+    {
+        TaskGraphBuilder &b = taskgraph_mgr.init(TaskGraphID::AppendOnly);
+        b.addToGraph<ParallelForNode<Engine, appendSystem, StepCount>>({});
+    }
+    {
+        TaskGraphBuilder &b = taskgraph_mgr.init(TaskGraphID::CompactOnly);
+        b.addToGraph<CompactArchetypeNode<Body>>({});
+    }
+#endif
+    TaskGraphBuilder &builder = taskgraph_mgr.init(TaskGraphID::Step);
 
     auto count = builder.addToGraph<ParallelForNode<Engine,
         countSystem, StepCount>>({});

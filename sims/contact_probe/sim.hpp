@@ -5,7 +5,9 @@
 // the worlds a query must get right besides: only static bodies, no bodies,
 // more than 64 bodies.  Its dump list has what the definition of a contact
 // reads, Scale, ObjectID and ResponseType included.  Compiled unchanged against
-// the reference CPU backend (oracle) and the HIP backend.
+// the reference CPU backend (oracle) and the HIP backend.  (On the HIP backend
+// two more task graphs, test probes, leave the Body table unsorted and sort it
+// again: TaskGraphID.)
 #pragma once
 
 #include <madrona/taskgraph_builder.hpp>
@@ -34,6 +36,11 @@ inline constexpr int32_t crowdedLayers = 2;
 
 enum class SimObject : int32_t { Cube, Plane, Sphere, NumObjects };
 enum class ExportID : uint32_t { StepCount, NumExports };
+// Step is the simulator; the other two are test probes of the HIP backend
+// (tests/test_shape_query_gpu.py): AppendOnly gives every world one more static
+// cube, far above everything, and sorts nothing, so that the Body table waits
+// for its world sort; CompactOnly is the sort it waits for.
+enum class TaskGraphID : uint32_t { Step, AppendOnly, CompactOnly, NumTaskGraphs };
 
 struct StepCount { int32_t n; };
 
